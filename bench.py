@@ -17,14 +17,26 @@ rank's device-resident shard of the synthetic stream:
 relays their output and exit code; under the driver's launcher (WORLD_SIZE set) it
 is one of the ranks.
 
-After the timed window every rank verifies its own index array ON THE DEVICE against
-the replication property (tests/replication.py: every index, placed with the offsets
-the stitch returned) and contributes a 64-bit hash to one all-gather; rank 0 compares
-the sum with the closed form of the oracle's unit indices: `config.verified`.
+A plain run does what the headline needs: set-up, W warm-up steps, the settle passes,
+the K timed steps, the total count checked against the oracle's unit count
+(`config.verified: "count"`), and the line.  `--full` adds everything else the line
+can carry, each outside the timed window:
+  * the `unsettled` window (the K steps right after the warm-up, before the settle),
+  * N = 1: the per-step distribution (`per_step_ms`), the box's own HBM ceilings,
+    the sub-records of BASELINE configs 3 and 4 (`other_configs`), `cpu_baseline`
+    (the oracle's block-for-block restatement of the reference, 1 thread, bounded
+    sample) and `end_to_end`;
+  * N > 1: each rank's standalone pass behind `scaling_efficiency`;
+  * the index-by-index verification: every rank checks its own index array ON THE
+    DEVICE against the replication property (tests/replication.py: every index,
+    placed with the offsets the stitch returned) and contributes a 64-bit hash to
+    one all-gather; rank 0 compares the sum with the closed form of the oracle's
+    unit indices (`config.verified: "indices"`).
+
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs()).
 
 Output: ONE JSON line on rank 0 (contract in the task statement), with
-`roofline` for the dominant kernel (stage1_kernel) and `cpu_baseline` (the
-oracle's block-for-block restatement of the reference, 1 thread, bounded sample).
+`roofline` for the dominant kernel (stage1_kernel).
 """
 import argparse
 import json
@@ -63,6 +75,35 @@ def unit_indices(unit):
     rc = f.msj_fast_stage1(data, len(data), idx.ctypes.data, idx.size, ctypes.byref(nn))
     assert rc == 0, f"the oracle rejects the synthetic unit: {rc}"
     return idx[: int(nn.value)].copy()
+
+
+DUMP_SAMPLE = 1 << 22  # entries of the index array in --dump-outputs (float64: 32 MiB)
+DUMP_SEED = 0
+
+
+def dump_positions(n, size=DUMP_SAMPLE, seed=DUMP_SEED):
+    """Sorted, distinct positions of a fixed sample of n entries: all of them if n <= size, else one seeded random
+    position in each of `size` equal strata -- the same positions for the same n in every run."""
+    if n <= size:
+        return np.arange(n, dtype=np.int64)
+    lo = np.arange(size, dtype=np.int64) * n // size
+    hi = np.arange(1, size + 1, dtype=np.int64) * n // size
+    return lo + (np.random.default_rng(seed).random(size) * (hi - lo)).astype(np.int64)
+
+
+def dump_outputs(out_dir, suffix, d_idx, n_entries, code, total_count, carry):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 .npy files (the inputs
+    are the same in every run with the same arguments, so two builds compare file for file):
+      result<suffix>.npy              [code, total count, then every scalar field of this rank's msj_carry in order]
+      structural_indexes<suffix>.npy  d_idx[p] as uint32 at dump_positions(n_entries): indices and trailer
+    d_idx is None when the step wrote no indices (--no-emit)."""
+    os.makedirs(out_dir, exist_ok=True)
+    fields = [code, total_count] + [getattr(carry, name) for name, ctype in carry._fields_ if not hasattr(ctype, "_length_")]
+    np.save(os.path.join(out_dir, f"result{suffix}.npy"), np.asarray(fields, dtype=np.float64))
+    if d_idx is not None:
+        pos = torch.from_numpy(dump_positions(min(n_entries, d_idx.numel()))).to(d_idx.device)
+        vals = (d_idx[pos].to(torch.int64) & 0xFFFFFFFF).cpu().numpy().astype(np.float64)
+        np.save(os.path.join(out_dir, f"structural_indexes{suffix}.npy"), vals)
 
 
 def cpu_baseline(unit, budget_s=10.0):
@@ -483,6 +524,13 @@ def main():
                     help="skip the sub-records of BASELINE configs 3 and 4 (`other_configs`; N = 1, default workload only)")
     ap.add_argument("--no-emit", action="store_true",
                     help="diagnostic: summary pass only, no index writes (never a reported number)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (module docstring): the unsettled window, "
+                         "per-step distribution, ceilings, other_configs, index verification, CPU baseline, end_to_end, "
+                         "scaling_efficiency; the --no-* options above switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float64): result.npy and a fixed, seeded "
+                         "sample of the index array (dump_outputs())")
     args = ap.parse_args()
     if args.gib_per_gpu is None:
         args.gib_per_gpu = 1.0 if args.gpus == 1 else 8.0
@@ -650,9 +698,10 @@ def main():
     unsettled = None
     settle_steps = 0
     if args.settle_ms > 0:
-        # (a) the K steps as they run right after W warm-up steps on a GPU that was idle: reported, not `value`
-        u_dt, u_ev, _ = timed_window()
-        unsettled = (u_dt, u_ev)
+        # (a) --full: the K steps as they run right after W warm-up steps on a GPU that was idle: reported, not `value`
+        if args.full:
+            u_dt, u_ev, _ = timed_window()
+            unsettled = (u_dt, u_ev)
         # (b) keep the GPU under the same load until its clocks have settled (untimed)
         t_end = time.perf_counter() + args.settle_ms * 1e-3
         while True:
@@ -672,6 +721,10 @@ def main():
     if last_timed is not None:
         last = last_timed
     timed_per_step = list(per_step)
+    # --dump-outputs: the last timed step's outputs, copied on the device before anything else runs (no host wait)
+    snap = None
+    if args.dump_outputs:
+        snap = (None if args.no_emit else d_idx.clone(), None if sharded else d_res.clone())
 
     # ---- "median / min of >= 10 runs".  A second window right behind the timed one (same
     #      clocks), every step bracketed by its own pair of HIP events; `ms_per_step` stays the K-step window's mean
@@ -683,7 +736,7 @@ def main():
 
     step_dist = None
     standalone = None
-    if not sharded:
+    if args.full and not sharded:
         n_dist = max(args.steps, 50)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_dist + 1)]
         evs[0].record()
@@ -692,7 +745,7 @@ def main():
             evs[k + 1].record()
         torch.cuda.synchronize()
         step_dist = quantiles([evs[k].elapsed_time(evs[k + 1]) for k in range(n_dist)])
-    else:
+    elif args.full:
         # this rank's shard WITHOUT the stitch (the exact carry its last result proved, no exchange, no host turn):
         # what the rank's GPU does alone -- the basis of `scaling_efficiency` below
         s_in, e_in, ps_in = sh.last_spec
@@ -718,7 +771,7 @@ def main():
     #      still under load (behind the ten idle seconds of the CPU leg the same trivial kernels read 4 % less), into a
     #      scratch buffer of their own (the index array is verified later)
     ceil_box = None
-    if world == 1 and rank == 0 and not args.no_emit and not args.no_ceilings and not args.rehearse_sharded:
+    if args.full and world == 1 and rank == 0 and not args.no_emit and not args.no_ceilings and not args.rehearse_sharded:
         try:
             n_c = min(shard_len, 0xFFFF0000) // 4096 * 4096
             d_scratch = torch.empty(3 * n_c + 4096, dtype=torch.uint8, device=device)
@@ -731,7 +784,7 @@ def main():
     # ---- BASELINE configs 3 and 4 under the same clock (N = 1, default workload at 1 GiB only): sub-records, each with its
     #      own warm-up, unsettled window, settle and K-step window; behind the headline's windows, before the CPU leg
     others, others_failed = None, False
-    if (world == 1 and rank == 0 and not sharded and args.workload == "minified" and args.gib_per_gpu == 1.0
+    if (args.full and world == 1 and rank == 0 and not sharded and args.workload == "minified" and args.gib_per_gpu == 1.0
             and not (args.no_other_configs or args.no_emit or args.no_verify)):
         others = {}
         for name, what, gen, *extra in OTHER_CONFIGS:
@@ -743,7 +796,7 @@ def main():
             except Exception as exc:  # the headline is still printed; the exit code says that a sub-record broke
                 others[name] = {"error": repr(exc)}
                 others_failed = True
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.rehearse_sharded:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.rehearse_sharded:
         torch.cuda.synchronize()
         cpu = cpu_baseline(unit)  # timed CPU baseline on rank 0 at N = 1 only; the GPU is idle meanwhile
         try:
@@ -769,7 +822,7 @@ def main():
     # ---- every index of this rank's shard, on the device, placed with the offsets the stitch returned
     #      (tests/replication.py; SURVEY.md section 8d config 5: device-side checker + 64-bit hash)
     verified, verify_detail = "count", None
-    if not (args.no_verify or args.no_emit):
+    if args.full and not (args.no_verify or args.no_emit):
         from tests import replication
 
         torch.cuda.synchronize()
@@ -830,16 +883,11 @@ def main():
         # the spread of the second figure over the ranks of one step is the skew of the ranks' kernel ends
         ps = torch.tensor(timed_per_step if len(timed_per_step) == args.steps else [(0, 0)] * args.steps,
                           dtype=torch.float64, device=device if backend == "nccl" else "cpu")
-        alone_t = torch.tensor([standalone, float(shard_len)], dtype=torch.float64, device=ps.device)
         all_ps = [torch.empty_like(ps) for _ in range(world)]
-        all_alone = [torch.empty_like(alone_t) for _ in range(world)]
         dist.all_gather(all_ps, ps)
-        dist.all_gather(all_alone, alone_t)
         kern = np.stack([t.cpu().numpy()[:, 0] for t in all_ps]) / 1e6    # [rank, step] ms
         arrive = np.stack([t.cpu().numpy()[:, 1] for t in all_ps]) / 1e3  # [rank, step] us
         skew = arrive.max(axis=0) - arrive.min(axis=0)
-        alone_ms = [float(t[0].item()) for t in all_alone]
-        alone_rate = sum(float(t[1].item()) / (float(t[0].item()) * 1e-3) for t in all_alone) / 1e9  # GB/s, all ranks
         stitch = {"exchange": sh.exchange_used, "rccl_ranks": sh.rccl_ranks, "reruns": int(v[0].item()),
                   "reruns_behind_queue": int(stats1["reruns_behind_queue"] - stats0["reruns_behind_queue"]),
                   "allgather_rounds": int(vmax[1].item()),
@@ -851,7 +899,6 @@ def main():
                   "reports_in_us": {"min_rank_median": round(float(np.median(arrive, axis=1).min()), 2),
                                     "max_rank_median": round(float(np.median(arrive, axis=1).max()), 2)},
                   "rank_skew_us": {"median": round(float(np.median(skew)), 2), "max": round(float(skew.max()), 2)},
-                  "standalone_ms": [round(x, 4) for x in alone_ms],
                   "note": "timed window only; reruns summed over ranks; stitch = HIP-event time from the end of a round's "
                           "kernel to the gathered reports' arrival in pinned host memory (max over ranks); result_wait = host "
                           "time blocked in msj_stage1_sharded_result per step (max over ranks, with up to 3 steps in flight); "
@@ -859,7 +906,14 @@ def main():
                           "reports_in_us = kernel end -> reports in, per rank (median over steps): the smallest is the "
                           "exchange's bare latency; rank_skew_us = per step, max - min of that figure over the ranks = how "
                           "far apart the ranks' kernels end; standalone_ms = each rank's shard through msj_stage1_shard_device "
-                          "with its exact carry, no exchange, no host turn (K steps after the timed window)"}
+                          "with its exact carry, no exchange, no host turn (K steps after the timed window; --full)"}
+    if sh is not None and standalone is not None:  # --full
+        alone_t = torch.tensor([standalone, float(shard_len)], dtype=torch.float64, device=ps.device)
+        all_alone = [torch.empty_like(alone_t) for _ in range(world)]
+        dist.all_gather(all_alone, alone_t)
+        alone_ms = [float(t[0].item()) for t in all_alone]
+        alone_rate = sum(float(t[1].item()) / (float(t[0].item()) * 1e-3) for t in all_alone) / 1e9  # GB/s, all ranks
+        stitch["standalone_ms"] = [round(x, 4) for x in alone_ms]
         scaling_eff = {"value": round(total_len * args.steps / dt_max / 1e9 / alone_rate, 4),
                        "gib_per_gpu": args.gib_per_gpu,
                        "basis": f"whole-job GB/s / sum over the {world} ranks of (shard bytes / standalone_ms): the same "
@@ -909,8 +963,8 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             # what really ran between the start of the process and the timed window: the W warm-up steps, the K steps of
-            # the `unsettled` window and the settle passes (config.dvfs_settle)
-            "untimed_passes_before_window": args.warmup + ((args.steps + settle_steps) if args.settle_ms > 0 else 0),
+            # the `unsettled` window (--full) and the settle passes (config.dvfs_settle)
+            "untimed_passes_before_window": args.warmup + (args.steps if unsettled is not None else 0) + settle_steps,
             "ms_per_step": round(ms_per_step, 4),
             **({"ms_per_step_median": step_dist["median"], "ms_per_step_min": step_dist["min"],
                 "ms_per_step_p95": step_dist["p95"]} if step_dist else {}),
@@ -928,7 +982,8 @@ def main():
                 "density": round(total_count / total_len, 5),
                 "utf8_validation": not args.no_utf8,
                 "dvfs_settle": (f"{settle_steps} untimed passes ({args.settle_ms:g} ms) between the {args.warmup} warm-up "
-                                f"steps and the {args.steps} timed ones; see 'unsettled'") if args.settle_ms > 0 else "none",
+                                f"steps and the {args.steps} timed ones" + ("; see 'unsettled'" if unsettled is not None else ""))
+                               if args.settle_ms > 0 else "none",
                 **({"diagnostic": "no-emit summary pass: not a stage-1 result"} if args.no_emit else {}),
                 **({"rehearsal": "--rehearse-sharded: the N > 1 code path on one rank (RCCL world 1): not the headline"}
                    if args.rehearse_sharded else {}),
@@ -981,6 +1036,16 @@ def main():
                 "note": "rank 0's clock; the first ~100 ms after idle run 10-15 % slower than the sustained rate",
             }
         print(json.dumps(out), flush=True)
+    if snap is not None:
+        if sharded:
+            s_code, s_total, s_carry = last
+            n_entries = int(s_carry.count) + (3 if rank == world - 1 else 0)  # the last rank's shard ends in the trailer
+        else:
+            s_carry = dev.fetch(snap[1])
+            s_code, s_total = int(s_carry.code), int(s_carry.count)
+            n_entries = s_total + 3
+        dump_outputs(args.dump_outputs, f"_rank{rank}" if world > 1 else "", snap[0], n_entries, s_code, s_total, s_carry)
+        del snap
     verify_failed = verified.startswith("FAILED") or others_failed
     # a run over RCCL whose stitch did not go through the library's own ncclAllGather on a communicator of all N ranks is
     # not the run the line claims to be: the line is printed (rank 0, above) and every rank leaves with exit code 4

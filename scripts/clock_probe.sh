@@ -8,7 +8,7 @@ OUT=gpurun_out/clock_probe; rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 for mode in 0 400; do
   timeout -k 10 200 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace -d $OUT/m$mode -o g --output-format csv -- \
-      python3 bench.py ${MSJ_LIB:+--lib $MSJ_LIB} --steps 20 --warmup 5 --settle-ms $mode --no-cpu-baseline --no-verify --workload $W > $OUT/m$mode.log 2>&1 || echo "mode $mode failed"
+      python3 bench.py ${MSJ_LIB:+--lib $MSJ_LIB} --steps 20 --warmup 5 --settle-ms $mode --full --no-cpu-baseline --no-verify --workload $W > $OUT/m$mode.log 2>&1 || echo "mode $mode failed"
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 W=${1:-minified}
 OUT=gpurun_out/pmc_lds; rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --kernel-trace -d $OUT/g -o g --output-format csv -- python3 bench.py ${MSJ_LIB:+--lib $MSJ_LIB} --steps 3 --warmup 1 --settle-ms 0 --workload $W --no-cpu-baseline --no-verify > $OUT/g.log 2>&1 || echo "failed"
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --kernel-trace -d $OUT/g -o g --output-format csv -- python3 bench.py ${MSJ_LIB:+--lib $MSJ_LIB} --steps 3 --warmup 1 --settle-ms 0 --workload $W --full --no-cpu-baseline --no-verify > $OUT/g.log 2>&1 || echo "failed"
 python3 - <<'PY'
 import csv, glob, collections
 agg = collections.defaultdict(list)

@@ -1190,7 +1190,7 @@ def test_bench_line_of_the_sharded_path_rehearsed_on_one_rank():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-sharded", "--steps", "8", "--warmup", "2",
-                        "--settle-ms", "50", "--gib-per-gpu", "1"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--settle-ms", "50", "--gib-per-gpu", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
     cfg, st = line["config"], line["config"]["stitch"]
@@ -1201,6 +1201,42 @@ def test_bench_line_of_the_sharded_path_rehearsed_on_one_rank():
     eff = line["scaling_efficiency"]["value"]
     assert 0.7 < eff < 1.1, line["scaling_efficiency"]
     assert line["n_gpus"] == 1 and line["roofline"]["frac"] > 0.3 and "rehearsal" in cfg
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """`bench.py` without --full: the headline fields over exactly --steps timed steps, none of the --full records, and
+    --dump-outputs: the last timed step's result and a seeded sample of its index array, float64, within 64 MB, equal
+    to the oracle's indices of the repeated unit at the sampled positions."""
+    import subprocess
+    import sys
+
+    import bench
+    from mojo_simdjson_amd import synth
+
+    r = subprocess.run([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=helpers.ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
+    assert line["unit"] == "GB/s" and line["higher_is_better"] is True and line["dtype"] == "u8" and line["value"] > 0
+    assert line["steps"] == 7 and line["ms_per_step"] > 0 and line["config"]["verified"] == "count"
+    assert line["cpu_baseline"] is None and not {"unsettled", "other_configs", "end_to_end", "ms_per_step_median"} & set(line)
+    cfg = line["config"]
+    total, nbytes = cfg["structurals_total"], cfg["bytes_total"]
+
+    assert sorted(os.listdir(tmp_path)) == ["result.npy", "structural_indexes.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64_000_000
+    res = np.load(tmp_path / "result.npy")
+    assert res.dtype == np.float64 and list(res[:4]) == [0, total, total, nbytes]
+    got = np.load(tmp_path / "structural_indexes.npy")
+    pos = bench.dump_positions(total + 3)
+    assert got.dtype == np.float64 and got.shape == pos.shape
+
+    unit = synth.unit(bench.UNIT_BYTES, synth.SEED_MINIFIED, 0, 0, False)
+    u_idx = bench.unit_indices(unit).astype(np.int64)
+    body = pos[pos < total]
+    want = u_idx[body % u_idx.size] + (body // u_idx.size) * unit.size
+    trailer = np.array([nbytes, nbytes, 0], dtype=np.int64)[pos[pos >= total] - total]
+    assert np.array_equal(got, np.concatenate([want, trailer]).astype(np.float64))
 
 
 def _shared_gpu_worker(k, barrier, q):
