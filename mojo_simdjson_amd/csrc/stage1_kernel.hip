@@ -43,6 +43,8 @@
 #include "lane_math.h"
 #include "stage1_kernel.h"
 
+namespace msj {
+
 // Issue priority of a worker wave by phase (s_setprio; the resolver runs at 3).  The four waves of a SIMD are in
 // different phases of their range iterations; left to the default arbitration, a wave in a latency-bound phase -- the
 // dependent steps of the scatter chain, the LDS round trip of the copy-out, the fold and the hand-over behind the
@@ -52,30 +54,10 @@
 // (profiles/r03/ab_wave_priority.txt; any level above the compute phase's does it, the levels differ by < 1 %);
 // the second tile of the compute phase one level above the first: another +1.5 % / +1.8 % / +3.5 %.  The ladder
 // 0, 1, 2, 3 follows a wave's progress through its iteration.
-// EXPERIMENT (round 5, off by default): request the NEXT range's first tile at the start of the present range's second
-// compute phase (its registers are free from there) and its second tile right before the barrier -- the ticket then has to
-// be known one iteration earlier (drawn two ranges ahead).  What it is for: on sparse input the range loop is a latency
-// chain (load -> compute -> barrier -> hand-over -> load), not issue-bound.
-#ifndef MSJ_EARLY_A
-#define MSJ_EARLY_A 0
-#endif
-#ifndef MSJ_TICKET_AT_TOP
-#define MSJ_TICKET_AT_TOP 0  // EXPERIMENT (round 5, off): see worker_wave
-#endif
-#ifndef MSJ_PRIO_COORD
-#define MSJ_PRIO_COORD 2    // behind the barrier: fold, publish, hand-over, issue of the next range's loads
-#endif
-#ifndef MSJ_PRIO_EMIT
-#define MSJ_PRIO_EMIT 3     // staging chains and copy-out of the parked tiles
-#endif
-#ifndef MSJ_PRIO_COMPUTE
-#define MSJ_PRIO_COMPUTE 0  // bit-planes, classification, masks, scans of the range's first tile ...
-#endif
-#ifndef MSJ_PRIO_COMPUTE2
-#define MSJ_PRIO_COMPUTE2 1  // ... and of its second: the closer a wave is to the barrier its three siblings wait at, the sooner it issues
-#endif
-
-namespace msj {
+constexpr uint32_t kPrioCoord = 2;     // behind the barrier: fold, publish, hand-over, issue of the next range's loads
+constexpr uint32_t kPrioEmit = 3;      // staging chains and copy-out of the parked tiles
+constexpr uint32_t kPrioCompute = 0;   // bit-planes, classification, masks, scans of the range's first tile ...
+constexpr uint32_t kPrioCompute2 = 1;  // ... and of its second: the closer a wave is to the barrier its three siblings wait at, the sooner it issues
 
 // ---- tile descriptors -------------------------------------------------------
 // One 64-bit word per tile in each of two arrays.
@@ -185,7 +167,6 @@ struct Shared {
     uint32_t role;
     uint32_t shard;          // worker workgroups: the ticket shard they draw from
     uint32_t first_lo;       // ... and the base tile of their first range
-    uint32_t second_lo;      // MSJ_EARLY_A: ... and of their second (two draws at start-up)
     // worker workgroups: wave 0 hands the next range to the other waves with ONE 8-byte LDS store:
     // low word = base tile of the next range, high word = the iteration it is for (r + 1)
     uint64_t handoff __attribute__((aligned(8)));
@@ -556,55 +537,6 @@ __device__ __forceinline__ Pending compute_tile(const KernelArgs &a, const uint3
     const uint32_t skip = tile == 0 ? (a.flags >> kFlagSkipShift) & 15u : 0u;  // uniform
     const bool partial = tile * kTileBytes + kTileBytes > len;  // uniform: the launch's last tile, cut short
 
-#ifdef MSJ_UNIFORM_TILES
-    // MEASURED NO-GAIN, not in the product (round 5, profiles/r05/ab_uniform_tiles.txt; build with -DMSJ_UNIFORM_TILES to
-    // repeat): with this path a tile of blanks / of one scalar character runs ~15 vector instructions instead of 311, and
-    // the d ~ 0 rows of the density sweep do not move (0.1790 / 0.1791 ms per GiB without it, 0.1714 / 0.1836 with it, same
-    // box, alternating) -- those rows are bound by the range loop's latency chain (one 8 KiB request per wave and
-    // iteration: load -> barrier -> hand-over -> load), not by instruction issue -- while the filter's 7 instructions
-    // cost every ordinary tile ~1 % (pretty-printed 0.2510 -> 0.2548 ms, UTF-8-heavy 0.2897 -> 0.2942).
-    // ---- a tile whose 4 096 bytes are ONE byte value that is a blank or a plain scalar character (padding between
-    //      records, the inside of a run of one character): nothing to transpose or classify.  Round 5 (VERDICT round 4,
-    //      "311 vector instructions are paid to learn that a tile of blanks holds nothing"): a three-dword filter that
-    //      ordinary text fails at once (7 vector instructions per tile), then the other thirteen dwords.  What
-    //      JsonScanner.next (json_scanner.mojo:64-70) computes for such a block is known in closed form:
-    //        blanks        no structural, no scalar carry out                       (whitespace: haswell.mojo:23-65)
-    //        scalar bytes  one structural -- the tile's first byte, unless the byte in front of the tile is a scalar
-    //                      (follows, json_scanner.mojo:76-79) and only outside a string -- and the scalar carry out set.
-    //      Neither holds a quote or a backslash, so parity, escape carry and both error flags are zero whatever the
-    //      carries in (an escaped first byte that is no quote and no backslash changes nothing).
-    if (!partial && !skip && tc.resolved && tc.u8_in == 0u) {  // uniform
-        const uint32_t splat = perm(x[0], x[0], 0u);  // byte 0 of the lane's block, four times
-        const uint32_t first = uniform32(splat);
-        uint32_t dif = lut3<MSJ_TT(TA | (TB ^ TC))>(x[0] ^ splat, x[7], splat);
-        dif = lut3<MSJ_TT(TA | (TB ^ TC))>(dif, x[15], splat);
-        if (__ballot((dif | (splat ^ first)) != 0u) == 0ull) {  // uniform: the filter passed in every lane
-            const uint32_t c = first & 0xFFu;
-            // op | ws | quote | backslash | control | >= 0x80 as a 128-entry bit table (haswell.mojo:22-74 + 22, 5C, < 20)
-            constexpr uint64_t kSpLo = 0xFFFFFFFFull | (1ull << 0x20) | (1ull << 0x22) | (1ull << 0x2C) | (1ull << 0x3A);
-            constexpr uint64_t kSpHi = (1ull << (0x5B - 64)) | (1ull << (0x5C - 64)) | (1ull << (0x5D - 64)) |
-                                       (1ull << (0x7B - 64)) | (1ull << (0x7D - 64));
-            const bool plain = c < 0x80u && !((((c & 0x40u) ? kSpHi : kSpLo) >> (c & 63u)) & 1ull);
-            if (c == 0x20u || plain) {  // uniform
-                uint32_t acc = 0;
-#pragma unroll
-                for (int k = 1; k < 15; k++)
-                    if (k != 7) acc = lut3<MSJ_TT(TA | (TB ^ TC))>(acc, x[k], splat);
-                if (__ballot(acc != 0u) == 0ull) {  // uniform: all 4 096 bytes are c
-                    Pending r;
-                    const uint32_t one = (plain && tc.ps_in == 0u) ? 1u : 0u;  // the tile's first byte starts a scalar
-                    r.T0 = (lane == 0u) ? (uint64_t)one : 0ull;
-                    r.T1 = 0ull;
-                    r.excl = (lane == 0u) ? 0u : one;  // packed (count if outside | count if inside << 16) in front of the lane
-                    r.tile_cnt = one;
-                    const uint32_t hi = (uint32_t)(kAgg >> 32) | ((plain ? 1u : 0u) << 25) | (timeout << 22);
-                    agg_word = u64(r.tile_cnt, hi);
-                    return r;
-                }
-            }
-        }
-    }
-#endif
     MSJ_STAMP(tile, 2);
     // ---- bit-planes and character classes (lane_math.h)
     uint64_t p[8];
@@ -863,90 +795,34 @@ __device__ __forceinline__ void stage_indices(const EmitU &e, const EmitV &v, ui
 // it from displacing the input in L2 / MALL (a trivial kernel with this read : write mix gains 2 % from them,
 // profiles/r02/hbm_bw_ubench_nt.txt).
 __device__ __forceinline__ void st_index_quad(uint8_t *p, const uint4 v) {
-#ifdef MSJ_PLAIN_INDEX_STORES
-    *reinterpret_cast<uint4 *>(p) = v;
-#else
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     u32x4 w = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(w, reinterpret_cast<u32x4 *>(p));
-#endif
 }
 
-__device__ __forceinline__ void copy_out(const KernelArgs &a, const EmitU &e, const uint32_t *stage,
-                                         const uint32_t lane, const uint32_t lane_p) {
-    // uniform 64-bit base + 32-bit lane offsets; full 16-byte quads in the body, the (at
-    // most two) partial quads at the ends element by element
-    uint8_t *out = reinterpret_cast<uint8_t *>(a.idx + (e.base - e.shift));  // out[4v] <-> stage[v]; 16-byte aligned
-    const uint8_t *src = reinterpret_cast<const uint8_t *>(stage);
-    const uint32_t q_lo0 = (e.shift + 3u) >> 2;       // first quad with all four elements valid
-    const uint32_t q_hi0 = e.vend >> 2;               // one past the last full quad
-    // The streaming stores cover whole 128-byte lines only: the quads of the (at most two) lines this tile shares with
-    // its neighbours leave as plain stores, which L2 merges with the neighbour's part -- a partially written line that
-    // leaves as a non-temporal store reaches memory on its own (WRITE_SIZE 0.883 GB for 0.831 GB of indices on the 1 GiB
-    // minified input).  Same box, alternating, 1 500 launches each (profiles/r03/ab_edge_plain.txt): minified 0.3289 ->
-    // 0.3183 ms, 0.3261 -> 0.3199 (+2 .. +3.4 %); pretty-printed +-0.5 %; UTF-8-heavy -0.7 .. -1.1 % -- where the
-    // instruction stream and not the traffic binds, the few extra instructions cost more than the lines save, so the
-    // edges are only taken apart for tiles with many indices (MSJ_EDGE_PLAIN_MIN; 0 = always, ~0 = never).
-#ifndef MSJ_EDGE_PLAIN_MIN
-#define MSJ_EDGE_PLAIN_MIN 512u
-#endif
-    uint32_t q_lo = q_lo0, q_hi = q_hi0;
-    if (e.vend - e.shift >= MSJ_EDGE_PLAIN_MIN) {  // uniform
-        const uint32_t a16 = (uint32_t)(reinterpret_cast<uintptr_t>(out) >> 4);  // the output's address in quads (uniform)
-        const uint32_t over = (a16 + q_hi0) & 7u;
-        q_lo = q_lo0 + ((8u - ((a16 + q_lo0) & 7u)) & 7u);   // first quad that starts a line
-        q_hi = q_hi0 >= over ? q_hi0 - over : 0u;            // one past the last quad that ends one
-        if (q_lo > q_hi0) q_lo = q_hi0;
-        if (q_hi < q_lo) q_hi = q_lo;
-        if (lane_p < 16u) {  // the edges: [q_lo0, q_lo) and [q_hi, q_hi0), at most seven quads each
-            const uint32_t q = lane_p < 8u ? q_lo0 + lane : q_hi + (lane - 8u);
-            const bool ok = lane_p < 8u ? q < q_lo : q < q_hi0;
-            if (ok) *reinterpret_cast<uint4 *>(out + 16u * q) = *reinterpret_cast<const uint4 *>(src + 16u * q);
-        }
-    }
-    // at most kStageWords / 256 = 4 rounds of 64 quads: one byte offset per lane, the rounds are
-    // immediate offsets of the LDS read and of the store; only the last round is partial
-    const uint32_t off = (q_lo + lane) * 16u;
-#pragma unroll
-    for (uint32_t k = 0; k < kStageWords / 256u; k++) {
-        if (q_lo + 64u * k >= q_hi) break;  // uniform
-        if (q_lo + 64u * (k + 1u) <= q_hi) {  // uniform: a full round, every lane stores
-            st_index_quad(out + off + 1024u * k, *reinterpret_cast<const uint4 *>(src + off + 1024u * k));
-        } else {  // the last round: the first (q_hi - q_lo - 64k) lanes
-            if (lane_p < q_hi - q_lo - 64u * k)
-                st_index_quad(out + off + 1024u * k, *reinterpret_cast<const uint4 *>(src + off + 1024u * k));
-            break;
-        }
-    }
-    // head (elements shift .. 4*q_lo) and tail (4*q_hi .. vend): < 8 elements in total, one
-    // element per lane of the first eight
-    if (lane_p < 8u) {
-        const bool head = lane_p < 4u;
-        const uint32_t v = head ? lane : 4u * q_hi0 + (lane - 4u);
-        const bool ok = head ? (v >= e.shift && v < 4u * q_lo0 && v < e.vend) : (v < e.vend && v >= 4u * q_lo0);
-        if (ok) *reinterpret_cast<uint32_t *>(out + 4u * v) = *reinterpret_cast<const uint32_t *>(src + 4u * v);
-    }
-}
-
-// kTypes (prototype): the type byte of four indices -- four byte gathers from the tile's bytes (L2 / MALL: the tile was
-// read two iterations ago), packed into the dword that lies beside the quad in types[].  Measured (scripts/fused_types.py,
-// profiles/r05/fused_types_*.txt): the gathers cost stage 1 0.235 ms per GiB minified (0.314 -> 0.549) -- 16 load
-// instructions per tile, each 64 scattered bytes = up to 32 cache lines: eight times the requests of the tile's own read --
-// and requesting all of a tile's rounds before the first is looked at made it 0.573, not faster: it is the texture
-// path's request rate, not the round trips.  The next step would be the tile's 4 KiB re-read coalesced into the staging
-// slice behind the copy-out and ds_read_u8 gathers from there.
+// kTypes (prototype, kFlagEmitTypes): the type byte of four indices -- four byte gathers from the tile's bytes (L2 / MALL:
+// the tile was read two iterations ago), packed into the dword that lies beside the quad in types[].  Measured
+// (scripts/fused_types.py, profiles/r05/fused_types_*.txt): the gathers cost stage 1 0.235 ms per GiB minified (0.314 ->
+// 0.549) -- 16 load instructions per tile, each 64 scattered bytes = up to 32 cache lines: eight times the requests of the
+// tile's own read -- and requesting all of a tile's rounds before the first is looked at made it 0.573, not faster: it is
+// the texture path's request rate, not the round trips.  The next step would be the tile's 4 KiB re-read coalesced into
+// the staging slice behind the copy-out and ds_read_u8 gathers from there.
 __device__ __forceinline__ uint32_t gather_types4(const uint8_t *bytes, const uint4 v) {
     return (uint32_t)bytes[v.x] | ((uint32_t)bytes[v.y] << 8) | ((uint32_t)bytes[v.z] << 16) | ((uint32_t)bytes[v.w] << 24);
 }
-__device__ __forceinline__ void copy_out_types(const KernelArgs &a, const EmitU &e, const uint32_t *stage,
+
+constexpr uint32_t kEdgePlainMin = 512;  // copy_out: a tile with this many indices or more stores its line edges apart
+
+template <bool kTypes>
+__device__ __forceinline__ void copy_out(const KernelArgs &a, const EmitU &e, const uint32_t *stage,
                                          const uint32_t lane, const uint32_t lane_p) {
-    // types[] runs parallel to idx[]: element (e.base - e.shift) + v of either belongs to stage[v]; offsets are byte offsets
-    // of the document (+ index_bias), so `bytes + offset` is the byte itself
-    constexpr bool kTypes = true;
+    // kTypes: types[] runs parallel to idx[]: element (e.base - e.shift) + v of either belongs to stage[v]; offsets are
+    // byte offsets of the document (+ index_bias), so `bytes + offset` is the byte itself
     uint8_t *tout = a.types + (e.base - e.shift);
     const uint8_t *bytes = a.buf - a.index_bias;
     // uniform 64-bit base + 32-bit lane offsets; full 16-byte quads in the body, the (at
-    // most two) partial quads at the ends element by element
+    // most two) partial quads at the ends element by element.  Each copy is one expression in the product (!kTypes): the
+    // kTypes form's local made hipcc split the 16-byte LDS reads there (+10 vector instructions per tile).
     uint8_t *out = reinterpret_cast<uint8_t *>(a.idx + (e.base - e.shift));  // out[4v] <-> stage[v]; 16-byte aligned
     const uint8_t *src = reinterpret_cast<const uint8_t *>(stage);
     const uint32_t q_lo0 = (e.shift + 3u) >> 2;       // first quad with all four elements valid
@@ -957,12 +833,9 @@ __device__ __forceinline__ void copy_out_types(const KernelArgs &a, const EmitU 
     // minified input).  Same box, alternating, 1 500 launches each (profiles/r03/ab_edge_plain.txt): minified 0.3289 ->
     // 0.3183 ms, 0.3261 -> 0.3199 (+2 .. +3.4 %); pretty-printed +-0.5 %; UTF-8-heavy -0.7 .. -1.1 % -- where the
     // instruction stream and not the traffic binds, the few extra instructions cost more than the lines save, so the
-    // edges are only taken apart for tiles with many indices (MSJ_EDGE_PLAIN_MIN; 0 = always, ~0 = never).
-#ifndef MSJ_EDGE_PLAIN_MIN
-#define MSJ_EDGE_PLAIN_MIN 512u
-#endif
+    // edges are only taken apart for tiles with many indices (kEdgePlainMin).
     uint32_t q_lo = q_lo0, q_hi = q_hi0;
-    if (e.vend - e.shift >= MSJ_EDGE_PLAIN_MIN) {  // uniform
+    if (e.vend - e.shift >= kEdgePlainMin) {  // uniform
         const uint32_t a16 = (uint32_t)(reinterpret_cast<uintptr_t>(out) >> 4);  // the output's address in quads (uniform)
         const uint32_t over = (a16 + q_hi0) & 7u;
         q_lo = q_lo0 + ((8u - ((a16 + q_lo0) & 7u)) & 7u);   // first quad that starts a line
@@ -973,9 +846,13 @@ __device__ __forceinline__ void copy_out_types(const KernelArgs &a, const EmitU 
             const uint32_t q = lane_p < 8u ? q_lo0 + lane : q_hi + (lane - 8u);
             const bool ok = lane_p < 8u ? q < q_lo : q < q_hi0;
             if (ok) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(src + 16u * q);
-                *reinterpret_cast<uint4 *>(out + 16u * q) = v;
-                if (kTypes) *reinterpret_cast<uint32_t *>(tout + 4u * q) = gather_types4(bytes, v);
+                if constexpr (kTypes) {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(src + 16u * q);
+                    *reinterpret_cast<uint4 *>(out + 16u * q) = v;
+                    *reinterpret_cast<uint32_t *>(tout + 4u * q) = gather_types4(bytes, v);
+                } else {
+                    *reinterpret_cast<uint4 *>(out + 16u * q) = *reinterpret_cast<const uint4 *>(src + 16u * q);
+                }
             }
         }
     }
@@ -986,14 +863,22 @@ __device__ __forceinline__ void copy_out_types(const KernelArgs &a, const EmitU 
     for (uint32_t k = 0; k < kStageWords / 256u; k++) {
         if (q_lo + 64u * k >= q_hi) break;  // uniform
         if (q_lo + 64u * (k + 1u) <= q_hi) {  // uniform: a full round, every lane stores
-            const uint4 v = *reinterpret_cast<const uint4 *>(src + off + 1024u * k);
-            st_index_quad(out + off + 1024u * k, v);
-            if (kTypes) *reinterpret_cast<uint32_t *>(tout + (off >> 2) + 256u * k) = gather_types4(bytes, v);
-        } else {  // the last round: the first (q_hi - q_lo - 64k) lanes
-            if (lane_p < q_hi - q_lo - 64u * k) {
+            if constexpr (kTypes) {
                 const uint4 v = *reinterpret_cast<const uint4 *>(src + off + 1024u * k);
                 st_index_quad(out + off + 1024u * k, v);
-                if (kTypes) *reinterpret_cast<uint32_t *>(tout + (off >> 2) + 256u * k) = gather_types4(bytes, v);
+                *reinterpret_cast<uint32_t *>(tout + (off >> 2) + 256u * k) = gather_types4(bytes, v);
+            } else {
+                st_index_quad(out + off + 1024u * k, *reinterpret_cast<const uint4 *>(src + off + 1024u * k));
+            }
+        } else {  // the last round: the first (q_hi - q_lo - 64k) lanes
+            if (lane_p < q_hi - q_lo - 64u * k) {
+                if constexpr (kTypes) {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(src + off + 1024u * k);
+                    st_index_quad(out + off + 1024u * k, v);
+                    *reinterpret_cast<uint32_t *>(tout + (off >> 2) + 256u * k) = gather_types4(bytes, v);
+                } else {
+                    st_index_quad(out + off + 1024u * k, *reinterpret_cast<const uint4 *>(src + off + 1024u * k));
+                }
             }
             break;
         }
@@ -1005,9 +890,13 @@ __device__ __forceinline__ void copy_out_types(const KernelArgs &a, const EmitU 
         const uint32_t v = head ? lane : 4u * q_hi0 + (lane - 4u);
         const bool ok = head ? (v >= e.shift && v < 4u * q_lo0 && v < e.vend) : (v < e.vend && v >= 4u * q_lo0);
         if (ok) {
-            const uint32_t x = *reinterpret_cast<const uint32_t *>(src + 4u * v);
-            *reinterpret_cast<uint32_t *>(out + 4u * v) = x;
-            if (kTypes) tout[v] = bytes[x];
+            if constexpr (kTypes) {
+                const uint32_t x = *reinterpret_cast<const uint32_t *>(src + 4u * v);
+                *reinterpret_cast<uint32_t *>(out + 4u * v) = x;
+                tout[v] = bytes[x];
+            } else {
+                *reinterpret_cast<uint32_t *>(out + 4u * v) = *reinterpret_cast<const uint32_t *>(src + 4u * v);
+            }
         }
     }
 }
@@ -1028,79 +917,9 @@ __device__ __forceinline__ void lds_wave_sync() {
 // contiguous bytes -- straight to the output.  16 instructions per 64-byte block whatever the density; no
 // staging, no LDS.  (Plain stores: a block's store covers a part of one or two 128-byte lines and the next block's
 // store the rest; as non-temporal stores the parts reach memory one by one -- `[10,10,...`: 0.76 -> 1.09 ms per GiB.)
+// kTypes (prototype): the type byte of every index written beside it, into types[] (bytes: see copy_out).
+template <bool kTypes>
 __device__ __noinline__ void emit_dense(uint32_t *idx, const uint32_t tile_base, const uint64_t base, const uint32_t tlo,
-                                        const uint32_t thi, const uint32_t first_slot, const uint32_t lane) {
-    // out[k] = the tile's k-th index; wave-uniform (the arguments of a called function arrive in vector registers)
-    const uint64_t out = uniform64(reinterpret_cast<uint64_t>(idx + base));
-    const uint32_t tb = uniform32(tile_base);
-    for (uint32_t b = 0; b < 64u; b++) {  // uniform
-        const uint32_t mlo = bcast(tlo, (int)b), mhi = bcast(thi, (int)b);
-        if ((mlo | mhi) == 0u) continue;
-        const uint32_t slot0 = bcast(first_slot, (int)b);  // slot of the block's first index
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
-        const uint32_t off = (slot0 + rank) * 4u;
-        const uint32_t val = tb + b * 64u + lane;
-        const uint64_t m = u64(mlo, mhi);
-        uint64_t save;
-        asm volatile(
-            "s_mov_b64 %[save], exec\n"
-            "s_mov_b64 exec, %[m]\n"
-            "global_store_dword %[off], %[val], %[out]\n"
-            "s_mov_b64 exec, %[save]\n"
-            : [save] "=&s"(save)
-            : [m] "s"(m), [off] "v"(off), [val] "v"(val), [out] "s"(out)
-            : "memory");
-    }
-}
-
-// An index buffer that is too small (the launch reports CAPACITY): element-wise, clipped.
-__device__ __noinline__ void emit_general(uint32_t *idx, const uint64_t capacity, const uint32_t tile_base,
-                                          const uint64_t base, const uint32_t shift, const uint32_t vend,
-                                          uint32_t tlo, uint32_t thi, uint32_t vpos, uint32_t *stage,
-                                          const uint32_t lane) {
-    const uint32_t v0 = tile_base + lane * 64u;
-    for (uint32_t r0 = 0; r0 < vend; r0 += kStageWords) {
-        const uint32_t r1 = r0 + kStageWords;
-        while (tlo && vpos < r1) {
-            stage[vpos - r0] = v0 + (uint32_t)__builtin_ctz(tlo);
-            tlo &= tlo - 1;
-            vpos++;
-        }
-        if (!tlo) {
-            while (thi && vpos < r1) {
-                stage[vpos - r0] = v0 + 32u + (uint32_t)__builtin_ctz(thi);
-                thi &= thi - 1;
-                vpos++;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint32_t lim = vend < r1 ? vend : r1;
-        const uint64_t gbase = base - shift + r0;
-        for (uint32_t q = lane; 4u * q < lim - r0; q += 64u) {
-            const uint32_t vq = r0 + 4u * q;
-            const uint4 val = *reinterpret_cast<const uint4 *>(&stage[4u * q]);
-            const uint64_t g = gbase + 4u * q;
-            if (vq >= shift && vq + 4u <= lim && g + 4u <= capacity) {
-                *reinterpret_cast<uint4 *>(&idx[g]) = val;
-            } else {
-                const uint32_t vv[4] = {val.x, val.y, val.z, val.w};
-#pragma unroll
-                for (uint32_t j = 0; j < 4; j++) {
-                    const uint32_t v = vq + j;
-                    if (v >= shift && v < lim && g + j < capacity) idx[g + j] = vv[j];
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();  // stage is reused by the next round / next tile
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-}
-
-// PROTOTYPE (kFlagEmitTypes): the same two with the type byte of every index written beside it
-__device__ __noinline__ void emit_dense_types(uint32_t *idx, const uint32_t tile_base, const uint64_t base, const uint32_t tlo,
                                         const uint32_t thi, const uint32_t first_slot, const uint32_t lane,
                                         uint8_t *types, const uint8_t *bytes) {
     // out[k] = the tile's k-th index; wave-uniform (the arguments of a called function arrive in vector registers)
@@ -1123,12 +942,13 @@ __device__ __noinline__ void emit_dense_types(uint32_t *idx, const uint32_t tile
             : [save] "=&s"(save)
             : [m] "s"(m), [off] "v"(off), [val] "v"(val), [out] "s"(out)
             : "memory");
-        if (types && ((m >> lane) & 1ull)) types[base + slot0 + rank] = bytes[val];  // (prototype: kFlagEmitTypes)
+        if (kTypes && types && ((m >> lane) & 1ull)) types[base + slot0 + rank] = bytes[val];
     }
 }
 
-// An index buffer that is too small (the launch reports CAPACITY): element-wise, clipped.
-__device__ __noinline__ void emit_general_types(uint32_t *idx, const uint64_t capacity, const uint32_t tile_base,
+// An index buffer that is too small (the launch reports CAPACITY): element-wise, clipped.  kTypes: as emit_dense.
+template <bool kTypes>
+__device__ __noinline__ void emit_general(uint32_t *idx, const uint64_t capacity, const uint32_t tile_base,
                                           const uint64_t base, const uint32_t shift, const uint32_t vend,
                                           uint32_t tlo, uint32_t thi, uint32_t vpos, uint32_t *stage,
                                           const uint32_t lane, uint8_t *types, const uint8_t *bytes) {
@@ -1158,7 +978,7 @@ __device__ __noinline__ void emit_general_types(uint32_t *idx, const uint64_t ca
             const uint64_t g = gbase + 4u * q;
             if (vq >= shift && vq + 4u <= lim && g + 4u <= capacity) {
                 *reinterpret_cast<uint4 *>(&idx[g]) = val;
-                if (types) *reinterpret_cast<uint32_t *>(&types[g]) = gather_types4(bytes, val);
+                if (kTypes && types) *reinterpret_cast<uint32_t *>(&types[g]) = gather_types4(bytes, val);
             } else {
                 const uint32_t vv[4] = {val.x, val.y, val.z, val.w};
 #pragma unroll
@@ -1166,7 +986,7 @@ __device__ __noinline__ void emit_general_types(uint32_t *idx, const uint64_t ca
                     const uint32_t v = vq + j;
                     if (v >= shift && v < lim && g + j < capacity) {
                         idx[g + j] = vv[j];
-                        if (types) types[g + j] = bytes[vv[j]];
+                        if (kTypes && types) types[g + j] = bytes[vv[j]];
                     }
                 }
             }
@@ -1241,26 +1061,21 @@ template <bool kTypes = false>
 __device__ __forceinline__ void emit_store(const KernelArgs &a, const Shared &sh, const EmitU &e, const uint32_t wave,
                                            const uint32_t slot, uint32_t *stage, const uint32_t lane, const uint32_t lane_p) {
     if (e.mode == kEmitStaged) {  // uniform
-        if (kTypes) copy_out_types(a, e, stage, lane, lane_p); else copy_out(a, e, stage, lane, lane_p);
+        copy_out<kTypes>(a, e, stage, lane, lane_p);
     } else if (e.mode == kEmitStaged2) {
-        if (kTypes) copy_out_types(a, emit_round(e, 0u), stage, lane, lane_p); else copy_out(a, emit_round(e, 0u), stage, lane, lane_p);
+        copy_out<kTypes>(a, emit_round(e, 0u), stage, lane, lane_p);
         lds_wave_sync();  // the slice is reused by the second round
         const EmitV v = emit_lane(sh, wave, slot, lane, e);
         stage_indices_round(e, v, stage, lane64_of(lane), 1u);
         lds_wave_sync();
-        if (kTypes) copy_out_types(a, emit_round(e, 1u), stage, lane, lane_p); else copy_out(a, emit_round(e, 1u), stage, lane, lane_p);
+        copy_out<kTypes>(a, emit_round(e, 1u), stage, lane, lane_p);
     } else if (e.mode == kEmitDense) {
         const EmitV v = emit_lane(sh, wave, slot, lane, e);
-        if (kTypes)
-            emit_dense_types(a.idx, e.tile_base, e.base, v.tlo, v.thi, v.vpos - e.shift, lane, a.types, a.buf - a.index_bias);
-        else
-            emit_dense(a.idx, e.tile_base, e.base, v.tlo, v.thi, v.vpos - e.shift, lane);
+        emit_dense<kTypes>(a.idx, e.tile_base, e.base, v.tlo, v.thi, v.vpos - e.shift, lane, a.types, a.buf - a.index_bias);
     } else if (e.mode == kEmitGeneral) {
         const EmitV v = emit_lane(sh, wave, slot, lane, e);
-        if (kTypes)
-            emit_general_types(a.idx, a.capacity, e.tile_base, e.base, e.shift, e.vend, v.tlo, v.thi, v.vpos, stage, lane, a.types, a.buf - a.index_bias);
-        else
-            emit_general(a.idx, a.capacity, e.tile_base, e.base, e.shift, e.vend, v.tlo, v.thi, v.vpos, stage, lane);
+        emit_general<kTypes>(a.idx, a.capacity, e.tile_base, e.base, e.shift, e.vend, v.tlo, v.thi, v.vpos, stage, lane,
+                             a.types, a.buf - a.index_bias);
     }
 }
 
@@ -1321,10 +1136,6 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
     MSJ_RSTAMP(a.ntiles + 4096u + blockIdx.x, 2, tid == 0);
     // LDS words every lane reads identically: uniform (tile indices and all control flow stay scalar)
     uint32_t lo_cur = uniform32(sh.first_lo);
-#if MSJ_EARLY_A
-    uint32_t lo_nxt = uniform32(sh.second_lo);  // the range behind lo_cur, known an iteration early
-    uint32_t nt_next = 0u;                      // ... and whether its bytes are requested non-temporally
-#endif
     const uint64_t count0 = uniform64(cin_count(a));  // launch invariants: read once
     const uint32_t carry0 = uniform32(cin_carry0(a));
     uint32_t timeout = 0;
@@ -1364,11 +1175,6 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
         // ---- 1. compute
         Pending now[kBatch];
         uint32_t req_reg = 0;
-#if MSJ_TICKET_AT_TOP
-        // EXPERIMENT (round 5): the next range's ticket drawn at the TOP of the iteration -- both compute phases cover the
-        // atomic's round trip instead of one (on sparse input one phase is shorter than the round trip)
-        if (tid_p == 0) req_reg = ticket_request(ticket_ctr_p, 0u, 1u);
-#endif
 #pragma unroll
         for (uint32_t j = 0; j < kBatch; j++) {
             const uint32_t t_cur = lo_cur + kWaves * j + wave;
@@ -1383,47 +1189,17 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
                 // the chunks the coalesced loads brought become this lane's block (the staging slice is free: the
                 // last emission's copy-out has been waited for)
                 chunks_to_block(blk[j], chunk_at);
-#if MSJ_EARLY_A
-                if (j == 1) {
-                    // the first tile's registers are free since its compute phase: the NEXT range's first tile goes there now
-                    // and has this compute phase, the barrier and the emission to arrive
-                    const uint32_t tn = lo_nxt + wave;
-                    if (nt_next) {
-                        asm volatile("; non-temporal early loads");
-                        load_block<true, true>(a, tn < ntiles ? tn : ntiles - 1u, lane_off, lane, blk[0]);
-                        asm volatile("; end of non-temporal early loads");
-                    } else {
-                        load_block<true, false>(a, tn < ntiles ? tn : ntiles - 1u, lane_off, lane, blk[0]);
-                    }
-                }
-#endif
                 now[j] = compute_tile(al, t_cur, lane, blk[j], carry0_p, timeout, agg_word);
                 lds_wave_sync_early();  // the next tile's chunks (or the emission) reuse the slice
             }
-#if MSJ_EARLY_A
-            else if (j == 1) {  // (a range whose second tile lies past the end: the next range's does too -- nothing to ask for,
-                                //  but the registers must hold SOMETHING loaded for the waits' bookkeeping: nothing is waited for)
-            }
-#endif
             if (j == 0) {
-#if MSJ_PRIO_COMPUTE2 != MSJ_PRIO_COMPUTE
-                __builtin_amdgcn_s_setprio(MSJ_PRIO_COMPUTE2);
-#endif
+                __builtin_amdgcn_s_setprio(kPrioCompute2);
                 // the prefix word requested above has arrived (nothing younger is in flight yet) ...
-#if MSJ_TICKET_AT_TOP
-                // (wave 0's ticket is younger than the prefix word and may stay out: returns come in order)
-                if (wave_p == 0) asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); else
-#endif
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 touch_u64(rp_word);
-#if MSJ_EARLY_A
-                touch_block(blk[1]);  // ... and so has this range's second tile (requested before the last barrier)
-#endif
                 // ... and the next range's ticket is drawn: one compute + one staging phase
                 // ahead of its use, which covers the atomic's round trip
-#if !MSJ_TICKET_AT_TOP
                 if (tid_p == 0) req_reg = ticket_request(ticket_ctr_p, 0u, 1u);
-#endif
             }
             if (lane_p == 0) {
                 if (valid_tile) st_desc(&a.ws[kDescOffset + t_cur], agg_word);  // carries for t_cur + 1
@@ -1431,22 +1207,6 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
             }
             MSJ_STAMP(valid_tile ? t_cur : ntiles - 1u, 7);
         }
-#if MSJ_EARLY_A
-        {   // the next range's SECOND tile: this range's has been consumed, its registers are free
-            const uint32_t c0 = now[0].tile_cnt, c1 = now[1].tile_cnt;
-            const uint32_t n0 = (c0 & 0xFFFFu) > (c0 >> 16) ? (c0 & 0xFFFFu) : (c0 >> 16);
-            const uint32_t n1 = (c1 & 0xFFFFu) > (c1 >> 16) ? (c1 & 0xFFFFu) : (c1 >> 16);
-            const uint32_t tn = lo_nxt + kWaves + wave;
-            if (nt_next) {
-                asm volatile("; non-temporal early loads B");
-                load_block<true, true>(a, tn < ntiles ? tn : ntiles - 1u, lane_off, lane, blk[1]);
-                asm volatile("; end of non-temporal early loads B");
-            } else {
-                load_block<true, false>(a, tn < ntiles ? tn : ntiles - 1u, lane_off, lane, blk[1]);
-            }
-            nt_next = (uniform32(n0 + n1) > kNtMaxIndices || ntiles < kNtMinTiles) ? 0u : 1u;  // for the range after that
-        }
-#endif
         const uint32_t srow = (lo_cur + kWaves + wave < ntiles) ? lo_cur + kWaves + wave : ntiles - 1u;  // stamp row (diagnostic builds)
         (void)srow;
         MSJ_STAMP(srow, 8);   // both tiles computed
@@ -1454,7 +1214,7 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
         // completed (__syncthreads() would wait for them)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         MSJ_STAMP(srow, 9);   // barrier passed
-        __builtin_amdgcn_s_setprio(MSJ_PRIO_COORD);
+        __builtin_amdgcn_s_setprio(kPrioCoord);
         // wave 0 passes the next range's ticket on (drawn a compute phase ago) ...
         if (wave_p == 0) {
             const uint32_t v = ticket_value(req_reg);
@@ -1537,7 +1297,6 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
             }
             lo_next = (uint32_t)h;
         }
-#if !MSJ_EARLY_A
         {
             // the load policy follows the data (load_block): dense input -> plain loads
             const uint32_t c0 = now[0].tile_cnt, c1 = now[1].tile_cnt;
@@ -1552,7 +1311,6 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
                 asm volatile("; end of non-temporal range loads");
             }
         }
-#endif
         MSJ_RSTAMP(lo_cur, 8, tid == 0);  // range aggregate published (real time)
         // ---- 3. emit the range parked kDefer iterations ago; hand the next range over in between
         if (have_old) {
@@ -1564,7 +1322,7 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
         timeout = uniform32(timeout);
         MSJ_STAMP(srow, 12);  // next range known, its loads issued, the old range's prefix in hand
         static_assert(kBatch == 2, "the emission below is written for two tiles per wave and range");
-        __builtin_amdgcn_s_setprio(MSJ_PRIO_EMIT);
+        __builtin_amdgcn_s_setprio(kPrioEmit);
         const uint32_t slot0 = ring * kBatch;
         EmitU e0 = emit_prepare(al, sh, wave, slot0, rp, count0, timeout);
         emit_stage(sh, e0, wave, slot0, stage, lane, lane64);
@@ -1577,22 +1335,14 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
         emit_stage(sh, e1, wave, slot0 + 1u, stage, lane, lane64);
         lds_wave_sync();
         MSJ_STAMP(srow, 15);  // tile B staged
-#if MSJ_EARLY_A
-        // the next range's FIRST tile has arrived (requested a compute phase, a barrier and an emission ago): loads return
-        // in order, so "at most the five younger loads outstanding" says so whatever the stores in between are doing.  Its
-        // second tile is waited for behind the next compute phase (the vmcnt(0) there).
-        asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        touch_block(blk[0]);
-#else
         // the bytes requested above (and the first tile's stores) have had a whole staging phase
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
         for (uint32_t j = 0; j < kBatch; j++) touch_block(blk[j]);
-#endif
         MSJ_STAMP(srow, 11);  // the next range's bytes have arrived
         emit_store<kTypes>(al, sh, e1, wave, slot0 + 1u, stage, lane, lane_p);
         lds_wave_sync();
-        __builtin_amdgcn_s_setprio(MSJ_PRIO_COMPUTE);
+        __builtin_amdgcn_s_setprio(kPrioCompute);
         // ---- 4. park this iteration's tiles
 #pragma unroll
         for (uint32_t j = 0; j < kBatch; j++) {
@@ -1605,18 +1355,13 @@ __device__ __forceinline__ void worker_wave(const KernelArgs &a, Shared &sh, con
                 *reinterpret_cast<uint4 *>(sh.pend_meta[wave][slot]) =
                     make_uint4(t_cur < ntiles ? t_cur : 0xFFFFFFFFu, now[j].tile_cnt, in_cnt[j], in_state[j]);
         }
-#if MSJ_EARLY_A
-        lo_cur = lo_nxt;
-        lo_nxt = lo_next;  // (what the hand-over brought is the range after the next one)
-#else
         lo_cur = lo_next;
-#endif
         r++;
         ring = (ring + 1u == kDefer) ? 0u : ring + 1u;
     }
     MSJ_RSTAMP(a.ntiles + 4096u + blockIdx.x, 4, tid == 0);  // last range computed
     // ---- drain: oldest first (the launch's tail: nothing but emission is left for this wave)
-    __builtin_amdgcn_s_setprio(MSJ_PRIO_EMIT);
+    __builtin_amdgcn_s_setprio(kPrioEmit);
     for (uint32_t step = 0; step < kDefer; step++) {
         lds_wave_sync();
         const uint32_t old_first = uniform32(sh.pend_meta[wave][ring * kBatch][0]);
@@ -2091,10 +1836,6 @@ __device__ __forceinline__ void stage1_body(const KernelArgs &a) {
         sh.role = (shard == 0u && k == 0u) ? 0u : 1u;
         sh.shard = shard;
         sh.first_lo = ticket_range(k, shard, shards) * kRange;
-        if (MSJ_EARLY_A && sh.role != 0u) {
-            const uint32_t k2 = atomicAdd(reinterpret_cast<unsigned int *>(a.ws + (uint64_t)shard * kTicketStrideWords), 1u);
-            sh.second_lo = ticket_range(k2, shard, shards) * kRange;
-        }
         sh.handoff = 0ull;
     }
     __syncthreads();

@@ -27,10 +27,6 @@
 #include "token_math.h"
 #include "tokens_launch.h"
 
-#ifndef MSJ_SPAN_ABLATE
-#define MSJ_SPAN_ABLATE 0  // diagnostic builds: 1 no token evaluation, 2 no depth aggregates, 3 no bit-plane transpose (wrong results)
-#endif
-
 namespace msj_tokens {
 
 #ifdef MSJ_TILE_STAMPS
@@ -871,16 +867,21 @@ struct MinTree {
     int nlev;
 };
 
-// level k from level k-1 (the levels above the three that apply_depth writes are tiny)
-__global__ __launch_bounds__(256) void build_level(const int32_t *__restrict__ in, uint32_t n_in, int32_t *__restrict__ out, uint32_t n_out) {
-    const uint32_t o = blockIdx.x * 256u + threadIdx.x;
-    if (o >= n_out) return;
+// entry o of a level: the minimum of entries 8o .. 8o+7 of the level below (n_in entries; kNone past its end)
+__device__ __forceinline__ int group_min(const int32_t *in, const uint32_t n_in, const uint32_t o) {
     int m = kNone;
     for (uint32_t k = 0; k <= kFanMask; k++) {
         const uint32_t i = (o << kFanShift) + k;
         if (i < n_in) m = min(m, in[i]);
     }
-    out[o] = m;
+    return m;
+}
+
+// level k from level k-1 (the levels above the three that apply_depth writes are tiny)
+__global__ __launch_bounds__(256) void build_level(const int32_t *__restrict__ in, uint32_t n_in, int32_t *__restrict__ out, uint32_t n_out) {
+    const uint32_t o = blockIdx.x * 256u + threadIdx.x;
+    if (o >= n_out) return;
+    out[o] = group_min(in, n_in, o);
 }
 
 // levels 6 .. of the tree in ONE single-workgroup launch (they hold n / 262 144 entries and less; one launch of
@@ -895,12 +896,7 @@ __global__ __launch_bounds__(1024) void build_upper_levels(const UpperLevels u) 
         const int32_t *in = u.lv[k - 1];
         const uint32_t n_in = u.cnt[k - 1], n_out = u.cnt[k];
         for (uint32_t o = threadIdx.x; o < n_out; o += 1024u) {
-            int m = kNone;
-            for (uint32_t j = 0; j <= kFanMask; j++) {
-                const uint32_t i = (o << kFanShift) + j;
-                if (i < n_in) m = min(m, in[i]);
-            }
-            u.lv[k][o] = m;
+            u.lv[k][o] = group_min(in, n_in, o);
         }
         __threadfence_block();
         __syncthreads();
@@ -938,19 +934,12 @@ __device__ __forceinline__ uint32_t first_le(const int v[8], uint32_t from, int 
 // GiB minified, 180 000 such brackets: one THREAD per bracket walking the tree 93 us (every load instruction of such a
 // wave is 64 scattered 32-byte reads), sixteen lanes per bracket with one step of the scan and one level of the climb
 // per round trip 84 us -- the longest chain of one bracket, whatever the grid -- and with the rounds below ...
-#ifndef MSJ_MATCH_GRID
-#define MSJ_MATCH_GRID 32
-#endif
-#ifndef MSJ_MATCH_LINEAR
-#define MSJ_MATCH_LINEAR 256
-#endif
-#ifndef MSJ_COMPACT_GRID
-#define MSJ_COMPACT_GRID 4096  // workgroups of match_compact at most (each strides over the blocks of 2 048 brackets)
-#endif
-#ifndef MSJ_MATCH_LINEAR_COMPACT
-#define MSJ_MATCH_LINEAR_COMPACT 64  // on the compact list: one round (the partners of the brackets a block of 2 048 brackets left over are mostly further away: 30.0 us against 33.9 with four rounds, 57 with none)
-#endif
-constexpr uint32_t kLinear = MSJ_MATCH_LINEAR, kLinearCompact = MSJ_MATCH_LINEAR_COMPACT, kGroup = 8, kSteps = 8;  // 64 tokens per group and round
+constexpr uint32_t kLinear = 256, kGroup = 8, kSteps = 8;  // 64 tokens per group and round
+// on the compact list: one round (the partners of the brackets a block of 2 048 brackets left over are mostly further
+// away: 30.0 us against 33.9 with four rounds, 57 with none)
+constexpr uint32_t kLinearCompact = 64;
+constexpr uint32_t kMatchGrid = 32;      // workgroups of match_brackets per survivor list at most
+constexpr uint32_t kCompactGrid = 4096;  // workgroups of match_compact at most (each strides over the blocks of 2 048 brackets)
 // kCompact (round 5, the pairs form): the same walk over the COMPACT list of the call's brackets -- t_in.lv[0] is that
 // list's depth word per bracket, brk_tok its token word (bit 31: a closing bracket), an entry of the lists the bracket's
 // place in the compact list, and the number of brackets -- hence every level's count -- is only known on the device:
@@ -1310,12 +1299,7 @@ __global__ __launch_bounds__(256) void build_level_compact(const int32_t *__rest
     const uint32_t o = blockIdx.x * 256u + threadIdx.x;
     const uint32_t n_in = level_entries(nbrk, lev - 1), n_out = level_entries(nbrk, lev);
     if (o >= n_out) return;
-    int m = kNone;
-    for (uint32_t k = 0; k <= kFanMask; k++) {
-        const uint32_t i = (o << kFanShift) + k;
-        if (i < n_in) m = min(m, in[i]);
-    }
-    out[o] = m;
+    out[o] = group_min(in, n_in, o);
 }
 // ... and the levels from 6 on in one workgroup, as build_upper_levels
 __global__ __launch_bounds__(1024) void build_upper_levels_compact(const MinTree t, const msj_tokens_result *__restrict__ result,
@@ -1327,12 +1311,7 @@ __global__ __launch_bounds__(1024) void build_upper_levels_compact(const MinTree
         int32_t *out = const_cast<int32_t *>(t.lv[k]);
         const uint32_t n_in = level_entries(nbrk, k - 1), n_out = level_entries(nbrk, k);
         for (uint32_t o = threadIdx.x; o < n_out; o += 1024u) {
-            int m = kNone;
-            for (uint32_t j = 0; j <= kFanMask; j++) {
-                const uint32_t i = (o << kFanShift) + j;
-                if (i < n_in) m = min(m, in[i]);
-            }
-            out[o] = m;
+            out[o] = group_min(in, n_in, o);
         }
         __threadfence_block();
         __syncthreads();
@@ -1451,12 +1430,12 @@ static int launch_depth_passes(const uint32_t *d_idx, uint64_t n, uint8_t *d_typ
         // the brackets' partners on the compact list: in-block pairs, the tree's levels above (grids laid out for n
         // brackets, the kernels take the call's count from the result), the containers that span a block of brackets
         const uint32_t ncb_max = (uint32_t)((n + kCompactBlock - 1) / kCompactBlock);
-        hipLaunchKernelGGL(match_compact, dim3(ncb_max < MSJ_COMPACT_GRID ? ncb_max : MSJ_COMPACT_GRID), dim3(256), 0, s, brk_tok, brk_depth, d_result,
+        hipLaunchKernelGGL(match_compact, dim3(ncb_max < kCompactGrid ? ncb_max : kCompactGrid), dim3(256), 0, s, brk_tok, brk_depth, d_result,
                            o.d_prev, d_pairs, l1, l2, l3, opens, survivors, survivor_capacity(nb));
         for (int k = 4; k < t.nlev && k < 6; k++)
             hipLaunchKernelGGL(build_level_compact, dim3((t.cnt[k] + 255u) / 256u), dim3(256), 0, s, t.lv[k - 1], lvl[k], k, d_result, o.d_prev);
         if (t.nlev > 6) hipLaunchKernelGGL(build_upper_levels_compact, dim3(1), dim3(1024), 0, s, t, d_result, o.d_prev);
-        hipLaunchKernelGGL(match_brackets<true>, dim3(per_list < MSJ_MATCH_GRID ? per_list : MSJ_MATCH_GRID, lists), dim3(256), 0, s, d_type, opens,
+        hipLaunchKernelGGL(match_brackets<true>, dim3(per_list < kMatchGrid ? per_list : kMatchGrid, lists), dim3(256), 0, s, d_type, opens,
                            survivors, t, d_match, survivor_capacity(nb), 0u, d_result, resid, d_pairs, brk_tok, o.d_prev);
     } else if (want_match) {
         for (int k = 4; k < t.nlev && k < 6; k++)
@@ -1476,7 +1455,7 @@ static int launch_depth_passes(const uint32_t *d_idx, uint64_t n, uint8_t *d_typ
         // (the lane groups of 32 workgroups stride over each of the lists)
         // (block b appends to list b mod kSurvivorShards: a short call uses the first nb lists only, and a list then holds
         // the survivors of nb / kSurvivorShards blocks -- the grid follows, instead of 8 192 workgroups for a handful of tokens)
-        hipLaunchKernelGGL(match_brackets<false>, dim3(per_list < MSJ_MATCH_GRID ? per_list : MSJ_MATCH_GRID, lists), dim3(256), 0, s, d_type, opens,
+        hipLaunchKernelGGL(match_brackets<false>, dim3(per_list < kMatchGrid ? per_list : kMatchGrid, lists), dim3(256), 0, s, d_type, opens,
                            survivors, t, d_match, survivor_capacity(nb), o.match_bias, d_result, resid, d_pairs, no_brk, o.d_prev);
         if (resid)  // the closing brackets whose partner lies in front of this call (behind match_brackets: it writes both ends)
             hipLaunchKernelGGL(collect_closers, dim3(per_list < 8u ? per_list : 8u, lists), dim3(256), 0, s, opens, survivors, survivor_capacity(nb),
@@ -1954,11 +1933,7 @@ __global__ __launch_bounds__(kSpanThreads) void token_spans(const uint8_t *__res
                 *reinterpret_cast<uint4 *>(stage + 64u * j + 16 * q) = make_uint4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
             if (kSpans) {
             uint64_t pl[8];
-#if MSJ_SPAN_ABLATE == 3
-            for (int q = 0; q < 8; q++) pl[q] = x[q] | ((uint64_t)x[q + 8] << 32);
-#else
             msj::bitplanes(x, pl);
-#endif
             const msj::SpanClasses cl = msj::span_classes(pl);
             const uint32_t w = kSpanMapFront + 2u * j;
             *reinterpret_cast<uint2 *>(m_num + w) = make_uint2((uint32_t)cl.digit, (uint32_t)(cl.digit >> 32));
@@ -1997,7 +1972,7 @@ __global__ __launch_bounds__(kSpanThreads) void token_spans(const uint8_t *__res
         }
         MSJ_SPAN_ARRIVED();
         __syncthreads();
-        if (!kSpans || MSJ_SPAN_ABLATE == 1) {  // the type bytes only
+        if (!kSpans) {  // the type bytes only
             if (have0) {
                 c0 = stage[(uint32_t)(start0 - lo)];
                 c1 = have1 ? (uint32_t)stage[(uint32_t)(start1 - lo)] : 0u;
@@ -2052,7 +2027,7 @@ __global__ __launch_bounds__(kSpanThreads) void token_spans(const uint8_t *__res
             if (kFused) type[tok0 + 1] = (uint8_t)c1;
         }
     }
-    if (kFused && MSJ_SPAN_ABLATE != 2) {
+    if (kFused) {
         // the bracket counts of this wave's 128 tokens = chunk 4 * blockIdx.x + wave of the grid token_tiles uses (same
         // downstream: merge_chunk_counts, the scans, apply_depth -- which supplies the minimum / maximum of the running
         // depth that this kernel reduced with two DPP chains, an LDS hand-over and a second barrier per workgroup until
@@ -2096,26 +2071,13 @@ static uint32_t span_lds_limit(const msj_token_opts &o) { return o.lds_limit < k
 // msj_stage2_prep_device -- five waves (4 tiles) load one SIMD twice as much as the others, and the smaller group's
 // LDS (25 KB) lets six workgroups = 24 waves onto a CU instead of four = 20.  Halo 1 KiB against 2 KiB: no difference on minified; the larger one keeps
 // more last chunks of a group on the LDS path where tokens are sparse.
-#ifndef MSJ_TG_TILES
-#define MSJ_TG_TILES 3
-#endif
-#ifndef MSJ_TG_HALO_BLOCKS
-#define MSJ_TG_HALO_BLOCKS 32
-#endif
-constexpr uint32_t kTgTiles = MSJ_TG_TILES;
-constexpr uint32_t kTgHaloBlocks = MSJ_TG_HALO_BLOCKS;  // 2 KiB behind them (<= 64: one wave)
-#ifdef MSJ_TG_OVERLAP
-// EXPERIMENT (round 5, measured slower, profiles/r05/token_tiles_parts.txt): no wave of its own for the halo -- every wave
-// stages and classifies a full tile, the groups advance by the staged range less the halo, which the next group classifies
-// again as the start of its first tile (redundant work halo / advance instead of one wave in kTgTiles + 1)
-constexpr uint32_t kTgWaves = kTgTiles;
-constexpr uint32_t kTgBytes = kTgTiles * 4096u - kTgHaloBlocks * 64u;
-constexpr uint32_t kTgBlocks = kTgTiles * 64;
-#else
+// A geometry without a halo wave (every wave a full tile, the groups overlapping by the halo) measured slower
+// (profiles/r05/token_tiles_parts.txt).
+constexpr uint32_t kTgTiles = 3;
+constexpr uint32_t kTgHaloBlocks = 32;                 // 2 KiB behind them (<= 64: one wave)
 constexpr uint32_t kTgWaves = kTgTiles + 1;            // one wave per tile + one for the halo
 constexpr uint32_t kTgBytes = kTgTiles * 4096u;        // bytes of the buffer per workgroup
 constexpr uint32_t kTgBlocks = kTgTiles * 64 + kTgHaloBlocks;
-#endif
 constexpr uint32_t kTgThreads = 64 * kTgWaves;
 constexpr uint32_t kTgStage = kTgBlocks * 64;          // bytes staged
 constexpr uint32_t kTgMapWords = kSpanMapFront + 2 * kTgBlocks + 4;
@@ -2401,9 +2363,6 @@ __global__ __launch_bounds__(kTgThreads) void token_tiles(const uint8_t *__restr
     }
     const uint32_t j = threadIdx.x;  // lane j of the workgroup classifies block j of the range
     MSJ_TSTAMP(2);
-#ifdef MSJ_TILE_PRIO_CLASS
-    __builtin_amdgcn_s_setprio(MSJ_TILE_PRIO_CLASS);
-#endif
     if (kSpans) {
         // LDS written by this wave, read by this wave
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -2486,9 +2445,6 @@ __global__ __launch_bounds__(kTgThreads) void token_tiles(const uint8_t *__restr
     MSJ_TSTAMP(3);
     __syncthreads();
     MSJ_TSTAMP(4);
-#ifdef MSJ_TILE_PRIO_LOOP
-    __builtin_amdgcn_s_setprio(MSJ_TILE_PRIO_LOOP);
-#endif
 
     const TileMaps maps = {stage, m_num, m_flt, m_dot, m_ink, m_q, m_e, co};
     const bool wide = (reinterpret_cast<uintptr_t>(end) & 7u) == 0 &&
