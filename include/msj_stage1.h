@@ -608,6 +608,50 @@ int32_t msj_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, i
                              uint32_t *d_doc_first, uint64_t capacity, msj_documents_result *d_result, void *stream);
 
 /*
+ * ---- number values for stage 2 (after row f4; DERIVED) ---------------------------------------
+ * msj_number_values_device -- the reference's Int(span) / Float64(span) (number_parsing.mojo:60-78, what feeds
+ * TapeWriter.append_s64 / append_double) for every number token of one segment, as a COMPACT LIST: one 16-byte record
+ * per token whose d_flags (from any span call for the same d_idx) has MSJ_SPAN_NUMBER, in token order.  A consumer that
+ * walks the tokens in order takes the next record at every number token; `token` serves random access.
+ * The definition (RFC 8259 plus the value Python's json gives):
+ *   text       -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? starting at idx[i], followed by a structural byte ({}[]:,), a
+ *              blank (space, tab, LF, CR), or the end of the buffer (bytes at or past len read as blanks).  Anything else
+ *              is MSJ_NUMBER_ERR_SYNTAX (01, -, 1., 1.e5, 1e, 1e+, 1.5x, 12a; every token flagged MSJ_SPAN_BAD)
+ *   integer    no fraction and no exponent: MSJ_NUMBER_INT64, the exact value in [-2^63, 2^63 - 1]; outside that range
+ *              MSJ_NUMBER_ERR_RANGE (the reference's Int is 64-bit too); -0 is the integer 0
+ *   float      anything else: MSJ_NUMBER_DOUBLE, the binary64 nearest to the exact decimal value, ties to even (CPython's
+ *              float()), for any number of digits and any exponent; underflow gives +-0 or a correctly rounded subnormal,
+ *              sign kept (-1e-400 is -0.0); a value whose correct rounding is +-infinity is MSJ_NUMBER_ERR_RANGE
+ * d_result: n_numbers counts every number token, also those beyond `capacity` (only the first `capacity` records are
+ * stored); first_error is the token index of the first erroneous number in token order (where the reference's stage 2
+ * stops with NUMBER_ERROR), UINT64_MAX if none.  Arguments and limits as msj_token_spans_device: one uint32 segment,
+ * n < 2^31 (MSJ_CAPACITY otherwise); d_idx 16-byte aligned, d_flags and d_result 8-byte, d_numbers 16-byte (MSJ_ERR_BAD_ARGUMENT,
+ * nothing launched).  n = 0 writes a zero result with first_error = UINT64_MAX.  Asynchronous on `stream`, no host round
+ * trip on any path (chains behind msj_stage2_prep_pairs_device in one stream).  Workspace: the context's own, see
+ * msj_number_values_workspace_bytes.
+ */
+#define MSJ_NUMBER_INT64 1u      /* bits = the int64 value */
+#define MSJ_NUMBER_DOUBLE 2u     /* bits = the IEEE-754 binary64 bit pattern */
+#define MSJ_NUMBER_ERR_SYNTAX 3u /* bits = 0 */
+#define MSJ_NUMBER_ERR_RANGE 4u  /* bits = 0 */
+typedef struct msj_number {      /* 16 bytes: one record per number token, in token order */
+    uint64_t bits;
+    uint32_t token;              /* index of the token in d_idx / d_type / d_flags */
+    uint32_t kind;               /* MSJ_NUMBER_* */
+} msj_number;
+typedef struct msj_numbers_result {
+    uint64_t n_numbers;   /* number tokens in the call, also those beyond capacity */
+    uint64_t n_errors;    /* records of an ERR kind */
+    uint64_t first_error; /* token index of the first erroneous number in token order; UINT64_MAX: none */
+    uint64_t n_slow;      /* numbers the exact fallback resolved (diagnostic) */
+} msj_numbers_result;
+int32_t msj_number_values_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                                 const uint8_t *d_flags, msj_number *d_numbers, uint64_t capacity,
+                                 msj_numbers_result *d_result, void *stream);
+/* Device workspace of one msj_number_values_device call over n tokens of a len-byte segment (the context keeps it). */
+uint64_t msj_number_values_workspace_bytes(uint64_t n, uint64_t len);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

@@ -46,6 +46,22 @@ class MsjDocumentsResult(ctypes.Structure):
                 ("tokens_complete", ctypes.c_uint64), ("resume_offset", ctypes.c_uint64)]
 
 
+class MsjNumber(ctypes.Structure):
+    """``msj_number`` (include/msj_stage1.h): one record per number token, in token order."""
+
+    _fields_ = [("bits", ctypes.c_uint64), ("token", ctypes.c_uint32), ("kind", ctypes.c_uint32)]
+
+
+class MsjNumbersResult(ctypes.Structure):
+    """``msj_numbers_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("n_numbers", ctypes.c_uint64), ("n_errors", ctypes.c_uint64), ("first_error", ctypes.c_uint64),
+                ("n_slow", ctypes.c_uint64)]
+
+
+NUMBER_INT64, NUMBER_DOUBLE, NUMBER_ERR_SYNTAX, NUMBER_ERR_RANGE = 1, 2, 3, 4
+
+
 class MsjSegment(ctypes.Structure):
     _fields_ = [
         ("byte_base", ctypes.c_uint64),
@@ -57,6 +73,7 @@ class MsjSegment(ctypes.Structure):
 
 assert ctypes.sizeof(MsjCarry) == 64
 assert ctypes.sizeof(MsjSegment) == 32
+assert ctypes.sizeof(MsjNumber) == 16 and ctypes.sizeof(MsjNumbersResult) == 32
 
 _lib = None
 
@@ -155,6 +172,11 @@ def load():
     lib.msj_documents_device.argtypes = [ctypes.c_void_p, u8p, ctypes.c_uint64, ctypes.c_int32, u32p, ctypes.c_uint64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_number_values_device.restype = ctypes.c_int32
+    lib.msj_number_values_device.argtypes = [ctypes.c_void_p, u8p, ctypes.c_uint64, u32p, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_number_values_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_number_values_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

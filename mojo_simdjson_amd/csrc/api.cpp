@@ -100,6 +100,8 @@ struct msj_ctx {
     msj_token_opts tok_opts;      // test hooks of the token calls (msj_debug_set_span_limits / _span_mode): per context
     void *doc_ws = nullptr;       // block counts of the document split
     uint64_t doc_ws_bytes = 0;
+    void *num_ws = nullptr;       // msj_number_values_device: block counts / offsets, the fallback and long-number lists
+    uint64_t num_ws_bytes = 0;
 };
 
 namespace {
@@ -711,6 +713,7 @@ void msj_ctx_destroy(msj_ctx *ctx) {
     if (ctx->resid) (void)hipFree(ctx->resid);
     if (ctx->span_fix) (void)hipFree(ctx->span_fix);
     if (ctx->doc_ws) (void)hipFree(ctx->doc_ws);
+    if (ctx->num_ws) (void)hipFree(ctx->num_ws);
     if (ctx->carries) (void)hipFree(ctx->carries);
     if (ctx->d_in) (void)hipFree(ctx->d_in);
     if (ctx->d_idx) (void)hipFree(ctx->d_idx);
@@ -1035,6 +1038,35 @@ int32_t msj_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, i
                                 pre, stream) == 0
                ? MSJ_SUCCESS
                : MSJ_ERR_HIP;
+}
+
+extern "C" int msj_launch_number_values(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_flags,
+                                        msj_number *d_numbers, uint64_t capacity, msj_numbers_result *d_result, void *d_ws, void *stream);
+
+int32_t msj_number_values_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                                 const uint8_t *d_flags, msj_number *d_numbers, uint64_t capacity,
+                                 msj_numbers_result *d_result, void *stream) {
+    if (!ctx || !d_result) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_buf || !d_idx || !d_flags)) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && !d_numbers) return MSJ_ERR_BAD_ARGUMENT;
+    if (len > MSJ_MAX_SEGMENT_BYTES || n >= (1ull << 31)) return MSJ_CAPACITY;
+    if ((reinterpret_cast<uintptr_t>(d_idx) & 15u) || (reinterpret_cast<uintptr_t>(d_flags) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_numbers) & 15u) || (reinterpret_cast<uintptr_t>(d_result) & 7u))
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (!hip_ok(hipSetDevice(ctx->device))) return MSJ_ERR_HIP;
+    const uint64_t need = msj_number_values_workspace_bytes(n, len);
+    if (need > ctx->num_ws_bytes) {
+        if (ctx->num_ws) {
+            (void)hipDeviceSynchronize();
+            (void)hipFree(ctx->num_ws);
+        }
+        ctx->num_ws = nullptr;
+        ctx->num_ws_bytes = 0;
+        if (!hip_ok(hipMalloc(&ctx->num_ws, need + need / 4))) return MSJ_MEMALLOC;
+        ctx->num_ws_bytes = need + need / 4;
+    }
+    return msj_launch_number_values(d_buf, len, d_idx, n, d_flags, d_numbers, capacity, d_result, ctx->num_ws, stream) == 0 ? MSJ_SUCCESS
+                                                                                                                       : MSJ_ERR_HIP;
 }
 
 int32_t msj_device_alloc(msj_ctx *ctx, uint64_t bytes, void **d_out) {

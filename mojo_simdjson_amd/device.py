@@ -246,6 +246,26 @@ class Stage1Device:
             return d_doc_first, d_result
         return d_doc_first, _lib.MsjDocumentsResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
 
+    def number_values(self, d_buf, length, d_idx, n, d_flags, capacity=None, d_result=None, sync=True):
+        """Values of the number tokens (``msj_number_values_device``): one 16-byte ``msj_number`` record per token whose
+        d_flags (from ``token_spans`` / ``stage2_prep*`` for the same d_idx) has MSJ_SPAN_NUMBER, in token order -- the exact
+        int64 or the nearest binary64, or a syntax / range error.  capacity: records stored at most (default n).
+        Returns (d_numbers, msj_numbers_result) -- d_numbers an int64 tensor of shape (capacity, 2): [k, 0] the bits,
+        [k, 1] token | kind << 32 -- blocking for the 32-byte result; with sync=False (d_numbers, d_result) with nothing
+        waited for."""
+        n = int(n)
+        capacity = n if capacity is None else int(capacity)
+        d_numbers = torch.empty((max(capacity, 1), 2), dtype=torch.int64, device=self.device)
+        if d_result is None:
+            d_result = torch.zeros(32, dtype=torch.uint8, device=self.device)
+        rc = self.lib.msj_number_values_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), n, _ptr(d_flags), _ptr(d_numbers),
+                                               capacity, _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_number_values_device failed: {rc}")
+        if not sync:
+            return d_numbers, d_result
+        return d_numbers, _lib.MsjNumbersResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
+
     def set_wait_ticks(self, ticks):
         """Test hook: bound of the single-pass kernel's inter-workgroup waits in 10 ns ticks (default 2 s)."""
         self.lib.msj_debug_set_wait_ticks(self.ctx, int(ticks))
