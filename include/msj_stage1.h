@@ -553,11 +553,13 @@ int32_t msj_stage2_prep_chain_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_
  * the token's index inside its segment: the element at which that token's type / depth / end / flags / match are
  * stored) of the other end of its container -- also when the container is opened in one segment and closed in a later
  * one (the stack of start_container / end_container, generic/stage2/tape_builder.mojo:235-272, has no such border):
- * every segment leaves the brackets it could not pair in a residual list of the context's (their depth is their place
- * in it), and a stitch behind the last segment pairs them.  0xFFFFFFFF: not a bracket, or no partner inside the shard.
+ * every segment leaves the brackets it could not pair in a residual list of the context's (their depth above the
+ * segment's minimum running depth is their place in it), and a stitch behind the last segment pairs them.  0xFFFFFFFF:
+ * not a bracket, or no partner inside the shard.
  * Limits with d_match: at most 32 segments and fewer than 2^32 - 1 output elements (MSJ_CAPACITY otherwise); at a segment
- * border, partners are stitched for nesting up to 65 536 containers deep -- beyond that the brackets keep 0xFFFFFFFF and
- * bit 31 of d_results[n_segments - 1].reserved is set.  The single calls (msj_stage2_prep_chain_device,
+ * border, every container less than 65 536 levels above the shard's minimum running depth is stitched.  With d_prev =
+ * NULL and a well-formed document, that means depth < 65 536.  Further above, a container cut by a border may keep
+ * 0xFFFFFFFF at both ends; bit 31 of d_results[n_segments - 1].reserved is then set.  The single calls (msj_stage2_prep_chain_device,
  * msj_tokens_chain_device) write into arrays of the caller's for each call and keep their partners local to the call.
  */
 int32_t msj_stage2_prep_segments(msj_ctx *ctx, const uint8_t *d_buf, const msj_segment *segments, uint32_t n_segments,

@@ -966,10 +966,15 @@ int32_t msj_stage2_prep_segments(msj_ctx *ctx, const uint8_t *d_buf, const msj_s
         if (!hip_ok(hipMemsetAsync(ctx->resid, 0, need * sizeof(uint32_t), st))) return MSJ_ERR_HIP;
     }
     uint64_t off = 0;
+    // the result each segment goes on from: that of the LAST segment with tokens (d_prev in front of them).  A segment
+    // without tokens carries the stream's depth, minimum and maximum on unchanged, but with n = 0 the call behind it
+    // could not tell it from the start of a stream and would drop the minimum and maximum of the tokens in front.
+    const msj_tokens_result *prev = d_prev;
     for (uint32_t s = 0; s < n_segments; s++) {
         const msj_segment &sg = segments[s];
         const uint64_t n = sg.count;
-        const uint32_t *idx = d_idx + (sg.index_begin - begin0);
+        // (a segment without tokens -- inside a long string -- reads no index: its slice may start anywhere)
+        const uint32_t *idx = n ? d_idx + (sg.index_begin - begin0) : nullptr;
         if (n && (reinterpret_cast<uintptr_t>(idx) & 15u)) {
             // stage 1 writes a shard's indices densely, so a later segment's slice starts wherever the one in front
             // ended: the token kernels read index quads, so it is copied to an aligned buffer first (4 bytes per token
@@ -996,8 +1001,9 @@ int32_t msj_stage2_prep_segments(msj_ctx *ctx, const uint8_t *d_buf, const msj_s
         const int32_t rc = prep_chain_impl(ctx, d_buf + (sg.byte_base - base0), sg.byte_len, idx, n, d_type ? d_type + off : nullptr,
                                            d_depth ? d_depth + off : nullptr, d_match ? d_match + off : nullptr,
                                            d_end ? d_end + off : nullptr, d_flags ? d_flags + off : nullptr, &d_results[s],
-                                           s == 0 ? d_prev : &d_results[s - 1], stream, (uint32_t)off, resid);
+                                           prev, stream, (uint32_t)off, resid);
         if (rc != MSJ_SUCCESS) return rc;
+        if (n) prev = &d_results[s];
         off += (n + 3u) & ~3ull;  // every segment's slices start 16-byte aligned (8 for the byte arrays: n rounded to 4 ... 8 below)
         off = (off + 7u) & ~7ull;
     }

@@ -298,7 +298,9 @@ __global__ __launch_bounds__(1024) void scan_blocks(const int32_t *__restrict__ 
     }
     // apply_depth / match_compact append the opening brackets they could not pair inside their block: one counter per list shard
     if (survivors && threadIdx.x < kSurvivorShards) survivors[threadIdx.x * kSurvivorStride] = 0u;
-    if (resid && threadIdx.x < 4) resid[threadIdx.x] = 0u;  // the counts of this call's residual brackets (match_brackets, collect_closers)
+    // the counts of this call's residual brackets (match_brackets, collect_closers) and, in word 2, the call's own minimum
+    // running depth, seeded with its start depth here and lowered by min_max_depth: both lists are indexed from it
+    if (resid && threadIdx.x < 4) resid[threadIdx.x] = threadIdx.x == 2 ? (uint32_t)(prev ? prev->final_depth : 0) : 0u;
 }
 
 // (3) depth of every token AND match[] -- a partner index per token -- for the calls that ask for it (the calls without,
@@ -827,8 +829,10 @@ __global__ __launch_bounds__(kThreads) void depth_rows(const uint8_t *__restrict
 // (4) minimum / maximum of the running depth over the stream, from the per-block values apply_depth left in the block
 //     aggregates (words 1 and 2): the scan set the result's fields to what ITS aggregates gave -- nothing (kNone /
 //     -kNone) when the kernel in front only counted brackets (token_tiles) -- and this folds the exact values in.
+//     resid (msj_stage2_prep_segments): word 2 takes this CALL's minimum too (the result's is the stream's).
 constexpr uint32_t kMinMaxGroups = 64;
-__global__ __launch_bounds__(256) void min_max_depth(const int32_t *__restrict__ block_mm, uint32_t nblocks, msj_tokens_result *__restrict__ result) {
+__global__ __launch_bounds__(256) void min_max_depth(const int32_t *__restrict__ block_mm, uint32_t nblocks, msj_tokens_result *__restrict__ result,
+                                                     uint32_t *__restrict__ resid) {
     __shared__ int w_mn[4], w_mx[4];
     int mn = kNone, mx = -kNone;
     for (uint32_t b = blockIdx.x * 256u + threadIdx.x; b < nblocks; b += gridDim.x * 256u) {
@@ -848,6 +852,7 @@ __global__ __launch_bounds__(256) void min_max_depth(const int32_t *__restrict__
         mx = max(max(w_mx[0], w_mx[1]), max(w_mx[2], w_mx[3]));
         if (mn != kNone) atomicMin(&result->min_depth, mn);
         if (mx != -kNone) atomicMax(&result->max_depth, mx);
+        if (resid && mn != kNone) atomicMin(reinterpret_cast<int *>(&resid[2]), mn);
     }
 }
 
@@ -1063,9 +1068,10 @@ __global__ __launch_bounds__(256) void match_brackets(const uint8_t *__restrict_
                 match[pos] = i + match_bias;
             }
         } else if (have && sub == 0u && resid) {
-            // never closed inside this call: the unclosed opening brackets nest, so the one at depth `target` is entry
-            // final_depth - 1 - target of the call's residual list (msj_stage2_prep_segments stitches the segments)
-            const uint32_t j = (uint32_t)(result->final_depth - 1 - target);
+            // never closed inside this call: the unclosed opening brackets nest, one per level from the call's minimum
+            // running depth m up, so the one at depth `target` is entry target - m of the call's residual list
+            // (msj_stage2_prep_segments stitches the segments; the cap drops the levels furthest above m)
+            const uint32_t j = (uint32_t)(target - (int)resid[2]);
             atomicAdd(&resid[0], 1u);
             if (j < MSJ_RESID_CAP) resid[4u + j] = i;
         }
@@ -1077,22 +1083,23 @@ __global__ __launch_bounds__(256) void match_brackets(const uint8_t *__restrict_
 // What is left are (a) opening brackets never closed in the call -- match_brackets finds them: the walk of a survivor
 // that reaches the call's end -- and (b) closing brackets whose partner is in front of the call: among the listed
 // candidates (apply_depth: below the block's start depth, unpaired in the block) those that match_brackets, which
-// writes both ends, has not touched either.  Both sets nest, so the bracket's DEPTH is its place in the list: no
-// sorting, no counting pass.  stitch_partners then pairs closing bracket k of segment s (depth c) with the unclosed
-// opening bracket at depth c of the latest segment in front that holds one.
+// writes both ends, has not touched either.  Both sets nest, one bracket per level from the call's minimum running depth
+// m (its start depth included; resid[2]) up, so the bracket's DEPTH - m is its place in the list: no sorting, no
+// counting pass, and the cap of the list drops the levels furthest above m, never the outermost ones.  stitch_partners
+// then pairs closing bracket k of segment s (depth c) with the unclosed opening bracket at depth c of the latest segment
+// in front that holds one.
 __global__ __launch_bounds__(256) void collect_closers(const uint32_t *__restrict__ opens, const uint32_t *__restrict__ n_opens,
                                                        uint64_t list_capacity, const int32_t *__restrict__ depth,
-                                                       const uint32_t *__restrict__ match, const msj_tokens_result *__restrict__ prev,
-                                                       uint32_t *__restrict__ resid) {
+                                                       const uint32_t *__restrict__ match, uint32_t *__restrict__ resid) {
     const uint32_t total = n_opens[blockIdx.y * kSurvivorStride];
     opens += (uint64_t)blockIdx.y * list_capacity;
-    const int d0 = prev ? prev->final_depth : 0;
+    const int m = (int)resid[2];
     for (uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x; w < total; w += (uint64_t)gridDim.x * 256u) {
         const uint32_t entry = opens[w];
         if (!(entry >> 31)) continue;
         const uint32_t i = entry & 0x7FFFFFFFu;
         if (match[i] != 0xFFFFFFFFu) continue;  // an opening bracket of an earlier block of this call claimed it
-        const uint32_t k = (uint32_t)(d0 - 1 - depth[i]);
+        const uint32_t k = (uint32_t)(depth[i] - m);
         atomicAdd(&resid[1], 1u);
         if (k < MSJ_RESID_CAP) resid[4u + MSJ_RESID_CAP + k] = i;
     }
@@ -1105,15 +1112,16 @@ __global__ __launch_bounds__(256) void stitch_partners(const msj_stitch_args a, 
     const uint32_t *rs = a.resid[s];
     const uint32_t n_close = rs[1];
     bool clipped = n_close > MSJ_RESID_CAP;
-    const int d0 = results[s - 1].final_depth;  // the depth this segment starts at
+    // the segment's lowest level: its closing brackets without a partner close the levels m .. (start depth - 1)
+    const int m = results[s - 1].final_depth - (int)n_close;
     for (uint32_t k = threadIdx.x; k < n_close && k < MSJ_RESID_CAP; k += 256u) {
-        const int c = d0 - 1 - (int)k;  // the closing bracket's depth = its container's
+        const int c = m + (int)k;  // the closing bracket's depth = its container's
         const uint32_t ci = rs[4u + MSJ_RESID_CAP + k];
         for (int q = (int)s - 1; q >= 0; q--) {
             const uint32_t *rq = a.resid[q];
             const int df = results[q].final_depth, nu = (int)rq[0];
-            if (c < df && c >= df - nu) {  // segment q left an opening bracket at this depth open
-                const uint32_t j = (uint32_t)(df - 1 - c);
+            if (c < df && c >= df - nu) {  // segment q left an opening bracket at this depth open (its levels df - nu .. df - 1)
+                const uint32_t j = (uint32_t)(c - (df - nu));
                 if (j < MSJ_RESID_CAP) {
                     const uint32_t oi = rq[4u + j];
                     match[a.offsets[s] + ci] = a.offsets[q] + oi;
@@ -1128,7 +1136,7 @@ __global__ __launch_bounds__(256) void stitch_partners(const msj_stitch_args a, 
         }
     }
     (void)prev;
-    if (clipped) atomicOr(&results[a.n_segments - 1u].reserved, 0x80000000u);  // nesting deeper than MSJ_RESID_CAP at a border
+    if (clipped) atomicOr(&results[a.n_segments - 1u].reserved, 0x80000000u);  // a border cut nesting over MSJ_RESID_CAP levels high
 }
 
 
@@ -1423,7 +1431,7 @@ static int launch_depth_passes(const uint32_t *d_idx, uint64_t n, uint8_t *d_typ
     else if (nb)
         hipLaunchKernelGGL(depth_rows<false>, dim3((nb + kRowsWaves - 1u) / kRowsWaves), dim3(kThreads), 0, s, d_type, n, nb, start, super_start, super_open,
                            open_start, d_depth, doc_agg, agg, o.d_prev, no_brk, no_level);
-    if (nb) hipLaunchKernelGGL(min_max_depth, dim3(nb < kMinMaxGroups * 256u ? (nb + 255u) / 256u : kMinMaxGroups), dim3(256), 0, s, agg, nb, d_result);
+    if (nb) hipLaunchKernelGGL(min_max_depth, dim3(nb < kMinMaxGroups * 256u ? (nb + 255u) / 256u : kMinMaxGroups), dim3(256), 0, s, agg, nb, d_result, resid);
     const uint32_t lists = nb < kSurvivorShards ? nb : kSurvivorShards;
     const uint32_t per_list = nb / kSurvivorShards / 8u + 1u;  // ~2 survivors per block, 16 brackets per workgroup and round
     if (compact) {
@@ -1459,7 +1467,7 @@ static int launch_depth_passes(const uint32_t *d_idx, uint64_t n, uint8_t *d_typ
                            survivors, t, d_match, survivor_capacity(nb), o.match_bias, d_result, resid, d_pairs, no_brk, o.d_prev);
         if (resid)  // the closing brackets whose partner lies in front of this call (behind match_brackets: it writes both ends)
             hipLaunchKernelGGL(collect_closers, dim3(per_list < 8u ? per_list : 8u, lists), dim3(256), 0, s, opens, survivors, survivor_capacity(nb),
-                               d_depth, d_match, o.d_prev, resid);
+                               d_depth, d_match, resid);
     }
     return (int)hipGetLastError();
 }

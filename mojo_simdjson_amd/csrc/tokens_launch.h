@@ -26,8 +26,9 @@ struct msj_token_opts {
 };
 
 // residual brackets of one call (device, uint32 words): [0] unclosed opening brackets, [1] closing brackets without a
-// partner, [2..3] spare; then MSJ_RESID_CAP positions of the former -- entry j = the one at depth final_depth - 1 - j --
-// and MSJ_RESID_CAP of the latter -- entry k = the one at depth start_depth - 1 - k (token indices local to the call)
+// partner, [2] the call's minimum running depth m (int32; its start depth included), [3] spare; then MSJ_RESID_CAP
+// positions of the former -- entry j = the one at depth m + j -- and MSJ_RESID_CAP of the latter -- entry k = the one at
+// depth m + k (token indices local to the call)
 #define MSJ_RESID_CAP 65536u
 #define MSJ_RESID_WORDS (4u + 2u * MSJ_RESID_CAP)
 #define MSJ_STITCH_MAX_SEGMENTS 32u

@@ -653,9 +653,14 @@ def test_prep_segments_of_one_shard(dev):
         assert stitched >= 2 * 7 and stitched % 2 == 0, stitched  # brackets whose partner lies in another segment
         # ... and a shard that starts and ends in the middle of things: segments 2 .. 6 alone (closing brackets whose
         # partners lie in front of the shard and opening ones never closed keep 0xFFFFFFFF; everything between pairs up)
+        # (d_prev: the result of segment 1, so that depths and results go on as in the whole shard)
         sub = segs[2:7]
-        d_prev = torch.zeros(24, dtype=torch.uint8, device=dev.device)
-        offs2, t2, d2, m2, e2, f2, res2 = dev.stage2_prep_segments(d_buf[sub[0][0]:], sub, d_idx[sub[0][2]:], match=True, d_prev=None)
+        d_prev = torch.frombuffer(bytearray(bytes(results[1])), dtype=torch.uint8).to(dev.device)
+        offs2, t2, d2, m2, e2, f2, res2 = dev.stage2_prep_segments(d_buf[sub[0][0]:], sub, d_idx[sub[0][2]:], match=True, d_prev=d_prev)
+        for k, sg in enumerate(sub):
+            assert torch.equal(d2[offs2[k]:offs2[k] + sg[3]], d[offs[k + 2]:offs[k + 2] + sg[3]]), k
+            r, w = res2[k], results[k + 2]
+            assert (r.n, r.final_depth, r.min_depth, r.max_depth) == (w.n, w.final_depth, w.min_depth, w.max_depth), k
         lo_tok, hi_tok = sub[0][2] - segs[0][2], sub[-1][2] + sub[-1][3] - segs[0][2]
         wm_sub = helpers.oracle_match(wt_all[lo_tok:hi_tok]).astype(np.int64)
         pos2 = np.concatenate([offs2[s] + np.arange(sg[3], dtype=np.int64) for s, sg in enumerate(sub)])
