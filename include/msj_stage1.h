@@ -654,6 +654,72 @@ int32_t msj_number_values_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t le
 uint64_t msj_number_values_workspace_bytes(uint64_t n, uint64_t len);
 
 /*
+ * ---- stage 2's verdict for one document (DERIVED) ---------------------------------------------
+ * msj_validate_device -- the code and the token at which the reference's walk_document
+ * (generic/stage2/json_iterator.mojo:40-254) with TapeBuilder's visitors (tape_builder.mojo, atom_parsing.mojo,
+ * string_parsing.mojo:267-386) would stop, for ONE document in ONE uint32 segment whose stage 1 returned MSJ_SUCCESS (so
+ * n >= 1 and every string is closed), with d_depth from a call that started at depth 0 (d_prev == NULL).  The reference
+ * cannot run here, so this text is the definition; it follows the reference line by line except where listed below.
+ * The walk is not done serially: the state in which the walker meets token i follows from at most three tokens in front
+ * of i and one hop through d_match, provided no earlier token is in error, and the walker returns the code of the FIRST
+ * token in error -- so every token is judged on its own and the verdict is a minimum over positions.
+ * Per token i in [0, n] (token n is the end of the stream: a token that matches nothing), in a valid prefix:
+ *   structure  the walker's state machine as written: after '{' a key string or '}'; after a key ':'; after ':', '[', or
+ *              a ',' inside an array, a value ('{', '[', '"', '-', 0-9, t, f, n; any other first byte is TAPE_ERROR 3, as
+ *              in visit_primitive :309-329); after a ',' inside an object a key string; after a value ',' or the closing
+ *              bracket of the container's own kind; after the root value nothing (i == n), else TAPE_ERROR at i
+ *              (:248-253).  At token 0: a root '{' / '[' whose LAST token is not '}' / ']' is TAPE_ERROR at token 0 (:54-59)
+ *   depth      a non-empty container (its next token is not its own closing bracket; {} and [] never count, :62-76,
+ *              :114-130, :193-211) opened at token i has walker depth d_depth[i] + 1.  '{': DEPTH_ERROR 4 if that is
+ *              > max_depth (:87); '[': if it is >= max_depth (:176).  Both comparisons as the reference writes them
+ *   atoms      t / f / n must spell true / false / null and be followed by one of {}[]:, space, tab, LF, CR or the end of
+ *              the buffer (bytes at or past len read as blanks, atom_parsing.mojo:34-80): else code 6 / 7 / 8
+ *   strings    (keys too, visit_key), only where d_flags has MSJ_SPAN_ESCAPED: walking the body up to d_end[i], every
+ *              backslash that starts an escape is followed by one of " \ / b f n r t, or by u and four hex digits; a code
+ *              unit in D800-DBFF must be followed at once by \u and four hex digits in DC00-DFFF (the pair is one escape);
+ *              a code unit in DC00-DFFF on its own is an error (handle_unicode_codepoint with allow_replacement = False,
+ *              :267-327; parse_string :353-381).  Else STRING_ERROR 5.  Exact at any body length
+ *   numbers    not re-parsed: d_numbers (optional) is the device msj_numbers_result of a msj_number_values_device call over
+ *              the same tokens; its first_error token competes as NUMBER_ERROR 9.  NULL: numbers are not checked and
+ *              MSJ_VALIDATE_NUMBERS_UNCHECKED is set in the result
+ *   count      a container whose 1 + (commas directly inside it) exceeds 0xFFFFFF is MSJ_CAPACITY at its closing bracket
+ *              (end_container, tape_builder.mojo:257-264).  Only a container with at least 2 * 0xFFFFFF + 1 tokens between
+ *              its brackets can reach that: the direct commas (type == ',' and d_depth == d_depth[open] + 1 between the
+ *              brackets) of up to MSJ_VALIDATE_BIG_CONTAINERS such containers are counted exactly; a call that finds none
+ *              does no second read of the arrays.  More than that: no count is checked, MSJ_VALIDATE_COUNTS_CLIPPED is
+ *              set, and with that flag a code of 0 does not rule out MSJ_CAPACITY
+ *   one code per token, first token wins: at a token a structure or depth error comes before a content error (string /
+ *              atom / number / count).  The result is the smallest i with a code, and that code.
+ * Deviations from the reference: (1) a root {} / [] is valid: the reference forgets the advance() at :61-76 (the three
+ * other empty-container sites have it) and returns TAPE_ERROR for these two documents; upstream simdjson advances.
+ * (2) the number grammar is msj_number_values_device's (RFC 8259), not Mojo's Int() / Float64().  (3) for '{' at walker
+ * depth == max_depth the reference's comparison passes and then indexes its lists one past the end; here it just passes.
+ * Inputs are exactly what msj_stage2_prep_device(..., d_match != NULL, ...) wrote for the same d_idx.  Alignment and limits
+ * as that call (d_idx, d_depth, d_match, d_end 16-byte, d_type, d_flags, d_numbers, d_result 8-byte: MSJ_ERR_BAD_ARGUMENT;
+ * len > MSJ_MAX_SEGMENT_BYTES or n >= 2^31: MSJ_CAPACITY; nothing launched); n == 0 or max_depth == 0 is
+ * MSJ_ERR_BAD_ARGUMENT.  Asynchronous on `stream`, no host round trip on any path, workspace in the context.  Safe on ANY
+ * token arrays stage 1 + prep can produce from arbitrary bytes: a neighbour that cannot be resolved (no partner, a token in
+ * front of token 0) means an earlier token is already in error, so the token reports nothing; no index derived from
+ * d_match is used unchecked.
+ */
+#define MSJ_VALIDATE_NUMBERS_UNCHECKED 1u
+#define MSJ_VALIDATE_COUNTS_CLIPPED 2u
+#define MSJ_VALIDATE_BIG_CONTAINERS 64u
+typedef struct msj_validate_result {
+    int32_t code;          /* reference code: 0, 1, 3..9 */
+    uint32_t flags;        /* MSJ_VALIDATE_* */
+    uint64_t error_token;  /* token index in [0, n]; UINT64_MAX when code == 0 */
+    uint64_t error_offset; /* d_idx[error_token], len for token n; UINT64_MAX when code == 0 */
+    uint64_t n_escaped;    /* strings whose escapes were walked (diagnostic) */
+} msj_validate_result;
+int32_t msj_validate_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                            const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
+                            const uint32_t *d_end, const uint8_t *d_flags, const msj_numbers_result *d_numbers,
+                            uint32_t max_depth, msj_validate_result *d_result, void *stream);
+/* Device workspace of one msj_validate_device call over n tokens of a len-byte segment (the context keeps it). */
+uint64_t msj_validate_workspace_bytes(uint64_t n, uint64_t len);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

@@ -62,6 +62,16 @@ class MsjNumbersResult(ctypes.Structure):
 NUMBER_INT64, NUMBER_DOUBLE, NUMBER_ERR_SYNTAX, NUMBER_ERR_RANGE = 1, 2, 3, 4
 
 
+class MsjValidateResult(ctypes.Structure):
+    """``msj_validate_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("error_token", ctypes.c_uint64),
+                ("error_offset", ctypes.c_uint64), ("n_escaped", ctypes.c_uint64)]
+
+
+VALIDATE_NUMBERS_UNCHECKED, VALIDATE_COUNTS_CLIPPED, VALIDATE_BIG_CONTAINERS = 1, 2, 64
+
+
 class MsjSegment(ctypes.Structure):
     _fields_ = [
         ("byte_base", ctypes.c_uint64),
@@ -74,6 +84,7 @@ class MsjSegment(ctypes.Structure):
 assert ctypes.sizeof(MsjCarry) == 64
 assert ctypes.sizeof(MsjSegment) == 32
 assert ctypes.sizeof(MsjNumber) == 16 and ctypes.sizeof(MsjNumbersResult) == 32
+assert ctypes.sizeof(MsjValidateResult) == 32
 
 _lib = None
 
@@ -177,6 +188,11 @@ def load():
                                              ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_number_values_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_number_values_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    lib.msj_validate_device.restype = ctypes.c_int32
+    lib.msj_validate_device.argtypes = [ctypes.c_void_p, u8p, ctypes.c_uint64, u32p, ctypes.c_uint64] + [ctypes.c_void_p] * 6 + \
+        [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_validate_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_validate_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

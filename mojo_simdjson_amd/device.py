@@ -266,6 +266,41 @@ class Stage1Device:
             return d_numbers, d_result
         return d_numbers, _lib.MsjNumbersResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
 
+    def validate(self, d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers_result=None, max_depth=100,
+                 d_result=None, sync=True):
+        """Stage 2's verdict for one document (``msj_validate_device``): the code and the token at which the reference's
+        ``walk_document`` would stop.  The arrays are what ``stage2_prep(match=True)`` wrote for the same d_idx;
+        d_numbers_result: the device ``msj_numbers_result`` of ``number_values(..., sync=False)`` over the same tokens (None:
+        numbers are not checked, MSJ_VALIDATE_NUMBERS_UNCHECKED is set).  Returns the ``MsjValidateResult`` -- blocking for
+        its 32 bytes; with sync=False the device tensor that holds it, nothing waited for."""
+        if d_result is None:
+            d_result = torch.zeros(32, dtype=torch.uint8, device=self.device)
+        rc = self.lib.msj_validate_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), int(n), _ptr(d_type), _ptr(d_depth),
+                                          _ptr(d_match), _ptr(d_end), _ptr(d_flags),
+                                          _ptr(d_numbers_result) if d_numbers_result is not None else None, int(max_depth),
+                                          _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_validate_device failed: {rc}")
+        if not sync:
+            return d_result
+        return _lib.MsjValidateResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
+
+    def validate_document(self, d_buf, length, max_depth=100):
+        """Is this device buffer one valid JSON document, and if not, which error and where: stage 1, ``stage2_prep`` with
+        partners, ``number_values`` and ``validate`` enqueued on one stream.  Returns stage 1's code if that is not 0, else
+        the ``MsjValidateResult``.  (The token count sizes the later launches: it is the one value read in between.)"""
+        length = int(length)
+        d_idx = torch.empty(length + 3 + 4, dtype=torch.int32, device=self.device)
+        d_carry = self.new_carry()
+        self.index(d_buf, d_idx, d_carry, length=length)
+        carry = self.fetch(d_carry)
+        if carry.code != 0:
+            return int(carry.code)
+        n = int(carry.count)
+        d_type, d_depth, _, d_match, d_end, d_flags = self.stage2_prep(d_buf, length, d_idx, n, match=True)
+        _, d_num = self.number_values(d_buf, length, d_idx, n, d_flags, capacity=0, sync=False)
+        return self.validate(d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_num, max_depth)
+
     def set_wait_ticks(self, ticks):
         """Test hook: bound of the single-pass kernel's inter-workgroup waits in 10 ns ticks (default 2 s)."""
         self.lib.msj_debug_set_wait_ticks(self.ctx, int(ticks))
