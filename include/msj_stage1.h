@@ -720,6 +720,66 @@ int32_t msj_validate_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, co
 uint64_t msj_validate_workspace_bytes(uint64_t n, uint64_t len);
 
 /*
+ * ---- the document: tape and string buffer (DERIVED) --------------------------------------------
+ * msj_tape_device -- what the reference's stage 2 exists to produce: Document.tape (uint64 words) and Document.string_buf,
+ * as TapeBuilder (generic/stage2/tape_builder.mojo) builds them and dump_raw_tape / DocumentEntryIterator
+ * (include/dom/document.mojo) read them, for ONE document in ONE uint32 segment.  The reference cannot run here, so this
+ * text is the definition.  Inputs are exactly what msj_stage2_prep_device(..., d_match != NULL, ...), started at depth 0,
+ * and msj_number_values_device (capacity >= n_numbers) wrote for the same d_idx.
+ * The tape is SPECIFIED ONLY for a document whose msj_validate_device code is 0 with flags == 0.  On any other token arrays
+ * the call stays inside the capacities it was given and returns; the contents are then unspecified (no index derived from
+ * d_match or d_end is used unchecked).
+ *   words     w(i) per token: 1 for { } [ ], for a string (key or value) and for t f n; 2 for a token with MSJ_SPAN_NUMBER;
+ *             0 for : , and any other byte
+ *   positions pos(i) = 1 + the sum of w(j) over j < i; E = pos(n); the tape has E + 1 words (< 2^32 because n < 2^31)
+ *   root      tape[0] = 'r' << 56 | (E + 1), tape[E] = 'r' << 56 (visit_document_start / _end, tape_builder.mojo:62-66,94-105)
+ *   opening bracket i with partner j = d_match[i]: type << 56 | count << 32 | (pos(j) + 1); count = min(elements, 0xFFFFFF),
+ *             elements = 0 if j == i + 1 (empty_container :227-233: start_index + 2), else 1 + the number of k in (i, j) with
+ *             d_type[k] == ',' and d_depth[k] == d_depth[i] + 1 (what increment_count keeps, :245-272; read back at
+ *             document.mojo:194-202)
+ *   closing bracket j with partner i: type << 56 | pos(i)
+ *   string    '"' << 56 | soff(i), soff(i) = the sum over string tokens k < i of 4 + ulen(k): the record in the string buffer
+ *             is a 4-byte little-endian length, then the bytes, NO NUL terminator (on_string_start / on_string_end :274-301)
+ *   number    the next record of d_numbers in token order: 'l' << 56 then the int64 bits, or 'd' << 56 then the binary64 bit
+ *             pattern.  'u' (UINT64) is never produced: a value above 2^63 - 1 is ERR_RANGE in the number call
+ *   atoms     't', 'f' or 'n' << 56
+ *   ulen(k)   without MSJ_SPAN_ESCAPED d_end[k] - d_idx[k] - 1.  With it the body is walked: a byte outside an escape counts 1
+ *             and is copied unchanged; \" \\ \/ \b \f \n \r \t give 1 byte; \uXXXX gives the UTF-8 of its code point (1, 2 or
+ *             3 bytes); a high surrogate followed at once by a \u low surrogate gives the pair's 4 bytes (parse_string,
+ *             string_parsing.mojo:334-386, handle_unicode_codepoint :267-327).  string_bytes = the sum of 4 + ulen
+ * Deviations from the reference: (1) the END word of a non-empty container is written: end_container (:245-272) says "Write
+ * the ending tape element" and has no append for it, but its own dump_raw_tape and upstream simdjson expect the word, and
+ * without it empty_container and end_container disagree about the layout.  (2) A double is stored as its bit pattern:
+ * append_double does a numeric cast under a "TODO: is this type cast correct?", the reader bitcasts (document.mojo:251).
+ * (3) A count above 0xFFFFFF saturates in the word; the reference's CAPACITY for it is msj_validate_device's to report.
+ * (4) The number grammar and the root {} / [] are as in msj_validate_device.
+ * d_verdict (optional): the device msj_validate_result of the document.  When its code is not 0 the kernels read that on the
+ * device and write only d_result, with that code and zero sizes: index -> prep -> numbers -> validate -> tape needs no host
+ * round trip.  d_string_buf may be NULL: the tape and string_bytes are still exact (the layout-only form).  Capacities are
+ * never written past; on overflow (tape, string buffer, or fewer number records than number tokens) code = MSJ_CAPACITY and
+ * the true sizes are reported.  Arguments as msj_validate_device: NULL (other than d_verdict, d_string_buf, and d_numbers
+ * with numbers_capacity == 0) or off-grid pointers (d_idx, d_depth, d_match, d_end, d_numbers, d_tape 16-byte; d_type, d_flags,
+ * d_numbers_result, d_verdict, d_result 8-byte; d_string_buf any) are MSJ_ERR_BAD_ARGUMENT, len > MSJ_MAX_SEGMENT_BYTES or
+ * n >= 2^31 MSJ_CAPACITY, n == 0 MSJ_ERR_BAD_ARGUMENT; nothing is launched on an error.  d_numbers_result (optional) is
+ * accepted for symmetry with the chain; the number tokens are counted from d_flags.  Asynchronous on `stream`, workspace in
+ * the context.
+ */
+typedef struct msj_tape_result {
+    int32_t code;          /* 0; MSJ_CAPACITY if tape / string buffer / d_numbers is too small; d_verdict's code if that is not 0 */
+    uint32_t flags;        /* 0 */
+    uint64_t tape_words;   /* E + 1, also when clipped */
+    uint64_t string_bytes; /* also when clipped, and when d_string_buf == NULL */
+    uint64_t n_strings;
+} msj_tape_result;
+int32_t msj_tape_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
+                        const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
+                        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+                        const msj_validate_result *d_verdict, uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf,
+                        uint64_t string_capacity, msj_tape_result *d_result, void *stream);
+/* Device workspace of one msj_tape_device call over n tokens of a len-byte segment (the context keeps it). */
+uint64_t msj_tape_workspace_bytes(uint64_t n, uint64_t len);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

@@ -72,6 +72,13 @@ class MsjValidateResult(ctypes.Structure):
 VALIDATE_NUMBERS_UNCHECKED, VALIDATE_COUNTS_CLIPPED, VALIDATE_BIG_CONTAINERS = 1, 2, 64
 
 
+class MsjTapeResult(ctypes.Structure):
+    """``msj_tape_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("tape_words", ctypes.c_uint64),
+                ("string_bytes", ctypes.c_uint64), ("n_strings", ctypes.c_uint64)]
+
+
 class MsjSegment(ctypes.Structure):
     _fields_ = [
         ("byte_base", ctypes.c_uint64),
@@ -85,6 +92,7 @@ assert ctypes.sizeof(MsjCarry) == 64
 assert ctypes.sizeof(MsjSegment) == 32
 assert ctypes.sizeof(MsjNumber) == 16 and ctypes.sizeof(MsjNumbersResult) == 32
 assert ctypes.sizeof(MsjValidateResult) == 32
+assert ctypes.sizeof(MsjTapeResult) == 32
 
 _lib = None
 
@@ -193,6 +201,12 @@ def load():
         [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_validate_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_validate_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    lib.msj_tape_device.restype = ctypes.c_int32
+    lib.msj_tape_device.argtypes = [ctypes.c_void_p, u8p, ctypes.c_uint64, u32p, ctypes.c_uint64] + [ctypes.c_void_p] * 6 + \
+        [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_tape_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_tape_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

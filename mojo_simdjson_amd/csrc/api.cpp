@@ -104,6 +104,8 @@ struct msj_ctx {
     uint64_t num_ws_bytes = 0;
     void *val_ws = nullptr;       // msj_validate_device: the call's state, the lists of long and huge escaped strings
     uint64_t val_ws_bytes = 0;
+    void *tape_ws = nullptr;      // msj_tape_device: pos[], element counts, block sums, the table of long strings
+    uint64_t tape_ws_bytes = 0;
 };
 
 namespace {
@@ -717,6 +719,7 @@ void msj_ctx_destroy(msj_ctx *ctx) {
     if (ctx->doc_ws) (void)hipFree(ctx->doc_ws);
     if (ctx->num_ws) (void)hipFree(ctx->num_ws);
     if (ctx->val_ws) (void)hipFree(ctx->val_ws);
+    if (ctx->tape_ws) (void)hipFree(ctx->tape_ws);
     if (ctx->carries) (void)hipFree(ctx->carries);
     if (ctx->d_in) (void)hipFree(ctx->d_in);
     if (ctx->d_idx) (void)hipFree(ctx->d_idx);
@@ -1109,6 +1112,46 @@ int32_t msj_validate_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, co
     }
     return msj_launch_validate(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, max_depth, d_result, ctx->val_ws,
                                stream) == 0
+               ? MSJ_SUCCESS
+               : MSJ_ERR_HIP;
+}
+
+extern "C" int msj_launch_tape(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
+                               const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
+                               const msj_number *d_numbers, uint64_t numbers_capacity, const msj_validate_result *d_verdict,
+                               uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf, uint64_t string_capacity,
+                               msj_tape_result *d_result, void *d_ws, void *stream);
+
+int32_t msj_tape_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
+                        const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
+                        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+                        const msj_validate_result *d_verdict, uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf,
+                        uint64_t string_capacity, msj_tape_result *d_result, void *stream) {
+    if (!ctx || !d_result || !d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags) return MSJ_ERR_BAD_ARGUMENT;
+    if ((tape_capacity > 0 && !d_tape) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
+    if (n == 0) return MSJ_ERR_BAD_ARGUMENT;
+    if (len > MSJ_MAX_SEGMENT_BYTES || n >= (1ull << 31)) return MSJ_CAPACITY;
+    if ((reinterpret_cast<uintptr_t>(d_idx) & 15u) || (reinterpret_cast<uintptr_t>(d_depth) & 15u) ||
+        (reinterpret_cast<uintptr_t>(d_match) & 15u) || (reinterpret_cast<uintptr_t>(d_end) & 15u) ||
+        (reinterpret_cast<uintptr_t>(d_numbers) & 15u) || (reinterpret_cast<uintptr_t>(d_tape) & 15u) ||
+        (reinterpret_cast<uintptr_t>(d_type) & 7u) || (reinterpret_cast<uintptr_t>(d_flags) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_numbers_result) & 7u) || (reinterpret_cast<uintptr_t>(d_verdict) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_result) & 7u))
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (!hip_ok(hipSetDevice(ctx->device))) return MSJ_ERR_HIP;
+    const uint64_t need = msj_tape_workspace_bytes(n, len);
+    if (need > ctx->tape_ws_bytes) {
+        if (ctx->tape_ws) {
+            (void)hipDeviceSynchronize();
+            (void)hipFree(ctx->tape_ws);
+        }
+        ctx->tape_ws = nullptr;
+        ctx->tape_ws_bytes = 0;
+        if (!hip_ok(hipMalloc(&ctx->tape_ws, need + need / 4))) return MSJ_MEMALLOC;
+        ctx->tape_ws_bytes = need + need / 4;
+    }
+    return msj_launch_tape(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, numbers_capacity, d_verdict, d_tape,
+                           tape_capacity, d_string_buf, string_capacity, d_result, ctx->tape_ws, stream) == 0
                ? MSJ_SUCCESS
                : MSJ_ERR_HIP;
 }

@@ -301,6 +301,73 @@ class Stage1Device:
         _, d_num = self.number_values(d_buf, length, d_idx, n, d_flags, capacity=0, sync=False)
         return self.validate(d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_num, max_depth)
 
+    def tape(self, d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, numbers_capacity, d_verdict=None,
+             d_tape=None, tape_capacity=None, d_string_buf=None, string_capacity=None, strings=True, d_result=None, sync=True):
+        """The document's tape and string buffer (``msj_tape_device``).  The arrays are what ``stage2_prep(match=True)`` and
+        ``number_values`` wrote for the same d_idx; d_verdict: the device ``msj_validate_result`` (``validate(..., sync=False)``),
+        read on the device -- a code other than 0 ends the call with that code.  d_tape: int64 tensor (default: one of
+        ``tape_capacity`` words, default n + numbers_capacity + 2, always enough); d_string_buf: uint8 tensor (default: one of
+        ``string_capacity`` bytes, default the reference's bound 5 * length // 3 + 64); strings=False: the layout-only form
+        (d_string_buf NULL).  Returns (``MsjTapeResult``, d_tape, d_string_buf) -- blocking for the 32-byte result; with
+        sync=False the device tensor that holds it, nothing waited for."""
+        n, length, numbers_capacity = int(n), int(length), int(numbers_capacity)
+        if d_tape is None:
+            tape_capacity = n + numbers_capacity + 2 if tape_capacity is None else int(tape_capacity)
+            d_tape = torch.empty(max(tape_capacity, 2), dtype=torch.int64, device=self.device)
+        elif tape_capacity is None:
+            tape_capacity = d_tape.numel()
+        if not strings:
+            d_string_buf, string_capacity = None, 0
+        elif d_string_buf is None:
+            string_capacity = 5 * length // 3 + 64 if string_capacity is None else int(string_capacity)
+            d_string_buf = torch.empty(max(string_capacity, 1), dtype=torch.uint8, device=self.device)
+        elif string_capacity is None:
+            string_capacity = d_string_buf.numel()
+        if d_result is None:
+            d_result = torch.zeros(32, dtype=torch.uint8, device=self.device)
+        rc = self.lib.msj_tape_device(self.ctx, _ptr(d_buf), length, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match),
+                                      _ptr(d_end), _ptr(d_flags), _ptr(d_numbers) if d_numbers is not None else None,
+                                      numbers_capacity, None, _ptr(d_verdict) if d_verdict is not None else None, _ptr(d_tape),
+                                      int(tape_capacity), _ptr(d_string_buf) if d_string_buf is not None else None,
+                                      int(string_capacity), _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_tape_device failed: {rc}")
+        if not sync:
+            return d_result, d_tape, d_string_buf
+        return _lib.MsjTapeResult.from_buffer_copy(d_result.cpu().numpy().tobytes()), d_tape, d_string_buf
+
+    def parse_document(self, d_buf, length, max_depth=100, exact_strings=False):
+        """The whole chain for one document in a device buffer: stage 1, ``stage2_prep`` with partners, ``number_values``,
+        ``validate`` and ``tape`` enqueued on one stream.  Returns stage 1's code if that is not 0, else
+        (``MsjValidateResult``, ``MsjTapeResult``, d_tape, d_string_buf); the tape is specified when both codes are 0 (wrap
+        it with ``mojo_simdjson_amd.document.Document.from_device``).  The token count and the number count size the later
+        launches: they are the values read in between.  The string buffer has the reference's bound, 5 * length // 3 + 64
+        bytes; exact_strings=True sizes it from a layout-only first call instead."""
+        length = int(length)
+        d_idx = torch.empty(length + 3 + 4, dtype=torch.int32, device=self.device)
+        d_carry = self.new_carry()
+        self.index(d_buf, d_idx, d_carry, length=length)
+        carry = self.fetch(d_carry)
+        if carry.code != 0:
+            return int(carry.code)
+        n = int(carry.count)
+        d_type, d_depth, _, d_match, d_end, d_flags = self.stage2_prep(d_buf, length, d_idx, n, match=True)
+        # (a layout pass of the number call: how many records the document needs)
+        _, num = self.number_values(d_buf, length, d_idx, n, d_flags, capacity=0)
+        cap = int(num.n_numbers)
+        d_numbers, d_num = self.number_values(d_buf, length, d_idx, n, d_flags, capacity=cap, sync=False)
+        d_verdict = self.validate(d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_num, max_depth, sync=False)
+        args = (d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, cap)
+        string_capacity = None
+        if exact_strings:
+            layout, d_tape, _ = self.tape(*args, d_verdict=d_verdict, strings=False)
+            string_capacity = int(layout.string_bytes)
+            tres, d_tape, d_sbuf = self.tape(*args, d_verdict=d_verdict, d_tape=d_tape, string_capacity=string_capacity)
+        else:
+            tres, d_tape, d_sbuf = self.tape(*args, d_verdict=d_verdict)
+        verdict = _lib.MsjValidateResult.from_buffer_copy(d_verdict.cpu().numpy().tobytes())
+        return verdict, tres, d_tape, d_sbuf
+
     def set_wait_ticks(self, ticks):
         """Test hook: bound of the single-pass kernel's inter-workgroup waits in 10 ns ticks (default 2 s)."""
         self.lib.msj_debug_set_wait_ticks(self.ctx, int(ticks))
