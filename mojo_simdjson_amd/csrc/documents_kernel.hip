@@ -27,8 +27,11 @@
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
+#include "launch.h"
+#include "wave_ops.h"
 
 namespace msj_docs {
+using namespace msj::wave;
 
 constexpr int kThreads = 256;
 constexpr int kPer = 8;                       // tokens per thread
@@ -73,17 +76,6 @@ __device__ __forceinline__ void classify8(const uint8_t *__restrict__ type, cons
     }
 }
 
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-
 // (1) per block of 2 048 tokens: number of starts, last start + 1, last depth-0 closing bracket + 1
 __global__ __launch_bounds__(kThreads) void doc_count(const uint8_t *__restrict__ type, const int32_t *__restrict__ depth, uint64_t n,
                                                       uint4 *__restrict__ block_agg) {
@@ -119,7 +111,6 @@ constexpr uint32_t kSuper = 1024;  // blocks per run: 256 threads x 4
 __global__ __launch_bounds__(256) void doc_scan_super(const uint4 *__restrict__ block_agg, uint32_t nblocks, uint32_t *__restrict__ rel_off,
                                                       uint4 *__restrict__ super_agg) {
     __shared__ uint32_t w_cnt[4], w_start[4], w_close[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t first = blockIdx.x * kSuper + threadIdx.x * 4u;
     uint32_t own[4], c = 0, ls = 0, lc = 0;
 #pragma unroll
@@ -133,12 +124,10 @@ __global__ __launch_bounds__(256) void doc_scan_super(const uint4 *__restrict__ 
         }
         c += own[k];
     }
+    const int lane = threadIdx.x & 63;
     uint32_t inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t p = (uint32_t)__shfl_up((int)inc, o);
-        if (lane >= o) inc += p;
-    }
+    inc = wave_scan32(inc, lane);
+    const int wave = threadIdx.x >> 6;
     ls = wave_max(ls);
     lc = wave_max(lc);
     if (lane == 63) w_cnt[wave] = inc;
@@ -148,7 +137,7 @@ __global__ __launch_bounds__(256) void doc_scan_super(const uint4 *__restrict__ 
     }
     __syncthreads();
     uint32_t run = inc - c;
-    for (int w = 0; w < wave; w++) run += w_cnt[w];
+    run = add_waves_before(run, w_cnt, wave);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         if (first + k < nblocks) rel_off[first + k] = run;
@@ -176,13 +165,10 @@ __global__ __launch_bounds__(1024) void doc_scan(const uint4 *__restrict__ block
         lc = max(lc, q.z);
     }
     // inclusive scan of c over the 1 024 threads: within the wave, then across the 16 waves
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     uint32_t inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t p = (uint32_t)__shfl_up((int)inc, o);
-        if (lane >= o) inc += p;
-    }
+    inc = wave_scan32(inc, lane);
+    const int wave = threadIdx.x >> 6;
     ls = wave_max(ls);
     lc = wave_max(lc);
     if (lane == 63) s_cnt[wave] = inc;
@@ -192,7 +178,7 @@ __global__ __launch_bounds__(1024) void doc_scan(const uint4 *__restrict__ block
     }
     __syncthreads();
     uint32_t before = 0;
-    for (int w = 0; w < wave; w++) before += s_cnt[w];
+    before = add_waves_before(before, s_cnt, wave);
     uint32_t run = before + inc - c;
     for (uint32_t b = b0; b < b1; b++) {
         block_off[b] = run;
@@ -245,17 +231,14 @@ __global__ __launch_bounds__(kThreads) void doc_write(const uint8_t *__restrict_
     uint32_t starts, closes;
     classify8(type, depth, n, base, starts, closes);
     const uint32_t c = __popc(starts);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     uint32_t inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t p = (uint32_t)__shfl_up((int)inc, o);
-        if (lane >= o) inc += p;
-    }
+    inc = wave_scan32(inc, lane);
+    const int wave = threadIdx.x >> 6;
     if (lane == 63) w_cnt[wave] = inc;
     __syncthreads();
     uint64_t slot = super_off[blockIdx.x / kSuper] + block_off[blockIdx.x] + inc - c;
-    for (int w = 0; w < wave; w++) slot += w_cnt[w];
+    slot = add_waves_before(slot, w_cnt, wave);
     while (starts) {
         const uint32_t k = __ffs(starts) - 1u;
         starts &= starts - 1u;

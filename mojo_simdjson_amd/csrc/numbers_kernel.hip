@@ -20,11 +20,14 @@
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
+#include "launch.h"
 #include "number_math.h"
+#include "wave_ops.h"
 
 namespace msj_nums {
 
 using namespace msj::num;
+using namespace msj::wave;
 
 constexpr int kThreads = 256;
 constexpr int kPer = 16;                      // flags per thread
@@ -112,12 +115,6 @@ struct WindowRuns {
     __device__ __forceinline__ bool any_nonzero(uint64_t b, uint64_t e) const { return first_nonzero(b, e) < e; }
 };
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(kThreads) void num_count(const uint8_t *__restrict__ flags, uint64_t n, uint32_t *__restrict__ block_cnt) {
     __shared__ uint32_t w_cnt[kThreads / 64];
     const uint64_t base = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) * kPer;
@@ -134,17 +131,14 @@ __global__ __launch_bounds__(kScanThreads) void num_scan(const uint32_t *__restr
     const uint32_t b0 = threadIdx.x * per, b1 = min(nb, b0 + per);
     uint32_t c = 0;
     for (uint32_t b = b0; b < b1; b++) c += block_cnt[b];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     uint32_t inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t p = (uint32_t)__shfl_up((int)inc, o);
-        if (lane >= o) inc += p;
-    }
+    inc = wave_scan32(inc, lane);
+    const int wave = threadIdx.x >> 6;
     if (lane == 63) s_cnt[wave] = inc;
     __syncthreads();
     uint32_t run = inc - c;
-    for (int w = 0; w < wave; w++) run += s_cnt[w];
+    run = add_waves_before(run, s_cnt, wave);
     for (uint32_t b = b0; b < b1; b++) {
         block_off[b] = run;
         run += block_cnt[b];
@@ -193,13 +187,10 @@ __global__ __launch_bounds__(kThreads) void num_convert(const uint8_t *__restric
     const uint64_t base = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) * kPer;
     uint32_t m = number_mask(flags, n, base);
     const uint32_t c = __popc(m);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     uint32_t inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t p = (uint32_t)__shfl_up((int)inc, o);
-        if (lane >= o) inc += p;
-    }
+    inc = wave_scan32(inc, lane);
+    const int wave = threadIdx.x >> 6;
     if (lane == 63) w_cnt[wave] = inc;
     __syncthreads();
     uint32_t pos = inc - c, total = 0;

@@ -1,0 +1,287 @@
+// stage2_api.cpp -- extern "C" entry points of everything that runs behind stage 1 (include/msj_stage1.h): tokens, spans,
+// the fused prep, segments, documents, number values, the verdict and the tape.  Every call is the same few steps: check
+// the arguments (the order of the checks is part of the ABI: callers see which error wins), select the device, grow the
+// call's workspace, launch.
+#include "ctx.h"
+
+namespace {
+
+constexpr uint64_t kMaxTokens = 1ull << 31;  // token numbers are uint32 with the top bit spare
+bool too_big(uint64_t len, uint64_t n) { return len > MSJ_MAX_SEGMENT_BYTES || n >= kMaxTokens; }
+template <class... P>
+bool all_aligned(uintptr_t a, P... p) { return (aligned(p, a) && ...); }  // (null pointers are aligned)
+
+// behind the argument checks of a device call: its device selected, its workspace at least `need` bytes
+int32_t begin_call(msj_ctx *ctx, DeviceBuffer &ws, uint64_t need) {
+    if (!hip_ok(hipSetDevice(ctx->device))) return MSJ_ERR_HIP;
+    return ws.reserve(need, true) ? MSJ_SUCCESS : MSJ_MEMALLOC;
+}
+int32_t launched(int hip_error) { return hip_error == 0 ? MSJ_SUCCESS : MSJ_ERR_HIP; }
+
+// the span kernel's fix-up list: allocated once, zeroed once
+bool ensure_span_fix(msj_ctx *ctx) {
+    if (ctx->span_fix.p) return true;
+    if (!ctx->span_fix.reserve(msj_span_fix_bytes(), false)) return false;
+    if (!hip_ok(hipMemset(ctx->span_fix.p, 0, msj_span_fix_bytes()))) {
+        ctx->span_fix.release();
+        return false;
+    }
+    return true;
+}
+
+// The token calls (spans = false: msj_launch_tokens; d_end / d_flags unused) and the fused prep calls (spans = true:
+// msj_launch_stage2_prep).  match_bias / d_resid: msj_stage2_prep_segments (partners as positions in the shard's arrays,
+// the call's unpaired brackets kept).  tok_doc_n says whose document aggregates the workspace holds: none while a launch
+// may have failed half-way.
+int32_t chain_impl(msj_ctx *ctx, bool spans, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, uint8_t *d_type,
+                   int32_t *d_depth, uint32_t *d_match, uint32_t *d_end, uint8_t *d_flags, msj_tokens_result *d_result,
+                   const msj_tokens_result *d_prev, void *stream, uint32_t match_bias, uint32_t *d_resid, msj_bracket_pair *d_pairs) {
+    if (!ctx || !d_result || d_prev == d_result) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth || (spans && (!d_end || !d_flags)))) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    if (!all_aligned(16, d_idx, d_depth, d_match) || !aligned(d_type, 8)) return MSJ_ERR_BAD_ARGUMENT;  // match[] leaves as 16-byte stores
+    // (the workspace includes the fused kernel's chunk aggregates and group table)
+    const int32_t rc = begin_call(ctx, ctx->tok_ws, msj_stage2_prep_workspace_bytes(n, len, d_pairs ? 2 : (d_match != nullptr ? 1 : 0)));
+    if (rc != MSJ_SUCCESS) return rc;
+    ctx->tok_doc_n = ~0ull;
+    if (spans && !ensure_span_fix(ctx)) return MSJ_MEMALLOC;
+    msj_token_opts o = ctx->tok_opts;
+    o.d_prev = d_prev;
+    o.match_bias = match_bias;
+    o.d_resid = d_match ? d_resid : nullptr;
+    o.d_pairs = d_pairs;
+    int32_t *ws = ctx->tok_ws.as<int32_t>();
+    const int e = spans ? msj_launch_stage2_prep(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_result, ws,
+                                                 ctx->span_fix.as<uint32_t>(), stream, o)
+                        : msj_launch_tokens(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_result, ws, stream, o);
+    if (e != 0) return MSJ_ERR_HIP;
+    ctx->tok_doc_n = n;
+    return MSJ_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t msj_stage1_types_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, uint32_t *d_idx, uint64_t idx_capacity,
+                                uint8_t *d_types, msj_carry *d_result, void *stream, uint32_t flags) {
+    if (!ctx || !d_result || !d_types || !aligned(d_types, 4)) return MSJ_ERR_BAD_ARGUMENT;
+    if (len == 0) return MSJ_EMPTY;
+    if (len > ctx->seg_bytes || (flags & MSJ_FLAG_TWO_PASS)) return MSJ_CAPACITY;  // one single-pass launch (prototype)
+    ctx->types_out = d_types;
+    const int32_t rc = enqueue_shard(ctx, d_buf, len, d_idx, idx_capacity, &ctx->carries[0], d_result, nullptr, 0, nullptr, false, true, false,
+                                     len, static_cast<hipStream_t>(stream), flags);
+    ctx->types_out = nullptr;
+    ctx->last.valid = false;  // (no two-pass fallback for this form: a poisoned launch stays poisoned)
+    return rc;
+}
+
+int32_t msj_depth_from_types_device(msj_ctx *ctx, const uint8_t *d_type, uint64_t n, int32_t *d_depth, uint32_t *d_match,
+                                    msj_tokens_result *d_result, const msj_tokens_result *d_prev, void *stream) {
+    if (!ctx || !d_result || d_prev == d_result) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_type || !d_depth)) return MSJ_ERR_BAD_ARGUMENT;
+    if (n >= kMaxTokens) return MSJ_CAPACITY;
+    if (!all_aligned(16, d_depth, d_match) || !aligned(d_type, 8)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->tok_ws, msj_stage2_prep_workspace_bytes(n, 0, d_match != nullptr));
+    if (rc != MSJ_SUCCESS) return rc;
+    ctx->tok_doc_n = ~0ull;
+    msj_token_opts o = ctx->tok_opts;
+    o.d_prev = d_prev;
+    if (msj_launch_depth_from_types(d_type, n, d_depth, d_match, d_result, ctx->tok_ws.as<int32_t>(), stream, o) != 0) return MSJ_ERR_HIP;
+    ctx->tok_doc_n = n;
+    return MSJ_SUCCESS;
+}
+
+int32_t msj_tokens_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                          uint8_t *d_type, int32_t *d_depth, uint32_t *d_match, msj_tokens_result *d_result,
+                          void *stream) {
+    return msj_tokens_chain_device(ctx, d_buf, len, d_idx, n, d_type, d_depth, d_match, d_result, nullptr, stream);
+}
+
+int32_t msj_tokens_chain_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                                uint8_t *d_type, int32_t *d_depth, uint32_t *d_match, msj_tokens_result *d_result,
+                                const msj_tokens_result *d_prev, void *stream) {
+    return chain_impl(ctx, false, d_buf, len, d_idx, n, d_type, d_depth, d_match, nullptr, nullptr, d_result, d_prev, stream, 0u, nullptr, nullptr);
+}
+
+int32_t msj_tokens_pairs_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, uint8_t *d_type,
+                                int32_t *d_depth, msj_bracket_pair *d_pairs, msj_tokens_result *d_result,
+                                const msj_tokens_result *d_prev, void *stream) {
+    if (!d_pairs || !aligned(d_pairs, 8)) return MSJ_ERR_BAD_ARGUMENT;
+    return chain_impl(ctx, false, d_buf, len, d_idx, n, d_type, d_depth, nullptr, nullptr, nullptr, d_result, d_prev, stream, 0u, nullptr, d_pairs);
+}
+
+int32_t msj_token_spans_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                               uint32_t *d_end, uint8_t *d_flags, void *stream) {
+    if (!ctx) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_buf || !d_idx || !d_end || !d_flags)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    const int32_t rc = begin_call(ctx, ctx->tok_ws, msj_stage2_prep_workspace_bytes(n, len, 0));  // the group table lives there
+    if (rc != MSJ_SUCCESS) return rc;
+    if (!ensure_span_fix(ctx)) return MSJ_MEMALLOC;
+    ctx->tok_doc_n = ~0ull;
+    return launched(msj_launch_token_spans(d_buf, len, d_idx, n, d_end, d_flags, ctx->tok_ws.as<int32_t>(), ctx->span_fix.as<uint32_t>(), stream,
+                                           ctx->tok_opts));
+}
+
+int32_t msj_stage2_prep_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                               uint8_t *d_type, int32_t *d_depth, uint32_t *d_match, uint32_t *d_end, uint8_t *d_flags,
+                               msj_tokens_result *d_result, void *stream) {
+    return msj_stage2_prep_chain_device(ctx, d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_result, nullptr, stream);
+}
+
+int32_t msj_stage2_prep_pairs_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                                     uint8_t *d_type, int32_t *d_depth, msj_bracket_pair *d_pairs, uint32_t *d_end, uint8_t *d_flags,
+                                     msj_tokens_result *d_result, const msj_tokens_result *d_prev, void *stream) {
+    if (!d_pairs || !aligned(d_pairs, 8)) return MSJ_ERR_BAD_ARGUMENT;
+    return chain_impl(ctx, true, d_buf, len, d_idx, n, d_type, d_depth, nullptr, d_end, d_flags, d_result, d_prev, stream, 0u, nullptr, d_pairs);
+}
+
+int32_t msj_stage2_prep_chain_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                                     uint8_t *d_type, int32_t *d_depth, uint32_t *d_match, uint32_t *d_end, uint8_t *d_flags,
+                                     msj_tokens_result *d_result, const msj_tokens_result *d_prev, void *stream) {
+    return chain_impl(ctx, true, d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_result, d_prev, stream, 0u, nullptr, nullptr);
+}
+
+int32_t msj_stage2_prep_segments(msj_ctx *ctx, const uint8_t *d_buf, const msj_segment *segments, uint32_t n_segments,
+                                 const uint32_t *d_idx, uint8_t *d_type, int32_t *d_depth, uint32_t *d_match, uint32_t *d_end,
+                                 uint8_t *d_flags, msj_tokens_result *d_results, const msj_tokens_result *d_prev,
+                                 uint64_t *offsets_out, void *stream) {
+    if (!ctx || !segments || n_segments == 0 || !d_results || !d_buf) return MSJ_ERR_BAD_ARGUMENT;
+    if (!hip_ok(hipSetDevice(ctx->device))) return MSJ_ERR_HIP;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t begin0 = segments[0].index_begin, base0 = segments[0].byte_base;
+    // the whole table is checked before the first launch: a bad entry k must not leave segments 0 .. k-1 on the stream
+    for (uint32_t s = 0; s < n_segments; s++) {
+        const msj_segment &sg = segments[s];
+        if (sg.byte_len == 0 || too_big(sg.byte_len, sg.count)) return MSJ_CAPACITY;
+        if (s > 0) {  // segments of one shard follow each other without gaps, in bytes and in indices
+            const msj_segment &pv = segments[s - 1];
+            if (sg.byte_base != pv.byte_base + pv.byte_len || sg.index_begin != pv.index_begin + pv.count) return MSJ_ERR_BAD_ARGUMENT;
+        }
+    }
+    // bracket partners over the whole shard: match[] holds positions in the shard's output arrays (uint32), every
+    // segment leaves its unpaired brackets in a residual list of the context's, a stitch pairs them at the end
+    msj_stitch_args st_args;
+    st_args.n_segments = n_segments;
+    if (d_match) {
+        if (n_segments > MSJ_STITCH_MAX_SEGMENTS) return MSJ_CAPACITY;
+        uint64_t total = 0;
+        for (uint32_t s = 0; s < n_segments; s++) total = (((total + segments[s].count + 3u) & ~3ull) + 7u) & ~7ull;
+        if (total >= 0xFFFFFFFFull) return MSJ_CAPACITY;  // (0xFFFFFFFF is "no partner")
+        const uint64_t need = (uint64_t)n_segments * MSJ_RESID_WORDS * sizeof(uint32_t);
+        if (!ctx->resid.reserve(need, false)) return MSJ_MEMALLOC;
+        if (!hip_ok(hipMemsetAsync(ctx->resid.p, 0, need, st))) return MSJ_ERR_HIP;
+    }
+    uint64_t off = 0;
+    // the result each segment goes on from: that of the LAST segment with tokens (d_prev in front of them).  A segment
+    // without tokens carries the stream's depth, minimum and maximum on unchanged, but with n = 0 the call behind it
+    // could not tell it from the start of a stream and would drop the minimum and maximum of the tokens in front.
+    const msj_tokens_result *prev = d_prev;
+    for (uint32_t s = 0; s < n_segments; s++) {
+        const msj_segment &sg = segments[s];
+        const uint64_t n = sg.count;
+        // (a segment without tokens -- inside a long string -- reads no index: its slice may start anywhere)
+        const uint32_t *idx = n ? d_idx + (sg.index_begin - begin0) : nullptr;
+        if (n && !aligned(idx, 16)) {
+            // stage 1 writes a shard's indices densely, so a later segment's slice starts wherever the one in front
+            // ended: the token kernels read index quads, so it is copied to an aligned buffer first (4 bytes per token
+            // each way, on the stream; the first segment of a shard never needs it)
+            if (!ctx->seg_idx.reserve((n + 4) * sizeof(uint32_t), false)) return MSJ_MEMALLOC;
+            if (!hip_ok(hipMemcpyAsync(ctx->seg_idx.p, idx, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st))) return MSJ_ERR_HIP;
+            idx = ctx->seg_idx.as<uint32_t>();
+        }
+        if (offsets_out) offsets_out[s] = off;
+        uint32_t *resid = d_match ? ctx->resid.as<uint32_t>() + (uint64_t)s * MSJ_RESID_WORDS : nullptr;
+        if (d_match) {
+            st_args.offsets[s] = (uint32_t)off;
+            st_args.resid[s] = resid;
+        }
+        const int32_t rc = chain_impl(ctx, true, d_buf + (sg.byte_base - base0), sg.byte_len, idx, n, d_type ? d_type + off : nullptr,
+                                      d_depth ? d_depth + off : nullptr, d_match ? d_match + off : nullptr, d_end ? d_end + off : nullptr,
+                                      d_flags ? d_flags + off : nullptr, &d_results[s], prev, stream, (uint32_t)off, resid, nullptr);
+        if (rc != MSJ_SUCCESS) return rc;
+        if (n) prev = &d_results[s];
+        off += (n + 3u) & ~3ull;  // every segment's slices start 16-byte aligned (8 for the byte arrays: n rounded to 4 ... 8 below)
+        off = (off + 7u) & ~7ull;
+    }
+    if (d_match && msj_launch_stitch_partners(st_args, d_match, d_results, d_prev, stream) != 0) return MSJ_ERR_HIP;
+    return MSJ_SUCCESS;
+}
+
+int32_t msj_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, int32_t is_final, const uint32_t *d_idx,
+                             uint64_t n, const uint8_t *d_type, const int32_t *d_depth, const msj_carry *d_carry,
+                             uint32_t *d_doc_first, uint64_t capacity, msj_documents_result *d_result, void *stream) {
+    if (!ctx || !d_result) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth)) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && !d_doc_first) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    if (!aligned(d_depth, 16) || !aligned(d_type, 8)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->doc_ws, msj_documents_workspace_bytes(n));
+    if (rc != MSJ_SUCCESS) return rc;
+    // MSJ_DOCS_AFTER_TOKENS: the block aggregates the token pre-pass left in its workspace are for these arrays
+    const void *pre = ((is_final & MSJ_DOCS_AFTER_TOKENS) && ctx->tok_ws.p && ctx->tok_doc_n == n && n > 0)
+                          ? msj_tokens_doc_aggregates(ctx->tok_ws.as<int32_t>(), n)
+                          : nullptr;
+    return launched(msj_launch_documents(d_buf, len, is_final & MSJ_DOCS_FINAL, d_idx, n, d_type, d_depth, d_carry, d_doc_first, capacity, d_result,
+                                         ctx->doc_ws.p, pre, stream));
+}
+
+int32_t msj_number_values_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                                 const uint8_t *d_flags, msj_number *d_numbers, uint64_t capacity,
+                                 msj_numbers_result *d_result, void *stream) {
+    if (!ctx || !d_result) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_buf || !d_idx || !d_flags)) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && !d_numbers) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    if (!all_aligned(16, d_idx, d_numbers) || !all_aligned(8, d_flags, d_result)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->num_ws, msj_number_values_workspace_bytes(n, len));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_number_values(d_buf, len, d_idx, n, d_flags, d_numbers, capacity, d_result, ctx->num_ws.p, stream));
+}
+
+int32_t msj_validate_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                            const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
+                            const uint32_t *d_end, const uint8_t *d_flags, const msj_numbers_result *d_numbers,
+                            uint32_t max_depth, msj_validate_result *d_result, void *stream) {
+    if (!ctx || !d_result || !d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags) return MSJ_ERR_BAD_ARGUMENT;
+    if (n == 0 || max_depth == 0) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    if (!all_aligned(16, d_idx, d_depth, d_match, d_end) || !all_aligned(8, d_type, d_flags, d_numbers, d_result)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->val_ws, msj_validate_workspace_bytes(n, len));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_validate(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, max_depth, d_result,
+                                        ctx->val_ws.p, stream));
+}
+
+int32_t msj_tape_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
+                        const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
+                        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+                        const msj_validate_result *d_verdict, uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf,
+                        uint64_t string_capacity, msj_tape_result *d_result, void *stream) {
+    if (!ctx || !d_result || !d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags) return MSJ_ERR_BAD_ARGUMENT;
+    if ((tape_capacity > 0 && !d_tape) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
+    if (n == 0) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers, d_tape) ||
+        !all_aligned(8, d_type, d_flags, d_numbers_result, d_verdict, d_result))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->tape_ws, msj_tape_workspace_bytes(n, len));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_tape(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, numbers_capacity, d_verdict, d_tape,
+                                    tape_capacity, d_string_buf, string_capacity, d_result, ctx->tape_ws.p, stream));
+}
+
+int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {
+    if (!ctx) return MSJ_ERR_BAD_ARGUMENT;
+    ctx->tok_opts.lds_limit = lds_limit_bytes;
+    ctx->tok_opts.fix_cap = fix_capacity;
+    return MSJ_SUCCESS;
+}
+int32_t msj_debug_set_span_mode(msj_ctx *ctx, uint32_t mode) {
+    if (!ctx || mode > 2u) return MSJ_ERR_BAD_ARGUMENT;
+    ctx->tok_opts.span_mode = mode;
+    return MSJ_SUCCESS;
+}
+
+}  // extern "C"

@@ -30,11 +30,14 @@
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
+#include "launch.h"
 #include "tape_math.h"
+#include "wave_ops.h"
 
 namespace msj_tape {
 
 using namespace msj::tape;
+using namespace msj::wave;
 using msj::val::ByteReader;
 
 constexpr int kThreads = 256;
@@ -67,34 +70,6 @@ struct Work {  // the workspace, carved by layout()
 __host__ __device__ inline uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 __host__ __device__ inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
-__device__ __forceinline__ uint32_t load_byte_quad(const uint8_t *__restrict__ a, uint64_t j, uint64_t n) {  // j % 4 == 0
-    if (j + 4 <= n) return *reinterpret_cast<const uint32_t *>(a + j);
-    uint32_t w = 0;
-    for (int k = 0; k < 4 && j + k < n; k++) w |= (uint32_t)a[j + k] << (8 * k);
-    return w;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
-    return v;
-}
-// inclusive sum over the wave
-template <class T>
-__device__ __forceinline__ T wave_scan(T v) {
-    const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T u = (T)__shfl_up((unsigned long long)v, o);
-        if (lane >= (uint32_t)o) v += u;
-    }
-    return v;
-}
 // exclusive sum over the workgroup (s_w: kWaves words of LDS, free again after the call); total receives the sum
 template <class T>
 __device__ __forceinline__ T block_scan(T v, T *s_w, T &total) {

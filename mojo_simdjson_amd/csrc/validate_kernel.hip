@@ -24,11 +24,14 @@
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
+#include "launch.h"
 #include "validate_math.h"
+#include "wave_ops.h"
 
 namespace msj_val {
 
 using namespace msj::val;
+using namespace msj::wave;
 
 constexpr int kThreads = 256;
 constexpr int kPer = 4;                        // tokens per lane
@@ -46,20 +49,6 @@ struct State {
     uint32_t big_count, long_count, huge_count, reserved;
     uint32_t big_open[kBig], big_close[kBig], big_commas[kBig];
 };
-
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
 
 __global__ void val_init(State *__restrict__ st) {
     st->err = kNoError;
@@ -91,7 +80,7 @@ struct BlockTokens {
 };
 
 __device__ __forceinline__ uint32_t load_type_word(const uint8_t *__restrict__ type, int64_t j, int64_t n) {  // j % 4 == 0
-    if (j < 0 || j >= n) return 0;
+    if (j < 0 || j >= n) return 0;  // (signed and guarded: not wave_ops.h's load_byte_quad, which compiles to other compares here)
     if (j + 4 <= n) return *reinterpret_cast<const uint32_t *>(type + j);
     uint32_t w = 0;
     for (int k = 0; k < 4 && j + k < n; k++) w |= (uint32_t)type[j + k] << (8 * k);

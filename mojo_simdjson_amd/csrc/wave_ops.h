@@ -1,0 +1,61 @@
+// wave_ops.h -- reductions and scans over one wave64 and the padded four-byte load that documents_kernel.hip,
+// numbers_kernel.hip, validate_kernel.hip and tape_kernel.hip share.  Device code only.  (tokens_kernel.hip has its own
+// DPP scans.)  The device code of the four files is pinned instruction for instruction: see the notes on the forms below.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace msj::wave {
+
+// op over the wave (xor butterfly): every lane gets the result
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, (T)__shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return a + b; }); }
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) { return wave_reduce((unsigned long long)v, [](uint64_t a, uint64_t b) { return a + b; }); }
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return max(a, b); }); }
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) { return wave_reduce(v, [](auto a, auto b) { return b < a ? b : a; }); }
+
+// Inclusive sum over the wave, two forms because they compile to different instructions.  wave_scan32 shuffles the 32-bit
+// value as it is (documents_kernel.hip, numbers_kernel.hip); wave_scan<T> shuffles every T as 64 bits, a 32-bit one included
+// (tape_kernel.hip).  maybe_undef: a plain by-value parameter is `noundef`, which lets the compiler drop the freeze of the
+// caller's value and changes the instructions of the kernels these loops were written out in.
+__device__ __forceinline__ uint32_t wave_scan32(__attribute__((maybe_undef)) uint32_t v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t p = (uint32_t)__shfl_up((int)v, o);
+        if (lane >= o) v += p;
+    }
+    return v;
+}
+template <class T>
+__device__ __forceinline__ T wave_scan(T v) {
+    const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = (T)__shfl_up((unsigned long long)v, o);
+        if (lane >= (uint32_t)o) v += u;
+    }
+    return v;
+}
+
+// wave totals through LDS: lane 63 of every wave has left its inclusive sum in s_w[wave] and the workgroup has met at a
+// barrier; adds what the waves in front of `wave` hold to sum
+template <class A, class T, int N>
+__device__ __forceinline__ A add_waves_before(__attribute__((maybe_undef)) A sum, const T (&s_w)[N], int wave) {
+    for (int w = 0; w < wave; w++) sum += s_w[w];
+    return sum;
+}
+
+// bytes a[j .. j + 4) as one word, j a multiple of 4; bytes from n on read as 0
+__device__ __forceinline__ uint32_t load_byte_quad(const uint8_t *__restrict__ a, uint64_t j, uint64_t n) {
+    if (j + 4 <= n) return *reinterpret_cast<const uint32_t *>(a + j);
+    uint32_t w = 0;
+    for (int k = 0; k < 4 && j + k < n; k++) w |= (uint32_t)a[j + k] << (8 * k);
+    return w;
+}
+
+}  // namespace msj::wave

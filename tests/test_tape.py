@@ -421,6 +421,59 @@ def test_bad_arguments_launch_nothing(dev):
     assert res[:4].view(np.int32)[0] == MSJ_CAPACITY and res[8:16].view(np.uint64)[0] == 7  # r [ l 1 "a" ] r
 
 
+def test_workspaces_grow_and_are_reused(oracle):
+    """One context of its own through small, large, small, large: every workspace of the chain is allocated, outgrown and
+    re-allocated, then reused twice (DeviceBuffer::reserve, csrc/ctx.h).  Each of the four results -- verdict, tape result,
+    tape words, string bytes -- equals what a fresh context gives for the same document.  The large document is sized so
+    that each workspace of the chain needs more than 1.25 times (the head-room factor) what the small one left."""
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from mojo_simdjson_amd import _lib
+    from mojo_simdjson_amd.device import Stage1Device
+
+    # numbers, escaped strings and nesting in both; the large one is the small one's elements about 4 MiB long
+    element = b'{"k":[1,-2.5e3,"' + _body(40, b"\\u20ac") + b'",{"x":[true,null,"a\\nb\\\\"]}],"z":[[],{}],"' + _body(30, b"\\tq") + b'":1e-7}'
+    small = b"[" + element + b"," + element + b"," + PLANTS[1][1](8) + b"]"
+    large = b"[" + (element + b",") * ((4 << 20) // (len(element) + 1)) + PLANTS[0][1](BLOCK + 5) + b"]"
+    assert 200 <= len(small) <= 1000 and len(large) >= (4 << 20) - 1024
+
+    lib = _lib.load()
+    prep = lib.msj_stage2_prep_workspace_bytes
+    prep.restype, prep.argtypes = ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
+    sizes = {}
+    for name, data in (("small", small), ("large", large)):
+        code, n, _ = helpers.run_oracle(oracle.msj_oracle_stage1, data)
+        assert code == 0
+        sizes[name] = (prep(n, len(data), 1), lib.msj_number_values_workspace_bytes(n, len(data)),
+                       lib.msj_validate_workspace_bytes(n, len(data)), lib.msj_tape_workspace_bytes(n, len(data)))
+    for s_bytes, l_bytes in zip(sizes["small"], sizes["large"]):
+        assert 4 * l_bytes > 5 * s_bytes, (sizes["small"], sizes["large"])  # large > 1.25 x small: really re-allocated
+
+    def run(d, data):
+        got = device_document(d, data)
+        assert not isinstance(got, int), got
+        verdict, tres, d_tape, d_sbuf = got
+        assert (verdict.code, tres.code) == (0, 0) and tres.tape_words > 2 and tres.string_bytes > 0
+        return (bytes(verdict), bytes(tres), d_tape[:int(tres.tape_words)].cpu().numpy().tobytes(),
+                d_sbuf[:int(tres.string_bytes)].cpu().numpy().tobytes())
+
+    want = {}
+    for name, data in (("small", small), ("large", large)):
+        fresh = Stage1Device(0)
+        want[name] = run(fresh, data)
+        fresh.close()
+    own = Stage1Device(0)
+    try:
+        for step, (name, data) in enumerate((("small", small), ("large", large), ("small", small), ("large", large))):
+            got = run(own, data)
+            for part, g, w in zip(("verdict", "tape result", "tape", "string buffer"), got, want[name]):
+                assert g == w, (step, name, part)
+    finally:
+        own.close()
+
+
 @pytest.mark.parametrize("workload", ["minified", "utf8", "pretty4"])
 def test_workloads_1mib(dev, oracle, tm, nm, workload):
     from mojo_simdjson_amd import synth
