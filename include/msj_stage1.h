@@ -780,6 +780,68 @@ int32_t msj_tape_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const 
 uint64_t msj_tape_workspace_bytes(uint64_t n, uint64_t len);
 
 /*
+ * ---- stage 2's verdict for every document of a window (DERIVED) --------------------------------
+ * msj_validate_documents_device -- msj_validate_device's verdict for EVERY complete document of a window that
+ * msj_documents_device has split, in one pass over the window's token arrays: no launch per document and no host round
+ * trip.  Read on the device: D = d_docs->n_complete and T = d_docs->tokens_complete (the device msj_documents_result of the
+ * split over the same arrays; d_doc_first holds at least D entries).  Document k covers the tokens [f_k, e_k), f_k =
+ * d_doc_first[k], e_k = d_doc_first[k + 1], e_(D-1) = T.  d_verdicts[k] is what the definition of msj_validate_device gives for
+ * the token sub-arrays [f_k, e_k) -- d_type, d_depth, d_match, d_end, d_flags from f_k on, e_k - f_k tokens -- with
+ *   buffer     the same d_buf / len and the same d_idx values: content checks look at the window's bytes, not at a slice of
+ *              them.  A `true` or a `12` directly followed by the next document's `"` is therefore an atom / number error,
+ *              exactly as the span and number calls already see it
+ *   partners   rebased: d_match[i] - f_k; a partner outside [f_k, e_k) counts as no partner
+ *   in front   a token in front of f_k matches nothing (it is "a token in front of token 0")
+ *   the end    token e_k is that document's end of the stream: a token that matches nothing, judged for document k
+ *   error_token is reported as an index into the WINDOW's arrays, in [f_k, e_k]
+ * Why this is exact: the per-token rule is local (three tokens in front, one hop through d_match) and the split starts a
+ * document at every depth-0 token that is not a closing bracket, so d_depth needs no rebase and the only thing to hide from
+ * a token is the other documents.  Tokens at or past T belong to the cut document: they are never judged and never read as
+ * anything but "nothing"; tokens in front of d_doc_first[0] (a window that starts below depth 0) belong to no document.
+ * d_verdicts[k] for k >= D is not written.
+ *   numbers    d_numbers_result == NULL: numbers are not checked, MSJ_VALIDATE_NUMBERS_UNCHECKED is set.  n_errors == 0 (read
+ *              on the device): nothing more is needed, d_numbers may be NULL with numbers_capacity 0 -- the usual case, no
+ *              record is ever written.  n_errors > 0 and n_numbers <= numbers_capacity: every record of an ERR kind whose
+ *              token is below T competes in its document as NUMBER_ERROR 9 (the first one of a document wins, as first_error
+ *              does in msj_validate_device).  n_errors > 0 and not every record stored: MSJ_VALIDATE_NUMBERS_UNCHECKED is set
+ *              (run the number call again with n_numbers records, then this call)
+ *   count      as msj_validate_device: up to MSJ_VALIDATE_BIG_CONTAINERS wide containers per CALL are counted exactly, a
+ *              MSJ_CAPACITY goes to the document that holds the container; more sets MSJ_VALIDATE_COUNTS_CLIPPED
+ * d_result: code 0, or MSJ_CAPACITY when D > capacity (then n_documents = D and nothing else is specified; no verdict is
+ * written); flags for the whole call; n_documents = D; n_invalid the verdicts with a code, first_invalid the smallest such k
+ * (UINT64_MAX: none); n_escaped as msj_validate_result's.  n == 0 or D == 0 writes a zero result with first_invalid =
+ * UINT64_MAX.  Arguments: alignment and limits of msj_validate_device (d_idx, d_depth, d_match, d_end, d_numbers 16-byte;
+ * d_type, d_flags, d_docs, d_numbers_result, d_verdicts, d_result 8-byte; d_doc_first 4-byte); NULL d_result / d_docs, NULL
+ * arrays with n > 0, NULL d_verdicts with capacity > 0, NULL d_numbers with numbers_capacity > 0 or max_depth == 0:
+ * MSJ_ERR_BAD_ARGUMENT; len > MSJ_MAX_SEGMENT_BYTES or n >= 2^31: MSJ_CAPACITY; nothing is launched on either.  Asynchronous on
+ * `stream`, no host round trip on any path, workspace in the context.  Safe on ANY arrays stage 1 + prep + split can produce
+ * from arbitrary bytes: no index from d_match or d_doc_first is used unchecked, D and T are clipped to n, and a window whose
+ * depth goes negative stays in bounds (its later tokens fall into one document, judged by the same rule).
+ */
+typedef struct msj_document_verdict {   /* 16 bytes, one per complete document */
+    int32_t  code;         /* reference code 0, 1, 3..9 -- as msj_validate_result.code */
+    uint32_t reserved;     /* 0 */
+    uint64_t error_token;  /* index into the WINDOW's token arrays, in [first_k, end_k]; UINT64_MAX when code == 0 */
+} msj_document_verdict;
+typedef struct msj_validate_documents_result {  /* 48 bytes */
+    int32_t  code;          /* 0, or MSJ_CAPACITY: more complete documents than `capacity`, nothing else specified */
+    uint32_t flags;         /* MSJ_VALIDATE_NUMBERS_UNCHECKED / MSJ_VALIDATE_COUNTS_CLIPPED, meaning as today, for the whole call */
+    uint64_t n_documents;   /* verdicts written = d_docs->n_complete */
+    uint64_t n_invalid;     /* verdicts with code != 0 */
+    uint64_t first_invalid; /* smallest such document index, UINT64_MAX if none */
+    uint64_t n_escaped;     /* diagnostic, as today */
+    uint64_t reserved;
+} msj_validate_documents_result;
+int32_t msj_validate_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+        const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
+        const uint32_t *d_doc_first, const msj_documents_result *d_docs,
+        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+        uint32_t max_depth, msj_document_verdict *d_verdicts, uint64_t capacity,
+        msj_validate_documents_result *d_result, void *stream);
+/* Device workspace of one msj_validate_documents_device call (the context keeps it; the documents' error words live in d_verdicts). */
+uint64_t msj_validate_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

@@ -72,6 +72,20 @@ class MsjValidateResult(ctypes.Structure):
 VALIDATE_NUMBERS_UNCHECKED, VALIDATE_COUNTS_CLIPPED, VALIDATE_BIG_CONTAINERS = 1, 2, 64
 
 
+class MsjDocumentVerdict(ctypes.Structure):
+    """``msj_document_verdict`` (include/msj_stage1.h): one per complete document of a window."""
+
+    _fields_ = [("code", ctypes.c_int32), ("reserved", ctypes.c_uint32), ("error_token", ctypes.c_uint64)]
+
+
+class MsjValidateDocumentsResult(ctypes.Structure):
+    """``msj_validate_documents_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_documents", ctypes.c_uint64),
+                ("n_invalid", ctypes.c_uint64), ("first_invalid", ctypes.c_uint64), ("n_escaped", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64)]
+
+
 class MsjTapeResult(ctypes.Structure):
     """``msj_tape_result`` (include/msj_stage1.h)."""
 
@@ -93,6 +107,7 @@ assert ctypes.sizeof(MsjSegment) == 32
 assert ctypes.sizeof(MsjNumber) == 16 and ctypes.sizeof(MsjNumbersResult) == 32
 assert ctypes.sizeof(MsjValidateResult) == 32
 assert ctypes.sizeof(MsjTapeResult) == 32
+assert ctypes.sizeof(MsjDocumentVerdict) == 16 and ctypes.sizeof(MsjValidateDocumentsResult) == 48
 
 _lib = None
 
@@ -201,6 +216,11 @@ def load():
         [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_validate_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_validate_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    lib.msj_validate_documents_device.restype = ctypes.c_int32
+    lib.msj_validate_documents_device.argtypes = [ctypes.c_void_p, u8p, ctypes.c_uint64, u32p, ctypes.c_uint64] + [ctypes.c_void_p] * 8 + \
+        [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_validate_documents_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_validate_documents_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]
     lib.msj_tape_device.restype = ctypes.c_int32
     lib.msj_tape_device.argtypes = [ctypes.c_void_p, u8p, ctypes.c_uint64, u32p, ctypes.c_uint64] + [ctypes.c_void_p] * 6 + \
         [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,

@@ -105,6 +105,7 @@ struct msj_ctx {
     DeviceBuffer doc_ws;          // block counts of the document split
     DeviceBuffer num_ws;          // msj_number_values_device: block counts / offsets, the fallback and long-number lists
     DeviceBuffer val_ws;          // msj_validate_device: the call's state, the lists of long and huge escaped strings
+    DeviceBuffer vdoc_ws;         // msj_validate_documents_device: the same for a window (the documents' error words live in d_verdicts)
     DeviceBuffer tape_ws;         // msj_tape_device: pos[], element counts, block sums, the table of long strings
 };
 

@@ -1,5 +1,5 @@
 // stage2_api.cpp -- extern "C" entry points of everything that runs behind stage 1 (include/msj_stage1.h): tokens, spans,
-// the fused prep, segments, documents, number values, the verdict and the tape.  Every call is the same few steps: check
+// the fused prep, segments, documents, number values, the verdict (one document, or every document of a window) and the tape.  Every call is the same few steps: check
 // the arguments (the order of the checks is part of the ABI: callers see which error wins), select the device, grow the
 // call's workspace, launch.
 #include "ctx.h"
@@ -252,6 +252,26 @@ int32_t msj_validate_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, co
     if (rc != MSJ_SUCCESS) return rc;
     return launched(msj_launch_validate(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, max_depth, d_result,
                                         ctx->val_ws.p, stream));
+}
+
+int32_t msj_validate_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                                      const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end,
+                                      const uint8_t *d_flags, const uint32_t *d_doc_first, const msj_documents_result *d_docs,
+                                      const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+                                      uint32_t max_depth, msj_document_verdict *d_verdicts, uint64_t capacity,
+                                      msj_validate_documents_result *d_result, void *stream) {
+    if (!ctx || !d_result || !d_docs || max_depth == 0) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((capacity > 0 && !d_verdicts) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers) || !all_aligned(8, d_type, d_flags, d_docs, d_numbers_result, d_verdicts, d_result) ||
+        !aligned(d_doc_first, 4))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->vdoc_ws, msj_validate_documents_workspace_bytes(n, len, capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_validate_documents(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_numbers,
+                                                  numbers_capacity, d_numbers_result, max_depth, d_verdicts, capacity, d_result, ctx->vdoc_ws.p,
+                                                  stream));
 }
 
 int32_t msj_tape_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,

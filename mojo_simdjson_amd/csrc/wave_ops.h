@@ -1,6 +1,7 @@
 // wave_ops.h -- reductions and scans over one wave64 and the padded four-byte load that documents_kernel.hip,
-// numbers_kernel.hip, validate_kernel.hip and tape_kernel.hip share.  Device code only.  (tokens_kernel.hip has its own
-// DPP scans.)  The device code of the four files is pinned instruction for instruction: see the notes on the forms below.
+// numbers_kernel.hip, validate_kernel.hip, validate_docs_kernel.hip and tape_kernel.hip share.  Device code only.
+// (tokens_kernel.hip has its own DPP scans.)  The device code of the four older files is pinned instruction for
+// instruction: see the notes on the forms below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,6 +39,28 @@ __device__ __forceinline__ T wave_scan(T v) {
     for (int o = 1; o < 64; o <<= 1) {
         const T u = (T)__shfl_up((unsigned long long)v, o);
         if (lane >= (uint32_t)o) v += u;
+    }
+    return v;
+}
+
+// Running maximum over the wave (lane l: the maximum of lanes 0 .. l) and running minimum from the other end (lane l: the
+// minimum of lanes l .. 63): validate_docs_kernel.hip finds every token's document with them -- the last start at or in
+// front of a token, the first start behind it.
+__device__ __forceinline__ uint32_t wave_scan_max(uint32_t v) {
+    const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t p = (uint32_t)__shfl_up((int)v, o);
+        if (lane >= (uint32_t)o) v = max(v, p);
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_rscan_min(uint32_t v) {
+    const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t p = (uint32_t)__shfl_down((int)v, o);
+        if (lane + (uint32_t)o < 64u) v = min(v, p);
     }
     return v;
 }

@@ -174,25 +174,31 @@ class Stage1Device:
             raise RuntimeError(f"msj_token_spans_device failed: {rc}")
         return d_end[:n], d_flags[:n]
 
-    def stage2_prep(self, d_buf, length, d_idx, n, match=False, d_prev=None, d_result=None):
+    def stage2_prep(self, d_buf, length, d_idx, n, match=False, d_prev=None, d_result=None, arrays=None, sync=True):
         """``tokens`` and ``token_spans`` in one go (``msj_stage2_prep_device``), identical results:
         returns (d_type, d_depth, msj_tokens_result, d_match or None, d_end, d_flags).  d_prev: the device
         msj_tokens_result of the call for the tokens in front (``msj_stage2_prep_chain_device``); d_result: where
-        this call's goes (to hand on as the next call's d_prev)."""
+        this call's goes (to hand on as the next call's d_prev).  arrays: (d_type, d_depth, d_match or None, d_end,
+        d_flags) of the caller's to write into, at least n long; sync=False: nothing is waited for, the third element is
+        the device tensor that holds the result."""
         n = int(n)
         dv = self.device
-        d_type = torch.empty(max(n, 1), dtype=torch.uint8, device=dv)
-        d_depth = torch.empty(max(n, 1), dtype=torch.int32, device=dv)
-        d_match = torch.empty(max(n, 1), dtype=torch.int32, device=dv) if match else None
-        d_end = torch.empty(max(n, 1), dtype=torch.int32, device=dv)
-        d_flags = torch.empty(max(n, 1), dtype=torch.uint8, device=dv)
+        if arrays is not None:
+            d_type, d_depth, d_match, d_end, d_flags = arrays
+            match = d_match is not None
+        else:
+            d_type = torch.empty(max(n, 1), dtype=torch.uint8, device=dv)
+            d_depth = torch.empty(max(n, 1), dtype=torch.int32, device=dv)
+            d_match = torch.empty(max(n, 1), dtype=torch.int32, device=dv) if match else None
+            d_end = torch.empty(max(n, 1), dtype=torch.int32, device=dv)
+            d_flags = torch.empty(max(n, 1), dtype=torch.uint8, device=dv)
         d_res = d_result if d_result is not None else torch.zeros(24, dtype=torch.uint8, device=dv)
         rc = self.lib.msj_stage2_prep_chain_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth),
                                                    _ptr(d_match) if match else None, _ptr(d_end), _ptr(d_flags), _ptr(d_res),
                                                    _ptr(d_prev) if d_prev is not None else None, self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_stage2_prep_device failed: {rc}")
-        res = _lib.MsjTokensResult.from_buffer_copy(d_res.cpu().numpy().tobytes())
+        res = _lib.MsjTokensResult.from_buffer_copy(d_res.cpu().numpy().tobytes()) if sync else d_res
         return d_type[:n], d_depth[:n], res, (d_match[:n] if match else None), d_end[:n], d_flags[:n]
 
     def stage2_prep_segments(self, d_buf, segments, d_idx, match=False, d_prev=None):
@@ -284,6 +290,37 @@ class Stage1Device:
         if not sync:
             return d_result
         return _lib.MsjValidateResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
+
+    def validate_documents(self, d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs,
+                           d_numbers=None, numbers_capacity=0, d_numbers_result=None, max_depth=100, d_verdicts=None, capacity=None,
+                           d_result=None, sync=True):
+        """A verdict for every complete document of a window (``msj_validate_documents_device``): what ``validate`` gives
+        for each document's token sub-arrays, in one pass over the window.  The arrays are what ``stage2_prep(match=True)``
+        wrote for the window's d_idx; d_doc_first / d_docs: the device arrays of ``documents(..., sync=False)`` over them (how
+        many documents there are is read on the device); d_numbers / d_numbers_result: from ``number_values(..., sync=False)``
+        -- no record is needed unless that call found an error (capacity 0 will do; MSJ_VALIDATE_NUMBERS_UNCHECKED in the
+        result's flags says that the records are wanted).  d_verdicts: int64 tensor of shape (capacity, 2) -- [k, 0] the code
+        in its low 32 bits, [k, 1] the error token, -1 for none -- default one row per token.  Returns (d_verdicts,
+        ``MsjValidateDocumentsResult``) -- blocking for the 48-byte result; with sync=False (d_verdicts, d_result) with
+        nothing waited for."""
+        n = int(n)
+        if d_verdicts is None:
+            capacity = n if capacity is None else int(capacity)
+            d_verdicts = torch.empty((max(capacity, 1), 2), dtype=torch.int64, device=self.device)
+        elif capacity is None:
+            capacity = d_verdicts.shape[0]
+        if d_result is None:
+            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        rc = self.lib.msj_validate_documents_device(
+            self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
+            _ptr(d_doc_first), _ptr(d_docs), _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, int(numbers_capacity),
+            _ptr(d_numbers_result) if d_numbers_result is not None else None, int(max_depth), _ptr(d_verdicts), int(capacity),
+            _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_validate_documents_device failed: {rc}")
+        if not sync:
+            return d_verdicts, d_result
+        return d_verdicts, _lib.MsjValidateDocumentsResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
 
     def validate_document(self, d_buf, length, max_depth=100):
         """Is this device buffer one valid JSON document, and if not, which error and where: stage 1, ``stage2_prep`` with

@@ -45,6 +45,14 @@ class Window:
     d_type: torch.Tensor       # uint8[n_tokens]
     d_depth: torch.Tensor      # int32[n_tokens]
     d_doc_first: torch.Tensor  # int32[n_documents]: token index of each document's first token
+    # DocumentStream(validate=True) only: the rest of stage2_prep's arrays and a verdict per document
+    d_match: torch.Tensor = None     # int32[n_tokens]: bracket partners (0xFFFFFFFF: none)
+    d_end: torch.Tensor = None       # int32[n_tokens]: end offsets of strings and numbers, relative to base
+    d_flags: torch.Tensor = None     # uint8[n_tokens]: MSJ_SPAN_*
+    d_verdicts: torch.Tensor = None  # int64[n_documents, 2]: msj_document_verdict -- [k, 0] & 0xFFFFFFFF the code, [k, 1] the error token (-1: none)
+    n_invalid: int = None            # documents with a code
+    first_invalid: int = None        # the first of them in this window, None if there is none
+    verdict_flags: int = None        # MSJ_VALIDATE_* of the window's verdict call
 
     def document_offsets(self):
         """Absolute byte offset of every complete document (host list; reads the device arrays)."""
@@ -60,9 +68,17 @@ class DocumentStream:
     window: bytes indexed per step (a document must fit in one window, like upstream's batch_size);
     index_capacity: structurals a window may hold (default: one per byte up to 64 MiB windows, one per
     two bytes beyond).  The arrays a Window carries are reused by the next one.
+
+    validate=True: every window also carries stage 2's verdict for each of its documents
+    (``msj_validate_documents_device``, max_depth as there) -- the token pre-pass becomes ``stage2_prep`` with partners, the
+    number call and the verdict call follow the split on the same stream, and the small results still come back in one
+    read.  Only a window in which the number call found a bad number is visited twice: the number call again with room
+    for its records, then the verdict call.  An invalid document is no error of the stream: it is reported in the
+    Window.  The window-level errors below stay what they are.
     """
 
-    def __init__(self, dev, d_buf, length=None, window=1 << 28, flags=0, index_capacity=None, reuse_counts=True):
+    def __init__(self, dev, d_buf, length=None, window=1 << 28, flags=0, index_capacity=None, reuse_counts=True, validate=False,
+                 max_depth=100):
         self.dev = dev
         self.d_buf = d_buf
         self.length = int(d_buf.numel() if length is None else length)
@@ -84,7 +100,17 @@ class DocumentStream:
         self._first = torch.empty(self.capacity, dtype=torch.int32, device=dvc)
         self._zero = dev.new_carry()
         self._carry = dev.new_carry()
-        self._results = torch.zeros(64, dtype=torch.uint8, device=dvc)  # msj_tokens_result | msj_documents_result
+        self.validate = bool(validate)
+        self.max_depth = int(max_depth)
+        # msj_tokens_result | msj_documents_result (validate: | msj_numbers_result | msj_validate_documents_result)
+        self._results = torch.zeros(144 if self.validate else 64, dtype=torch.uint8, device=dvc)
+        if self.validate:
+            self._match = torch.empty(self.capacity, dtype=torch.int32, device=dvc)
+            self._end = torch.empty(self.capacity, dtype=torch.int32, device=dvc)
+            self._flags = torch.empty(self.capacity, dtype=torch.uint8, device=dvc)
+            # a verdict per document; documents are a few tokens at the least, and a window with more of them than this
+            # (the call says so) grows the array and asks again
+            self._verdicts = torch.empty((self.capacity // 8 + 1024, 2), dtype=torch.int64, device=dvc)
         self.windows = 0
 
     def __iter__(self):
@@ -104,10 +130,18 @@ class DocumentStream:
                 raise DocumentStreamError(errors.CAPACITY, f"window at {base}: more than {self.capacity} structurals")
             n = int(carry.count)
             # the two small result structs of the token pre-pass and the split come back in one read
-            d_type, d_depth, _ = dev.tokens(d_win, wlen, self._idx, n, d_type=self._type, d_depth=self._depth,
-                                            d_result=self._results[:24], sync=False)
+            if self.validate:
+                d_type, d_depth, _, d_match, d_end, d_flags = dev.stage2_prep(
+                    d_win, wlen, self._idx, n, d_result=self._results[:24], sync=False,
+                    arrays=(self._type, self._depth, self._match, self._end, self._flags))
+            else:
+                d_type, d_depth, _ = dev.tokens(d_win, wlen, self._idx, n, d_type=self._type, d_depth=self._depth,
+                                                d_result=self._results[:24], sync=False)
             d_first, _ = dev.documents(d_win, wlen, self._idx, n, d_type, d_depth, is_final=last, d_carry=self._carry,
                                        d_doc_first=self._first, d_result=self._results[32:64], sync=False, after_tokens=self.reuse_counts)
+            if self.validate:  # ... and with them those of the number call and the verdict call
+                dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=0, d_result=self._results[64:96], sync=False)
+                self._verdict_call(d_win, wlen, n, None, 0)
             blob = self._results.cpu().numpy().tobytes()
             tok = _lib.MsjTokensResult.from_buffer_copy(blob[:24])
             res = _lib.MsjDocumentsResult.from_buffer_copy(blob[32:64])
@@ -124,7 +158,34 @@ class DocumentStream:
             self.windows += 1
             nt, nd = int(res.tokens_complete), int(res.n_complete)
             consumed = int(res.resume_offset) if cut else wlen
+            extra = {}
+            if self.validate:
+                vres = _lib.MsjValidateDocumentsResult.from_buffer_copy(blob[96:144])
+                if vres.code == errors.CAPACITY:  # more documents than verdicts: room for all of them, and once more
+                    self._verdicts = torch.empty((nd, 2), dtype=torch.int64, device=dev.device)
+                    vres = self._verdict_call(d_win, wlen, n, None, 0, read=True)
+                if vres.flags & _lib.VALIDATE_NUMBERS_UNCHECKED:
+                    # the rare window with a bad number: its records, then the verdicts again
+                    cap = _lib.MsjNumbersResult.from_buffer_copy(blob[64:96]).n_numbers
+                    d_numbers, _ = dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=cap, d_result=self._results[64:96],
+                                                     sync=False)
+                    vres = self._verdict_call(d_win, wlen, n, d_numbers, cap, read=True)
+                extra = dict(d_match=d_match[:nt], d_end=d_end[:nt], d_flags=d_flags[:nt], d_verdicts=self._verdicts[:nd],
+                             n_invalid=int(vres.n_invalid), verdict_flags=int(vres.flags),
+                             first_invalid=int(vres.first_invalid) if vres.n_invalid else None)
             yield Window(base=base, length=wlen, consumed=consumed, n_tokens=nt, n_documents=nd,
                          utf8_error=bool(carry.utf8_error), d_idx=self._idx[:nt], d_type=d_type[:nt],
-                         d_depth=d_depth[:nt], d_doc_first=d_first[:nd])
+                         d_depth=d_depth[:nt], d_doc_first=d_first[:nd], **extra)
             pos = base + consumed
+
+    def _verdict_call(self, d_win, wlen, n, d_numbers, numbers_capacity, read=False):
+        """``validate_documents`` over the stream's arrays, on the results of the split and the number call where they lie
+        on the device; read: wait for its result and return it."""
+        r = self._results
+        self.dev.validate_documents(d_win, wlen, self._idx, n, self._type, self._depth, self._match, self._end, self._flags,
+                                    self._first, r[32:64], d_numbers=d_numbers, numbers_capacity=numbers_capacity,
+                                    d_numbers_result=r[64:96], max_depth=self.max_depth, d_verdicts=self._verdicts, d_result=r[96:144],
+                                    sync=False)
+        if read:
+            return _lib.MsjValidateDocumentsResult.from_buffer_copy(r[96:144].cpu().numpy().tobytes())
+        return None
