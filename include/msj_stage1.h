@@ -842,6 +842,78 @@ int32_t msj_validate_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64
 uint64_t msj_validate_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity);
 
 /*
+ * ---- a tape for every document of a window (DERIVED) -------------------------------------------
+ * msj_tape_documents_device -- msj_tape_device's tape and string buffer for EVERY complete document of a window that
+ * msj_documents_device has split, in one pass over the window's tokens: no launch per document and no host round trip.
+ * Inputs as for msj_validate_documents_device: the window's d_buf / len, and d_idx, d_type, d_depth, d_match, d_end, d_flags
+ * from msj_stage2_prep_device(..., d_match != NULL, ...) started at depth 0; d_doc_first and the device
+ * msj_documents_result of the split; d_numbers / numbers_capacity / d_numbers_result from msj_number_values_device over the
+ * WHOLE window's tokens; optionally d_verdicts, the msj_document_verdict array of msj_validate_documents_device (D entries;
+ * none is read when D > capacity).  D = d_docs->n_complete and T = d_docs->tokens_complete are read on the device and clipped to n.  Document k
+ * covers the tokens [f_k, e_k), f_k = d_doc_first[k], e_k = d_doc_first[k + 1], e_(D-1) = T.
+ * Document k's tape and string buffer are exactly what the definition of msj_tape_device gives for the token sub-arrays
+ * [f_k, e_k), with these four conventions:
+ *   buffer     the same d_buf / len and the same d_idx / d_end values are used, as in the verdict call
+ *   partners   rebased (d_match[i] - f_k); a partner outside [f_k, e_k) is no partner
+ *   numbers    the records are those whose token lies in [f_k, e_k), in order
+ *   local      positions in bracket words, tape[0]'s word count and string offsets are LOCAL to the document
+ * Each document's slice is therefore a self-contained Document(tape, string_buf).  It is specified for a document whose
+ * verdict is 0, as for the single call.  d_depth needs no rebase, because f_k sits at depth 0.
+ * Layout in the window's output arrays, in closed form.  Let W(i), S(i), N(i) be the sums over window tokens j < i of the
+ * words per token (W), of 4 + ulen at strings (S) and of the number tokens (N).  Then
+ *   document k's tape starts at word tape_first[k] = W(f_k) - W(f_0) + 2k of d_tape and has W(e_k) - W(f_k) + 2 words
+ *   its string records start at byte string_first[k] = S(f_k) - S(f_0) of d_string_buf
+ *   token i of document k writes at word W(i) - W(f_0) + 2k + 1; a string's word holds S(i) - S(f_k)
+ *   a number takes record N(i), the global rank in the window, not rebased
+ *   the end root word of document k - 1 and the first root word of document k are adjacent, at tape_first[k] - 1 and
+ *   tape_first[k]
+ * Word addresses are 64-bit: W(T) + 2D can pass 2^32 although every local position stays below it.  No scan over documents
+ * is needed.  The price is that a document with a verdict code still occupies its slot: its record reports the verdict's
+ * code with tape_words = string_bytes = 0, and the contents of its slot are unspecified but stay inside it and inside the
+ * capacities.  Tokens in front of f_0 and at or past T write nothing and are read only as "nothing".
+ * Results: one 32-byte msj_document_tape per complete document in d_doc_tapes, and one 64-byte msj_tape_documents_result:
+ * code 0, or MSJ_CAPACITY when the tape, the string buffer, the records (D > capacity: nothing else is written then) or the
+ * number records (fewer than the number tokens below T: n_numbers > numbers_capacity) do not fit; tape_words and
+ * string_bytes are the window's true totals, also when clipped, n_numbers the records the call reads.  Capacities are never
+ * written past.  d_string_buf == NULL is the layout-only form, as in msj_tape_device.  d_verdicts == NULL builds every
+ * document (unspecified where one is invalid, still in bounds).  n == 0 or D == 0 writes a zero result.
+ * Arguments, alignments and limits follow msj_validate_documents_device / msj_tape_device: d_idx, d_depth, d_match, d_end,
+ * d_numbers, d_tape 16-byte; d_type, d_flags, d_docs, d_numbers_result, d_verdicts, d_doc_tapes, d_result 8-byte;
+ * d_doc_first 4-byte; d_string_buf any.  NULL d_result / d_docs, NULL arrays with n > 0, NULL d_tape / d_doc_tapes / d_numbers
+ * with a capacity > 0: MSJ_ERR_BAD_ARGUMENT; len > MSJ_MAX_SEGMENT_BYTES or n >= 2^31: MSJ_CAPACITY; nothing is launched on
+ * either.  d_numbers_result (optional) is accepted for symmetry with the chain; the number tokens are counted from d_flags.
+ * Asynchronous on `stream`, workspace in the context.  Safe on ANY arrays stage 1 + prep + split can produce from arbitrary
+ * bytes: no index from d_match, d_end or d_doc_first is used unchecked and every store is checked against its capacity.
+ */
+typedef struct msj_document_tape {   /* 32 bytes, one per complete document */
+    uint64_t tape_first;    /* word offset of the document's tape in d_tape */
+    uint64_t string_first;  /* byte offset of its records in d_string_buf */
+    uint32_t tape_words;    /* 0 when code != 0 */
+    int32_t  code;          /* 0, or d_verdicts[k].code */
+    uint64_t string_bytes;  /* 0 when code != 0 */
+} msj_document_tape;
+typedef struct msj_tape_documents_result {  /* 64 bytes */
+    int32_t  code;          /* 0, or MSJ_CAPACITY: tape / string buffer / records / number records too small */
+    uint32_t flags;         /* 0 */
+    uint64_t n_documents;   /* D */
+    uint64_t n_built;       /* records with code 0 */
+    uint64_t tape_words;    /* W(T) - W(f_0) + 2D, also when clipped */
+    uint64_t string_bytes;  /* S(T) - S(f_0), also when clipped, and when d_string_buf == NULL */
+    uint64_t n_strings;
+    uint64_t n_numbers;     /* number tokens below T = the records of d_numbers the call reads */
+    uint64_t reserved;
+} msj_tape_documents_result;
+int32_t msj_tape_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+        const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
+        const uint32_t *d_doc_first, const msj_documents_result *d_docs,
+        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+        const msj_document_verdict *d_verdicts, uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf,
+        uint64_t string_capacity, msj_document_tape *d_doc_tapes, uint64_t capacity,
+        msj_tape_documents_result *d_result, void *stream);
+/* Device workspace of one msj_tape_documents_device call (the context keeps it): msj_tape_device's plus 8 bytes per document. */
+uint64_t msj_tape_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

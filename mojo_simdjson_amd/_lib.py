@@ -93,6 +93,21 @@ class MsjTapeResult(ctypes.Structure):
                 ("string_bytes", ctypes.c_uint64), ("n_strings", ctypes.c_uint64)]
 
 
+class MsjDocumentTape(ctypes.Structure):
+    """``msj_document_tape`` (include/msj_stage1.h): one per complete document of a window."""
+
+    _fields_ = [("tape_first", ctypes.c_uint64), ("string_first", ctypes.c_uint64), ("tape_words", ctypes.c_uint32),
+                ("code", ctypes.c_int32), ("string_bytes", ctypes.c_uint64)]
+
+
+class MsjTapeDocumentsResult(ctypes.Structure):
+    """``msj_tape_documents_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_documents", ctypes.c_uint64),
+                ("n_built", ctypes.c_uint64), ("tape_words", ctypes.c_uint64), ("string_bytes", ctypes.c_uint64),
+                ("n_strings", ctypes.c_uint64), ("n_numbers", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
 class MsjSegment(ctypes.Structure):
     _fields_ = [
         ("byte_base", ctypes.c_uint64),
@@ -108,6 +123,8 @@ assert ctypes.sizeof(MsjNumber) == 16 and ctypes.sizeof(MsjNumbersResult) == 32
 assert ctypes.sizeof(MsjValidateResult) == 32
 assert ctypes.sizeof(MsjTapeResult) == 32
 assert ctypes.sizeof(MsjDocumentVerdict) == 16 and ctypes.sizeof(MsjValidateDocumentsResult) == 48
+
+assert ctypes.sizeof(MsjDocumentTape) == 32 and ctypes.sizeof(MsjTapeDocumentsResult) == 64
 
 _lib = None
 
@@ -227,6 +244,12 @@ def load():
          ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_tape_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_tape_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    lib.msj_tape_documents_device.restype = ctypes.c_int32
+    lib.msj_tape_documents_device.argtypes = [ctypes.c_void_p, u8p, ctypes.c_uint64, u32p, ctypes.c_uint64] + [ctypes.c_void_p] * 8 + \
+        [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_tape_documents_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_tape_documents_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

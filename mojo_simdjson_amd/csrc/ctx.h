@@ -107,6 +107,7 @@ struct msj_ctx {
     DeviceBuffer val_ws;          // msj_validate_device: the call's state, the lists of long and huge escaped strings
     DeviceBuffer vdoc_ws;         // msj_validate_documents_device: the same for a window (the documents' error words live in d_verdicts)
     DeviceBuffer tape_ws;         // msj_tape_device: pos[], element counts, block sums, the table of long strings
+    DeviceBuffer tdoc_ws;         // msj_tape_documents_device: the same for a window, and 8 bytes per document
 };
 
 // ---- api.cpp ----

@@ -1,5 +1,5 @@
 // stage2_api.cpp -- extern "C" entry points of everything that runs behind stage 1 (include/msj_stage1.h): tokens, spans,
-// the fused prep, segments, documents, number values, the verdict (one document, or every document of a window) and the tape.  Every call is the same few steps: check
+// the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a window).  Every call is the same few steps: check
 // the arguments (the order of the checks is part of the ABI: callers see which error wins), select the device, grow the
 // call's workspace, launch.
 #include "ctx.h"
@@ -290,6 +290,27 @@ int32_t msj_tape_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const 
     if (rc != MSJ_SUCCESS) return rc;
     return launched(msj_launch_tape(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, numbers_capacity, d_verdict, d_tape,
                                     tape_capacity, d_string_buf, string_capacity, d_result, ctx->tape_ws.p, stream));
+}
+
+int32_t msj_tape_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
+                                  const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
+                                  const uint32_t *d_doc_first, const msj_documents_result *d_docs, const msj_number *d_numbers,
+                                  uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+                                  const msj_document_verdict *d_verdicts, uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf,
+                                  uint64_t string_capacity, msj_document_tape *d_doc_tapes, uint64_t capacity,
+                                  msj_tape_documents_result *d_result, void *stream) {
+    if (!ctx || !d_result || !d_docs) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((tape_capacity > 0 && !d_tape) || (capacity > 0 && !d_doc_tapes) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers, d_tape) ||
+        !all_aligned(8, d_type, d_flags, d_docs, d_numbers_result, d_verdicts, d_doc_tapes, d_result) || !aligned(d_doc_first, 4))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->tdoc_ws, msj_tape_documents_workspace_bytes(n, len, capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_tape_documents(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_numbers,
+                                              numbers_capacity, d_verdicts, d_tape, tape_capacity, d_string_buf, string_capacity, d_doc_tapes,
+                                              capacity, d_result, ctx->tdoc_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

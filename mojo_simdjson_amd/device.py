@@ -252,16 +252,17 @@ class Stage1Device:
             return d_doc_first, d_result
         return d_doc_first, _lib.MsjDocumentsResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
 
-    def number_values(self, d_buf, length, d_idx, n, d_flags, capacity=None, d_result=None, sync=True):
+    def number_values(self, d_buf, length, d_idx, n, d_flags, capacity=None, d_result=None, sync=True, d_numbers=None):
         """Values of the number tokens (``msj_number_values_device``): one 16-byte ``msj_number`` record per token whose
         d_flags (from ``token_spans`` / ``stage2_prep*`` for the same d_idx) has MSJ_SPAN_NUMBER, in token order -- the exact
         int64 or the nearest binary64, or a syntax / range error.  capacity: records stored at most (default n).
         Returns (d_numbers, msj_numbers_result) -- d_numbers an int64 tensor of shape (capacity, 2): [k, 0] the bits,
         [k, 1] token | kind << 32 -- blocking for the 32-byte result; with sync=False (d_numbers, d_result) with nothing
-        waited for."""
+        waited for.  d_numbers: a tensor of that shape to write into instead of a new one (at least `capacity` rows)."""
         n = int(n)
         capacity = n if capacity is None else int(capacity)
-        d_numbers = torch.empty((max(capacity, 1), 2), dtype=torch.int64, device=self.device)
+        if d_numbers is None:
+            d_numbers = torch.empty((max(capacity, 1), 2), dtype=torch.int64, device=self.device)
         if d_result is None:
             d_result = torch.zeros(32, dtype=torch.uint8, device=self.device)
         rc = self.lib.msj_number_values_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), n, _ptr(d_flags), _ptr(d_numbers),
@@ -372,6 +373,51 @@ class Stage1Device:
         if not sync:
             return d_result, d_tape, d_string_buf
         return _lib.MsjTapeResult.from_buffer_copy(d_result.cpu().numpy().tobytes()), d_tape, d_string_buf
+
+    def tape_documents(self, d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_numbers,
+                       numbers_capacity, d_verdicts=None, d_tape=None, tape_capacity=None, d_string_buf=None, string_capacity=None,
+                       strings=True, d_doc_tapes=None, capacity=None, d_result=None, sync=True):
+        """A tape and a string buffer for every complete document of a window (``msj_tape_documents_device``): what ``tape``
+        gives for each document's token sub-arrays, in one pass over the window.  The arrays are what
+        ``stage2_prep(match=True)`` wrote for the window's d_idx; d_doc_first / d_docs: the device arrays of
+        ``documents(..., sync=False)``; d_numbers: the records of ``number_values`` over the whole window; d_verdicts: the
+        rows of ``validate_documents`` (None: every document is built).  d_tape: int64 tensor (default: one of
+        ``tape_capacity`` words, default 3 * n + 2, always enough); d_string_buf: uint8 tensor (default: one of
+        ``string_capacity`` bytes, default 5 * length // 3 + 4 * n + 64); strings=False: the layout-only form; d_doc_tapes:
+        int64 tensor of shape (capacity, 4), one ``msj_document_tape`` per row (default one row per token).  Returns
+        (``MsjTapeDocumentsResult``, d_tape, d_string_buf, d_doc_tapes) -- blocking for the 64-byte result; with sync=False
+        the device tensor that holds it, nothing waited for."""
+        n, length, numbers_capacity = int(n), int(length), int(numbers_capacity)
+        if d_tape is None:
+            tape_capacity = 3 * n + 2 if tape_capacity is None else int(tape_capacity)
+            d_tape = torch.empty(max(tape_capacity, 2), dtype=torch.int64, device=self.device)
+        elif tape_capacity is None:
+            tape_capacity = d_tape.numel()
+        if not strings:
+            d_string_buf, string_capacity = None, 0
+        elif d_string_buf is None:
+            string_capacity = 5 * length // 3 + 4 * n + 64 if string_capacity is None else int(string_capacity)
+            d_string_buf = torch.empty(max(string_capacity, 1), dtype=torch.uint8, device=self.device)
+        elif string_capacity is None:
+            string_capacity = d_string_buf.numel()
+        if d_doc_tapes is None:
+            capacity = n if capacity is None else int(capacity)
+            d_doc_tapes = torch.empty((max(capacity, 1), 4), dtype=torch.int64, device=self.device)
+        elif capacity is None:
+            capacity = d_doc_tapes.shape[0]
+        if d_result is None:
+            d_result = torch.zeros(64, dtype=torch.uint8, device=self.device)
+        rc = self.lib.msj_tape_documents_device(
+            self.ctx, _ptr(d_buf), length, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
+            _ptr(d_doc_first), _ptr(d_docs), _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
+            None, _ptr(d_verdicts) if d_verdicts is not None else None, _ptr(d_tape), int(tape_capacity),
+            _ptr(d_string_buf) if d_string_buf is not None else None, int(string_capacity), _ptr(d_doc_tapes), int(capacity),
+            _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_tape_documents_device failed: {rc}")
+        if not sync:
+            return d_result, d_tape, d_string_buf, d_doc_tapes
+        return _lib.MsjTapeDocumentsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()), d_tape, d_string_buf, d_doc_tapes
 
     def parse_document(self, d_buf, length, max_depth=100, exact_strings=False):
         """The whole chain for one document in a device buffer: stage 1, ``stage2_prep`` with partners, ``number_values``,

@@ -14,11 +14,16 @@ Every window starts at a document.  Stage 1 wants a 16-byte aligned base, so the
 the document's offset rounded down and the up to 15 bytes in front (the end of the previous document)
 read as blanks (``MSJ_FLAG_SKIP``).  Offsets in ``d_idx`` are relative to ``Window.base``.
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 
 from . import _lib, errors
+from .document import Document
+
+DOC_TAPE_DTYPE = np.dtype([("tape_first", "<u8"), ("string_first", "<u8"), ("tape_words", "<u4"), ("code", "<i4"),
+                           ("string_bytes", "<u8")])  # msj_document_tape
 
 MAX_WINDOW = 1 << 31
 
@@ -53,6 +58,37 @@ class Window:
     n_invalid: int = None            # documents with a code
     first_invalid: int = None        # the first of them in this window, None if there is none
     verdict_flags: int = None        # MSJ_VALIDATE_* of the window's verdict call
+    # DocumentStream(parse=True) only: every document's tape and string buffer (msj_tape_documents_device)
+    d_tape: torch.Tensor = None        # int64[tape_words]: document k's tape at [tape_first_k, + tape_words_k)
+    d_string_buf: torch.Tensor = None  # uint8[string_bytes]: its string records from string_first_k on
+    d_doc_tapes: torch.Tensor = None   # int64[n_documents, 4]: msj_document_tape per document
+    n_built: int = None                # documents with code 0: the ones that have a tape
+    _documents: list = field(default=None, repr=False, compare=False)  # what documents() built: host copies, kept
+
+    def documents(self):
+        """A ``Document`` per complete document, None for one with a verdict code (its code: ``d_doc_tapes`` / ``d_verdicts``).
+        One copy of the three arrays to the host; the list is kept.  d_tape, d_string_buf and d_doc_tapes are views of
+        arrays that the next window reuses, like every array a Window carries: call this before the iterator advances (the
+        Documents it returned stay valid, they are host copies)."""
+        if self.d_doc_tapes is None:
+            raise ValueError("no tapes: the stream was not created with parse=True")
+        if self._documents is None:
+            recs = np.ascontiguousarray(self.d_doc_tapes.cpu().numpy()).view(DOC_TAPE_DTYPE).reshape(-1)
+            tape = self.d_tape.cpu().numpy().view(np.uint64)
+            sbuf = self.d_string_buf.cpu().numpy()
+            out = []
+            for r in recs:
+                if r["code"] != 0:
+                    out.append(None)
+                    continue
+                t0, s0 = int(r["tape_first"]), int(r["string_first"])
+                out.append(Document(tape[t0:t0 + int(r["tape_words"])], sbuf[s0:s0 + int(r["string_bytes"])]))
+            self._documents = out
+        return self._documents
+
+    def document(self, k):
+        """Document k of the window (None if it has a verdict code)."""
+        return self.documents()[k]
 
     def document_offsets(self):
         """Absolute byte offset of every complete document (host list; reads the device arrays)."""
@@ -75,10 +111,17 @@ class DocumentStream:
     read.  Only a window in which the number call found a bad number is visited twice: the number call again with room
     for its records, then the verdict call.  An invalid document is no error of the stream: it is reported in the
     Window.  The window-level errors below stay what they are.
+
+    parse=True (implies validate): every window also carries its documents (``msj_tape_documents_device``):
+    ``Window.documents()`` yields a ``Document`` per valid document.  The number call runs with room for its records, the
+    tape call follows the verdict call on the same stream, and its 64-byte result comes back in the same read.  The tape,
+    the string buffer, the records and the number records start at tape_words / string_bytes / documents / numbers
+    (defaults from the index capacity) and grow to what a window needs: the call reports the true sizes, and only the
+    calls that need it run again.
     """
 
     def __init__(self, dev, d_buf, length=None, window=1 << 28, flags=0, index_capacity=None, reuse_counts=True, validate=False,
-                 max_depth=100):
+                 max_depth=100, parse=False, tape_words=None, string_bytes=None, documents=None, numbers=None):
         self.dev = dev
         self.d_buf = d_buf
         self.length = int(d_buf.numel() if length is None else length)
@@ -100,10 +143,12 @@ class DocumentStream:
         self._first = torch.empty(self.capacity, dtype=torch.int32, device=dvc)
         self._zero = dev.new_carry()
         self._carry = dev.new_carry()
-        self.validate = bool(validate)
+        self.parse = bool(parse)
+        self.validate = bool(validate) or self.parse
         self.max_depth = int(max_depth)
-        # msj_tokens_result | msj_documents_result (validate: | msj_numbers_result | msj_validate_documents_result)
-        self._results = torch.zeros(144 if self.validate else 64, dtype=torch.uint8, device=dvc)
+        # msj_tokens_result | msj_documents_result (validate: | msj_numbers_result | msj_validate_documents_result; parse:
+        # | msj_tape_documents_result)
+        self._results = torch.zeros(208 if self.parse else (144 if self.validate else 64), dtype=torch.uint8, device=dvc)
         if self.validate:
             self._match = torch.empty(self.capacity, dtype=torch.int32, device=dvc)
             self._end = torch.empty(self.capacity, dtype=torch.int32, device=dvc)
@@ -111,6 +156,12 @@ class DocumentStream:
             # a verdict per document; documents are a few tokens at the least, and a window with more of them than this
             # (the call says so) grows the array and asks again
             self._verdicts = torch.empty((self.capacity // 8 + 1024, 2), dtype=torch.int64, device=dvc)
+        if self.parse:
+            cap = self.capacity
+            self._tape = torch.empty(max(int(cap + cap // 2 + 2 if tape_words is None else tape_words), 2), dtype=torch.int64, device=dvc)
+            self._sbuf = torch.empty(max(int(w + cap // 2 + 64 if string_bytes is None else string_bytes), 16), dtype=torch.uint8, device=dvc)
+            self._doc_tapes = torch.empty((max(int(cap // 8 + 1024 if documents is None else documents), 1), 4), dtype=torch.int64, device=dvc)
+            self._numbers = torch.empty((max(int(cap // 4 + 1024 if numbers is None else numbers), 1), 2), dtype=torch.int64, device=dvc)
         self.windows = 0
 
     def __iter__(self):
@@ -140,8 +191,15 @@ class DocumentStream:
             d_first, _ = dev.documents(d_win, wlen, self._idx, n, d_type, d_depth, is_final=last, d_carry=self._carry,
                                        d_doc_first=self._first, d_result=self._results[32:64], sync=False, after_tokens=self.reuse_counts)
             if self.validate:  # ... and with them those of the number call and the verdict call
-                dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=0, d_result=self._results[64:96], sync=False)
-                self._verdict_call(d_win, wlen, n, None, 0)
+                if self.parse:  # with room for the records: the tapes read them
+                    d_numbers, ncap = self._numbers, self._numbers.shape[0]
+                    dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=ncap, d_result=self._results[64:96], sync=False,
+                                      d_numbers=d_numbers)
+                    self._verdict_call(d_win, wlen, n, d_numbers, ncap)
+                    self._tape_call(d_win, wlen, n)
+                else:
+                    dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=0, d_result=self._results[64:96], sync=False)
+                    self._verdict_call(d_win, wlen, n, None, 0)
             blob = self._results.cpu().numpy().tobytes()
             tok = _lib.MsjTokensResult.from_buffer_copy(blob[:24])
             res = _lib.MsjDocumentsResult.from_buffer_copy(blob[32:64])
@@ -161,18 +219,35 @@ class DocumentStream:
             extra = {}
             if self.validate:
                 vres = _lib.MsjValidateDocumentsResult.from_buffer_copy(blob[96:144])
+                d_numbers, ncap = (self._numbers, self._numbers.shape[0]) if self.parse else (None, 0)
+                again = False  # the tape call has to follow a verdict call that ran again
                 if vres.code == errors.CAPACITY:  # more documents than verdicts: room for all of them, and once more
                     self._verdicts = torch.empty((nd, 2), dtype=torch.int64, device=dev.device)
-                    vres = self._verdict_call(d_win, wlen, n, None, 0, read=True)
+                    vres = self._verdict_call(d_win, wlen, n, d_numbers, ncap, read=True)
+                    again = True
                 if vres.flags & _lib.VALIDATE_NUMBERS_UNCHECKED:
                     # the rare window with a bad number: its records, then the verdicts again
                     cap = _lib.MsjNumbersResult.from_buffer_copy(blob[64:96]).n_numbers
+                    if self.parse:
+                        self._numbers = torch.empty((cap, 2), dtype=torch.int64, device=dev.device)
                     d_numbers, _ = dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=cap, d_result=self._results[64:96],
-                                                     sync=False)
+                                                     sync=False, d_numbers=self._numbers if self.parse else None)
                     vres = self._verdict_call(d_win, wlen, n, d_numbers, cap, read=True)
+                    again = True
                 extra = dict(d_match=d_match[:nt], d_end=d_end[:nt], d_flags=d_flags[:nt], d_verdicts=self._verdicts[:nd],
                              n_invalid=int(vres.n_invalid), verdict_flags=int(vres.flags),
                              first_invalid=int(vres.first_invalid) if vres.n_invalid else None)
+                if self.parse:
+                    tres = _lib.MsjTapeDocumentsResult.from_buffer_copy(blob[144:208])
+                    for _ in range(3):
+                        if tres.code == 0 and not again:
+                            break
+                        tres = self._grow_and_tape(d_win, wlen, n, d_flags, tres)
+                        again = False
+                    if tres.code != 0:
+                        raise DocumentStreamError(int(tres.code), f"window at {base}: the tapes do not fit what the call asked for")
+                    extra.update(d_tape=self._tape[:int(tres.tape_words)], d_string_buf=self._sbuf[:int(tres.string_bytes)],
+                                 d_doc_tapes=self._doc_tapes[:nd], n_built=int(tres.n_built))
             yield Window(base=base, length=wlen, consumed=consumed, n_tokens=nt, n_documents=nd,
                          utf8_error=bool(carry.utf8_error), d_idx=self._idx[:nt], d_type=d_type[:nt],
                          d_depth=d_depth[:nt], d_doc_first=d_first[:nd], **extra)
@@ -189,3 +264,32 @@ class DocumentStream:
         if read:
             return _lib.MsjValidateDocumentsResult.from_buffer_copy(r[96:144].cpu().numpy().tobytes())
         return None
+
+    def _tape_call(self, d_win, wlen, n, read=False):
+        """``tape_documents`` over the stream's arrays behind the verdict call; read: wait for its result and return it."""
+        r = self._results
+        # (no more records than verdict rows: the call reads a verdict per document it builds, and builds none when there
+        # are more documents than records)
+        capacity = min(self._doc_tapes.shape[0], self._verdicts.shape[0])
+        self.dev.tape_documents(d_win, wlen, self._idx, n, self._type, self._depth, self._match, self._end, self._flags, self._first,
+                                r[32:64], self._numbers, self._numbers.shape[0], d_verdicts=self._verdicts, d_tape=self._tape,
+                                d_string_buf=self._sbuf, d_doc_tapes=self._doc_tapes, capacity=capacity, d_result=r[144:208], sync=False)
+        if read:
+            return _lib.MsjTapeDocumentsResult.from_buffer_copy(r[144:208].cpu().numpy().tobytes())
+        return None
+
+    def _grow_and_tape(self, d_win, wlen, n, d_flags, tres):
+        """Room for what the last tape call reported (a quarter more, so that the next window of the kind fits), the number
+        call again if its records were too few, then the tape call once more."""
+        dvc = self.dev.device
+        if tres.tape_words > self._tape.numel():
+            self._tape = torch.empty(int(tres.tape_words) * 5 // 4 + 2, dtype=torch.int64, device=dvc)
+        if tres.string_bytes > self._sbuf.numel():
+            self._sbuf = torch.empty(int(tres.string_bytes) * 5 // 4 + 16, dtype=torch.uint8, device=dvc)
+        if tres.n_documents > self._doc_tapes.shape[0]:
+            self._doc_tapes = torch.empty((int(tres.n_documents) * 5 // 4 + 1, 4), dtype=torch.int64, device=dvc)
+        if tres.n_numbers > self._numbers.shape[0]:
+            self._numbers = torch.empty((int(tres.n_numbers) * 5 // 4 + 1, 2), dtype=torch.int64, device=dvc)
+            self.dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=self._numbers.shape[0], d_result=self._results[64:96],
+                                   sync=False, d_numbers=self._numbers)
+        return self._tape_call(d_win, wlen, n, read=True)
