@@ -914,6 +914,71 @@ int32_t msj_tape_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t l
 uint64_t msj_tape_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity);
 
 /*
+ * ---- fields by path for every document of a window (DERIVED) ------------------------------------
+ * msj_select_documents_device -- upstream simdjson's at_key / at_pointer, restricted to object keys, for up to 16 paths and
+ * EVERY complete document of a window in one call: one 16-byte msj_field per (path, document), path-major, so that each path
+ * is a contiguous column.  The reference stops in front of this (its dom/element, object and array files are empty; the
+ * three codes below sit in its errors file unused).
+ * Paths: msj_paths_create compiles n_paths RFC 6901 JSON pointers, synchronously, into device memory the object owns.  ""
+ * is the document's root value; otherwise /seg/seg..., with ~1 for '/' and ~0 for '~'.  Every segment is an OBJECT KEY,
+ * compared as bytes with the UNESCAPED key of the document; a numeric segment is a key like any other (array indices are
+ * not supported; a key that holds a NUL byte cannot be named, the pointers being C strings).  1 to 16 paths, at most 8 segments per path, each of 0 to 255 bytes (the empty key is legal JSON):
+ * MSJ_ERR_BAD_ARGUMENT beyond that or on NULL; 22 (INVALID_JSON_POINTER) for a non-empty pointer that does not start with
+ * '/' or a '~' not followed by 0 or 1.  The object is immutable and may be used by any number of later calls on any stream
+ * of its context's device; msj_paths_destroy(NULL) does nothing.
+ * The call: inputs, D, T, [f_k, e_k), clipping, alignments, argument checks, "asynchronous on `stream`, no host round trip,
+ * workspace in the context" and "safe on ANY arrays" are those of msj_tape_documents_device, with d_fields (16-byte aligned,
+ * n_paths * capacity records; NULL only with capacity 0) in the place of its outputs and NULL `paths`, or paths of another
+ * device, MSJ_ERR_BAD_ARGUMENT.  d_numbers_result is READ here: the records searched are the first min(n_numbers,
+ * numbers_capacity); without it no record is available.
+ * Lookup of path p (segments s_0 .. s_(L-1)) in document k with verdict 0: start with v = f_k; for l = 0 .. L-1:
+ *   if d_type[v] != '{', or m = d_match[v] is not in (v, e_k): code 17 (INCORRECT_TYPE), stop
+ *   the members of v are the tokens i in (v, m) with d_type[i] == '"', d_depth[i] == d_depth[v] + 1 and d_type[i + 1] == ':'
+ *   (any token strictly between partners is at least that deep, so these are exactly the direct keys; f_k sits at depth 0,
+ *   so they are the keys at depth l + 1)
+ *   the match is the SMALLEST such i whose unescaped body equals s_l: the first duplicate wins, as in at_key (json.loads
+ *   keeps the last); none: code 20 (NO_SUCH_FIELD), stop; else v = i + 2
+ * and the value is token v with code 0.  A key with MSJ_SPAN_ESCAPED is unescaped as msj_tape_device does it; it can only
+ * match when its raw length lies in [len(s), 6 * len(s)].
+ * d_fields[p * capacity + k] for k < D; records for k >= D are not written.  A number's bits are those of the msj_number
+ * record whose token is v (binary search: the records are in token order); with no record available (d_numbers or
+ * d_numbers_result NULL, the record not stored, or of an ERR kind) type is 'd' / 'l' from MSJ_SPAN_FLOAT -- exact in a
+ * document with verdict 0 -- and MSJ_FIELD_NO_BITS is set.  d_verdicts == NULL looks every document up (unspecified where
+ * one is invalid, still in bounds).  d_result: code 0, or MSJ_CAPACITY when D > capacity (then n_documents = D and no record
+ * is written).  n == 0 or D == 0 writes a zero result (n_paths kept).
+ */
+#define MSJ_FIELD_NO_BITS 64u   /* msj_field.flags: a number without a record: bits = 0, type from MSJ_SPAN_FLOAT */
+typedef struct msj_paths msj_paths;
+typedef struct msj_field {   /* 16 bytes, one per (path, document) */
+    uint64_t bits;   /* 'l': the int64; 'd': the binary64 bit pattern; '"': (d_idx[v] + 1) | (d_end[v] - d_idx[v] - 1) << 32, the
+                        raw body's window offset and length; '{' '[': d_match[v], a window token; 't' 'f' 'n' and code != 0: 0 */
+    uint32_t token;  /* v as a window index; 0xFFFFFFFF when code != 0 */
+    uint8_t  type;   /* the tape's tag of the value: '{' '[' '"' 'l' 'd' 't' 'f' 'n'; 0 when code != 0 */
+    uint8_t  flags;  /* MSJ_SPAN_ESCAPED of a string value; MSJ_FIELD_NO_BITS on a number when no record was available */
+    uint16_t code;   /* 0; 20 NO_SUCH_FIELD; 17 INCORRECT_TYPE; or d_verdicts[k].code when that is not 0 (nothing is looked up) */
+} msj_field;
+typedef struct msj_select_documents_result {  /* 48 bytes */
+    int32_t  code;         /* 0, or MSJ_CAPACITY: more complete documents than `capacity`, no record written */
+    uint32_t flags;        /* 0 */
+    uint64_t n_documents;  /* D */
+    uint64_t n_paths;
+    uint64_t n_found;      /* records with code 0, over all paths */
+    uint64_t n_no_bits;    /* records with MSJ_FIELD_NO_BITS */
+    uint64_t reserved;
+} msj_select_documents_result;
+int32_t msj_paths_create(msj_ctx *ctx, const char *const *pointers, uint32_t n_paths, msj_paths **out);
+void msj_paths_destroy(msj_paths *paths);
+int32_t msj_select_documents_device(msj_ctx *ctx, const msj_paths *paths,
+        const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+        const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
+        const uint32_t *d_doc_first, const msj_documents_result *d_docs,
+        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+        const msj_document_verdict *d_verdicts,
+        msj_field *d_fields, uint64_t capacity, msj_select_documents_result *d_result, void *stream);
+/* Device workspace of one msj_select_documents_device call (the context keeps it): two state words per (path, document). */
+uint64_t msj_select_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity, uint32_t n_paths);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

@@ -108,6 +108,26 @@ class MsjTapeDocumentsResult(ctypes.Structure):
                 ("n_strings", ctypes.c_uint64), ("n_numbers", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
 
 
+class MsjField(ctypes.Structure):
+    """``msj_field`` (include/msj_stage1.h): one per (path, document) of a window."""
+
+    _fields_ = [("bits", ctypes.c_uint64), ("token", ctypes.c_uint32), ("type", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("code", ctypes.c_uint16)]
+
+
+class MsjSelectDocumentsResult(ctypes.Structure):
+    """``msj_select_documents_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_documents", ctypes.c_uint64),
+                ("n_paths", ctypes.c_uint64), ("n_found", ctypes.c_uint64), ("n_no_bits", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64)]
+
+
+FIELD_NO_BITS = 64
+NO_SUCH_FIELD, INCORRECT_TYPE, INVALID_JSON_POINTER = 20, 17, 22
+MAX_PATHS, MAX_PATH_SEGMENTS, MAX_SEGMENT_BYTES = 16, 8, 255
+
+
 class MsjSegment(ctypes.Structure):
     _fields_ = [
         ("byte_base", ctypes.c_uint64),
@@ -125,6 +145,7 @@ assert ctypes.sizeof(MsjTapeResult) == 32
 assert ctypes.sizeof(MsjDocumentVerdict) == 16 and ctypes.sizeof(MsjValidateDocumentsResult) == 48
 
 assert ctypes.sizeof(MsjDocumentTape) == 32 and ctypes.sizeof(MsjTapeDocumentsResult) == 64
+assert ctypes.sizeof(MsjField) == 16 and ctypes.sizeof(MsjSelectDocumentsResult) == 48
 
 _lib = None
 
@@ -250,6 +271,16 @@ def load():
          ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_tape_documents_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_tape_documents_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]
+    lib.msj_paths_create.restype = ctypes.c_int32
+    lib.msj_paths_create.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
+    lib.msj_paths_destroy.restype = None
+    lib.msj_paths_destroy.argtypes = [ctypes.c_void_p]
+    lib.msj_select_documents_device.restype = ctypes.c_int32
+    lib.msj_select_documents_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, ctypes.c_uint64, u32p, ctypes.c_uint64] + \
+        [ctypes.c_void_p] * 8 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                 ctypes.c_void_p]
+    lib.msj_select_documents_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_select_documents_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

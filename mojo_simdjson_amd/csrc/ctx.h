@@ -108,6 +108,7 @@ struct msj_ctx {
     DeviceBuffer vdoc_ws;         // msj_validate_documents_device: the same for a window (the documents' error words live in d_verdicts)
     DeviceBuffer tape_ws;         // msj_tape_device: pos[], element counts, block sums, the table of long strings
     DeviceBuffer tdoc_ws;         // msj_tape_documents_device: the same for a window, and 8 bytes per document
+    DeviceBuffer sel_ws;          // msj_select_documents_device: two state words per (path, document)
 };
 
 // ---- api.cpp ----

@@ -2,7 +2,17 @@
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a window).  Every call is the same few steps: check
 // the arguments (the order of the checks is part of the ABI: callers see which error wins), select the device, grow the
 // call's workspace, launch.
+#include <new>
+
 #include "ctx.h"
+#include "select_math.h"
+
+// msj_paths_create's object: the compiled paths (select_math.h: Paths) in device memory, and what the host needs of them
+struct msj_paths {
+    int device = 0;
+    uint32_t n_paths = 0, max_levels = 0;
+    DeviceBuffer blob;
+};
 
 namespace {
 
@@ -311,6 +321,55 @@ int32_t msj_tape_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t l
     return launched(msj_launch_tape_documents(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_numbers,
                                               numbers_capacity, d_verdicts, d_tape, tape_capacity, d_string_buf, string_capacity, d_doc_tapes,
                                               capacity, d_result, ctx->tdoc_ws.p, stream));
+}
+
+int32_t msj_paths_create(msj_ctx *ctx, const char *const *pointers, uint32_t n_paths, msj_paths **out) {
+    using namespace msj::sel;
+    if (!ctx || !out) return MSJ_ERR_BAD_ARGUMENT;
+    std::vector<Paths> host(1);  // (33 KiB: not on the stack)
+    Paths &h = host[0];
+    const int parsed = compile_paths(pointers, n_paths, h);
+    if (parsed != 0) return parsed < 0 ? MSJ_ERR_BAD_ARGUMENT : parsed;
+    if (!hip_ok(hipSetDevice(ctx->device))) return MSJ_ERR_HIP;
+    msj_paths *obj = new (std::nothrow) msj_paths;
+    if (!obj) return MSJ_MEMALLOC;
+    obj->device = ctx->device, obj->n_paths = n_paths, obj->max_levels = h.max_levels;
+    if (!obj->blob.reserve(sizeof h, false)) {
+        delete obj;
+        return MSJ_MEMALLOC;
+    }
+    if (!hip_ok(hipMemcpy(obj->blob.p, &h, sizeof h, hipMemcpyHostToDevice))) {  // synchronous: usable on any stream from here on
+        delete obj;
+        return MSJ_ERR_HIP;
+    }
+    *out = obj;
+    return MSJ_SUCCESS;
+}
+
+void msj_paths_destroy(msj_paths *paths) {
+    if (!paths) return;
+    (void)hipSetDevice(paths->device);
+    delete paths;
+}
+
+int32_t msj_select_documents_device(msj_ctx *ctx, const msj_paths *paths, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                                    const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end,
+                                    const uint8_t *d_flags, const uint32_t *d_doc_first, const msj_documents_result *d_docs,
+                                    const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+                                    const msj_document_verdict *d_verdicts, msj_field *d_fields, uint64_t capacity,
+                                    msj_select_documents_result *d_result, void *stream) {
+    if (!ctx || !paths || paths->device != ctx->device || !d_result || !d_docs) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((capacity > 0 && !d_fields) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers, d_fields) ||
+        !all_aligned(8, d_type, d_flags, d_docs, d_numbers_result, d_verdicts, d_result) || !aligned(d_doc_first, 4))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->sel_ws, msj_select_documents_workspace_bytes(n, len, capacity, paths->n_paths));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_select_documents(paths->blob.p, paths->n_paths, paths->max_levels, d_buf, len, d_idx, n, d_type, d_depth, d_match,
+                                                d_end, d_flags, d_doc_first, d_docs, d_numbers, numbers_capacity, d_numbers_result, d_verdicts,
+                                                d_fields, capacity, d_result, ctx->sel_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

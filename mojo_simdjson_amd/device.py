@@ -18,6 +18,27 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+class Paths:
+    """Compiled JSON pointers (``msj_paths``), from ``Stage1Device.compile_paths``."""
+
+    def __init__(self, lib, handle, pointers):
+        self.lib, self.handle = lib, handle
+        self.pointers = [p.decode("utf-8", "surrogateescape") for p in pointers]
+        self.n_paths = len(pointers)
+
+    def index(self, path_or_index):
+        """The column of a pointer (str) or of an index"""
+        if isinstance(path_or_index, (str, bytes)):
+            p = path_or_index.decode("utf-8", "surrogateescape") if isinstance(path_or_index, bytes) else path_or_index
+            return self.pointers.index(p)
+        return range(self.n_paths)[path_or_index]
+
+    def close(self):
+        if self.handle:
+            self.lib.msj_paths_destroy(self.handle)
+            self.handle = None
+
+
 class Stage1Device:
     """One ``msj_ctx`` bound to one GPU (one process per GPU)."""
 
@@ -32,9 +53,13 @@ class Stage1Device:
         if rc != 0:
             raise RuntimeError(f"msj_ctx_create failed: {rc}")
         self.ctx = h
+        self._paths = []  # what compile_paths handed out: closed with the device
 
     def close(self):
         if self.ctx:
+            for paths in self._paths:
+                paths.close()
+            self._paths = []
             self.lib.msj_ctx_destroy(self.ctx)
             self.ctx = None
 
@@ -418,6 +443,57 @@ class Stage1Device:
         if not sync:
             return d_result, d_tape, d_string_buf, d_doc_tapes
         return _lib.MsjTapeDocumentsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()), d_tape, d_string_buf, d_doc_tapes
+
+    def compile_paths(self, pointers):
+        """Compile RFC 6901 JSON pointers -- object keys only, "" the root value; 1 to 16 of them, at most 8 segments of at
+        most 255 bytes each -- for ``select_documents`` (``msj_paths_create``).  pointers: str (UTF-8) or bytes.  The handle
+        is immutable, usable by any number of calls, and closed with the device.  ValueError for a pointer that is none
+        (INVALID_JSON_POINTER) or beyond the limits."""
+        pointers = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in pointers]
+        if any(b"\0" in p for p in pointers):
+            raise ValueError("a JSON pointer cannot hold a NUL byte")
+        table = (ctypes.c_char_p * max(len(pointers), 1))(*pointers)
+        h = ctypes.c_void_p()
+        rc = self.lib.msj_paths_create(self.ctx, table, len(pointers), ctypes.byref(h))
+        if rc == _lib.INVALID_JSON_POINTER:
+            raise ValueError(f"not a JSON pointer (error {rc}): {pointers}")
+        if rc == -1:
+            raise ValueError(f"1 to {_lib.MAX_PATHS} paths of at most {_lib.MAX_PATH_SEGMENTS} segments of at most "
+                             f"{_lib.MAX_SEGMENT_BYTES} bytes: {pointers}")
+        if rc != 0:
+            raise RuntimeError(f"msj_paths_create failed: {rc}")
+        paths = Paths(self.lib, h, pointers)
+        self._paths.append(paths)
+        return paths
+
+    def select_documents(self, paths, d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs,
+                         d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_verdicts=None, d_fields=None, capacity=None,
+                         d_result=None, sync=True):
+        """Fields by path for every complete document of a window (``msj_select_documents_device``): one 16-byte
+        ``msj_field`` per (path, document), path-major.  paths: from ``compile_paths``; the arrays as for ``tape_documents``;
+        d_numbers / d_numbers_result: the records and the device result of ``number_values`` over the whole window (without
+        them a number field has its tag and MSJ_FIELD_NO_BITS); d_verdicts: the rows of ``validate_documents`` (None: every
+        document is looked up).  d_fields: int64 tensor of shape (n_paths, capacity, 2) -- [p, k, 0] the bits, [p, k, 1]
+        token | type << 32 | flags << 40 | code << 48 -- default one row per token.  Returns (``MsjSelectDocumentsResult``,
+        d_fields) -- blocking for the 48-byte result; with sync=False the device tensor that holds it, nothing waited for."""
+        n, length, numbers_capacity = int(n), int(length), int(numbers_capacity)
+        if d_fields is None:
+            capacity = n if capacity is None else int(capacity)
+            d_fields = torch.empty((paths.n_paths, max(capacity, 1), 2), dtype=torch.int64, device=self.device)
+        elif capacity is None:
+            capacity = d_fields.shape[1]
+        if d_result is None:
+            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        rc = self.lib.msj_select_documents_device(
+            self.ctx, paths.handle, _ptr(d_buf), length, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
+            _ptr(d_doc_first), _ptr(d_docs), _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
+            _ptr(d_numbers_result) if d_numbers_result is not None else None, _ptr(d_verdicts) if d_verdicts is not None else None,
+            _ptr(d_fields), int(capacity), _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_select_documents_device failed: {rc}")
+        if not sync:
+            return d_result, d_fields
+        return _lib.MsjSelectDocumentsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()), d_fields
 
     def parse_document(self, d_buf, length, max_depth=100, exact_strings=False):
         """The whole chain for one document in a device buffer: stage 1, ``stage2_prep`` with partners, ``number_values``,

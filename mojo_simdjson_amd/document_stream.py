@@ -14,6 +14,8 @@ Every window starts at a document.  Stage 1 wants a 16-byte aligned base, so the
 the document's offset rounded down and the up to 15 bytes in front (the end of the previous document)
 read as blanks (``MSJ_FLAG_SKIP``).  Offsets in ``d_idx`` are relative to ``Window.base``.
 """
+import json
+import struct
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -24,8 +26,44 @@ from .document import Document
 
 DOC_TAPE_DTYPE = np.dtype([("tape_first", "<u8"), ("string_first", "<u8"), ("tape_words", "<u4"), ("code", "<i4"),
                            ("string_bytes", "<u8")])  # msj_document_tape
+FIELD_DTYPE = np.dtype([("bits", "<u8"), ("token", "<u4"), ("type", "u1"), ("flags", "u1"), ("code", "<u2")])  # msj_field
 
 MAX_WINDOW = 1 << 31
+
+
+def _first_wins(pairs):
+    out = {}
+    for key, value in pairs:
+        out.setdefault(key, value)
+    return out
+
+
+# a selected container's text: duplicate keys as the lookup itself treats them (at_key: the first one wins)
+_CONTAINER = json.JSONDecoder(object_pairs_hook=_first_wins)
+_ATOMS = {ord("t"): True, ord("f"): False, ord("n"): None}
+
+
+def field_value(rec, data, idx, end):
+    """The Python value of one ``msj_field`` (a FIELD_DTYPE row): None when it has a code; a string decoded from the
+    window's bytes `data` (through json when it is escaped), a container from its text (its closing bracket is token
+    rec["bits"]), a number from its bits -- or from its text when the record has none (MSJ_FIELD_NO_BITS).  idx, end: host
+    copies of the window's d_idx / d_end."""
+    if rec["code"] != 0:
+        return None
+    t, bits = int(rec["type"]), int(rec["bits"])
+    if t in _ATOMS:
+        return _ATOMS[t]
+    if t == ord('"'):
+        raw = bytes(data[bits & 0xFFFFFFFF:(bits & 0xFFFFFFFF) + (bits >> 32)])
+        return json.loads(b'"' + raw + b'"') if rec["flags"] & 2 else raw.decode("utf-8")
+    if t in (ord("{"), ord("[")):
+        return _CONTAINER.decode(bytes(data[int(idx[int(rec["token"])]):int(idx[bits]) + 1]).decode("utf-8"))
+    if t in (ord("l"), ord("d")):
+        if rec["flags"] & _lib.FIELD_NO_BITS:
+            v = int(rec["token"])
+            return json.loads(bytes(data[int(idx[v]):int(end[v])]))
+        return struct.unpack("<q" if t == ord("l") else "<d", struct.pack("<Q", bits))[0]
+    raise ValueError(f"not a tape tag: {t}")
 
 
 def _skip_flag(n):
@@ -63,7 +101,30 @@ class Window:
     d_string_buf: torch.Tensor = None  # uint8[string_bytes]: its string records from string_first_k on
     d_doc_tapes: torch.Tensor = None   # int64[n_documents, 4]: msj_document_tape per document
     n_built: int = None                # documents with code 0: the ones that have a tape
+    # DocumentStream(select=[...]) only: a record per (path, document) (msj_select_documents_device)
+    d_fields: torch.Tensor = None      # int64[n_paths, n_documents, 2]: msj_field per path and document, each path a column
+    d_window: torch.Tensor = None      # uint8[length]: the window's bytes (string fields are spans of them)
+    paths: object = None               # the compiled paths (Stage1Device.compile_paths)
+    n_found: int = None                # records with code 0, over all paths
     _documents: list = field(default=None, repr=False, compare=False)  # what documents() built: host copies, kept
+    _host: tuple = field(default=None, repr=False, compare=False)      # what values() reads: host copies, kept
+
+    def column(self, path_or_index):
+        """The records of one path as a numpy structured array (FIELD_DTYPE), one per complete document: one host copy.
+        Like every array a Window carries, d_fields is reused by the next window."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        p = self.paths.index(path_or_index)
+        return np.ascontiguousarray(self.d_fields[p].cpu().numpy()).view(FIELD_DTYPE).reshape(-1)
+
+    def values(self, path_or_index):
+        """The values of one path as a Python list, one per complete document: None where the record has a code (20
+        NO_SUCH_FIELD, 17 INCORRECT_TYPE, an invalid document's), see ``field_value``.  The window's bytes, d_idx and d_end
+        come to the host once per window."""
+        col = self.column(path_or_index)
+        if self._host is None:
+            self._host = (self.d_window.cpu().numpy(), self.d_idx.cpu().numpy().view(np.uint32), self.d_end.cpu().numpy().view(np.uint32))
+        return [field_value(r, *self._host) for r in col]
 
     def documents(self):
         """A ``Document`` per complete document, None for one with a verdict code (its code: ``d_doc_tapes`` / ``d_verdicts``).
@@ -118,10 +179,16 @@ class DocumentStream:
     the string buffer, the records and the number records start at tape_words / string_bytes / documents / numbers
     (defaults from the index capacity) and grow to what a window needs: the call reports the true sizes, and only the
     calls that need it run again.
+
+    select=[pointers...] (implies validate): every window also carries one ``msj_field`` per pointer and document
+    (``msj_select_documents_device``; ``Window.column`` / ``Window.values``).  The pointers are compiled once, here; the
+    number call runs with room for its records, the select call follows the verdict call on the same stream and its
+    48-byte result comes back in the same read.  A window with more documents than `documents` records per path grows the
+    array and runs only that call again.
     """
 
     def __init__(self, dev, d_buf, length=None, window=1 << 28, flags=0, index_capacity=None, reuse_counts=True, validate=False,
-                 max_depth=100, parse=False, tape_words=None, string_bytes=None, documents=None, numbers=None):
+                 max_depth=100, parse=False, tape_words=None, string_bytes=None, documents=None, numbers=None, select=None):
         self.dev = dev
         self.d_buf = d_buf
         self.length = int(d_buf.numel() if length is None else length)
@@ -144,11 +211,14 @@ class DocumentStream:
         self._zero = dev.new_carry()
         self._carry = dev.new_carry()
         self.parse = bool(parse)
-        self.validate = bool(validate) or self.parse
+        self.paths = dev.compile_paths(select) if select is not None else None
+        self.validate = bool(validate) or self.parse or self.paths is not None
         self.max_depth = int(max_depth)
         # msj_tokens_result | msj_documents_result (validate: | msj_numbers_result | msj_validate_documents_result; parse:
-        # | msj_tape_documents_result)
-        self._results = torch.zeros(208 if self.parse else (144 if self.validate else 64), dtype=torch.uint8, device=dvc)
+        # | msj_tape_documents_result; select: | msj_select_documents_result)
+        self._sel_at = 208 if self.parse else 144
+        size = 208 if self.parse else (144 if self.validate else 64)
+        self._results = torch.zeros(size + (48 if self.paths is not None else 0), dtype=torch.uint8, device=dvc)
         if self.validate:
             self._match = torch.empty(self.capacity, dtype=torch.int32, device=dvc)
             self._end = torch.empty(self.capacity, dtype=torch.int32, device=dvc)
@@ -161,7 +231,12 @@ class DocumentStream:
             self._tape = torch.empty(max(int(cap + cap // 2 + 2 if tape_words is None else tape_words), 2), dtype=torch.int64, device=dvc)
             self._sbuf = torch.empty(max(int(w + cap // 2 + 64 if string_bytes is None else string_bytes), 16), dtype=torch.uint8, device=dvc)
             self._doc_tapes = torch.empty((max(int(cap // 8 + 1024 if documents is None else documents), 1), 4), dtype=torch.int64, device=dvc)
+        if self.parse or self.paths is not None:
+            cap = self.capacity
             self._numbers = torch.empty((max(int(cap // 4 + 1024 if numbers is None else numbers), 1), 2), dtype=torch.int64, device=dvc)
+        if self.paths is not None:
+            rows = max(int(self.capacity // 8 + 1024 if documents is None else documents), 1)
+            self._fields = torch.empty((self.paths.n_paths, rows, 2), dtype=torch.int64, device=dvc)
         self.windows = 0
 
     def __iter__(self):
@@ -191,12 +266,15 @@ class DocumentStream:
             d_first, _ = dev.documents(d_win, wlen, self._idx, n, d_type, d_depth, is_final=last, d_carry=self._carry,
                                        d_doc_first=self._first, d_result=self._results[32:64], sync=False, after_tokens=self.reuse_counts)
             if self.validate:  # ... and with them those of the number call and the verdict call
-                if self.parse:  # with room for the records: the tapes read them
+                if self.parse or self.paths is not None:  # with room for the records: the tapes and the fields read them
                     d_numbers, ncap = self._numbers, self._numbers.shape[0]
                     dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=ncap, d_result=self._results[64:96], sync=False,
                                       d_numbers=d_numbers)
                     self._verdict_call(d_win, wlen, n, d_numbers, ncap)
-                    self._tape_call(d_win, wlen, n)
+                    if self.parse:
+                        self._tape_call(d_win, wlen, n)
+                    if self.paths is not None:
+                        self._select_call(d_win, wlen, n)
                 else:
                     dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=0, d_result=self._results[64:96], sync=False)
                     self._verdict_call(d_win, wlen, n, None, 0)
@@ -219,7 +297,9 @@ class DocumentStream:
             extra = {}
             if self.validate:
                 vres = _lib.MsjValidateDocumentsResult.from_buffer_copy(blob[96:144])
-                d_numbers, ncap = (self._numbers, self._numbers.shape[0]) if self.parse else (None, 0)
+                records = self.parse or self.paths is not None
+                d_numbers, ncap = (self._numbers, self._numbers.shape[0]) if records else (None, 0)
+                numbers_were = self._numbers if records else None
                 again = False  # the tape call has to follow a verdict call that ran again
                 if vres.code == errors.CAPACITY:  # more documents than verdicts: room for all of them, and once more
                     self._verdicts = torch.empty((nd, 2), dtype=torch.int64, device=dev.device)
@@ -228,15 +308,16 @@ class DocumentStream:
                 if vres.flags & _lib.VALIDATE_NUMBERS_UNCHECKED:
                     # the rare window with a bad number: its records, then the verdicts again
                     cap = _lib.MsjNumbersResult.from_buffer_copy(blob[64:96]).n_numbers
-                    if self.parse:
+                    if records:
                         self._numbers = torch.empty((cap, 2), dtype=torch.int64, device=dev.device)
                     d_numbers, _ = dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=cap, d_result=self._results[64:96],
-                                                     sync=False, d_numbers=self._numbers if self.parse else None)
+                                                     sync=False, d_numbers=self._numbers if records else None)
                     vres = self._verdict_call(d_win, wlen, n, d_numbers, cap, read=True)
                     again = True
                 extra = dict(d_match=d_match[:nt], d_end=d_end[:nt], d_flags=d_flags[:nt], d_verdicts=self._verdicts[:nd],
                              n_invalid=int(vres.n_invalid), verdict_flags=int(vres.flags),
                              first_invalid=int(vres.first_invalid) if vres.n_invalid else None)
+                sel_again = again  # ... and so has the select call
                 if self.parse:
                     tres = _lib.MsjTapeDocumentsResult.from_buffer_copy(blob[144:208])
                     for _ in range(3):
@@ -248,6 +329,20 @@ class DocumentStream:
                         raise DocumentStreamError(int(tres.code), f"window at {base}: the tapes do not fit what the call asked for")
                     extra.update(d_tape=self._tape[:int(tres.tape_words)], d_string_buf=self._sbuf[:int(tres.string_bytes)],
                                  d_doc_tapes=self._doc_tapes[:nd], n_built=int(tres.n_built))
+                if self.paths is not None:
+                    sres = _lib.MsjSelectDocumentsResult.from_buffer_copy(blob[self._sel_at:self._sel_at + 48])
+                    need = _lib.MsjNumbersResult.from_buffer_copy(blob[64:96]).n_numbers
+                    if need > self._numbers.shape[0]:  # fewer records than number tokens: the number call again
+                        self._numbers = torch.empty((int(need) * 5 // 4 + 1, 2), dtype=torch.int64, device=dev.device)
+                        dev.number_values(d_win, wlen, self._idx, n, d_flags, capacity=self._numbers.shape[0], d_result=self._results[64:96],
+                                          sync=False, d_numbers=self._numbers)
+                    if sres.code == errors.CAPACITY:  # more documents than records per path: room for them, only this call again
+                        self._fields = torch.empty((self.paths.n_paths, nd * 5 // 4 + 1, 2), dtype=torch.int64, device=dev.device)
+                    if sel_again or sres.code != 0 or self._numbers is not numbers_were:
+                        sres = self._select_call(d_win, wlen, n, read=True)
+                    if sres.code != 0:
+                        raise DocumentStreamError(int(sres.code), f"window at {base}: the fields do not fit what the call asked for")
+                    extra.update(d_fields=self._columns[:, :nd], d_window=d_win, paths=self.paths, n_found=int(sres.n_found))
             yield Window(base=base, length=wlen, consumed=consumed, n_tokens=nt, n_documents=nd,
                          utf8_error=bool(carry.utf8_error), d_idx=self._idx[:nt], d_type=d_type[:nt],
                          d_depth=d_depth[:nt], d_doc_first=d_first[:nd], **extra)
@@ -276,6 +371,23 @@ class DocumentStream:
                                 d_string_buf=self._sbuf, d_doc_tapes=self._doc_tapes, capacity=capacity, d_result=r[144:208], sync=False)
         if read:
             return _lib.MsjTapeDocumentsResult.from_buffer_copy(r[144:208].cpu().numpy().tobytes())
+        return None
+
+    def _select_call(self, d_win, wlen, n, read=False):
+        """``select_documents`` over the stream's arrays behind the verdict call; read: wait for its result and return it."""
+        r = self._results
+        at = self._sel_at
+        # (no more records per path than verdict rows: a verdict is read per document looked up.  The records of path p
+        # start at p * capacity: the view of the array that the Window carries has that shape)
+        capacity = min(self._fields.shape[1], self._verdicts.shape[0])
+        n_paths = self.paths.n_paths
+        self._columns = self._fields.view(-1, 2)[:n_paths * capacity].view(n_paths, capacity, 2)
+        self.dev.select_documents(self.paths, d_win, wlen, self._idx, n, self._type, self._depth, self._match, self._end, self._flags,
+                                  self._first, r[32:64], d_numbers=self._numbers, numbers_capacity=self._numbers.shape[0],
+                                  d_numbers_result=r[64:96], d_verdicts=self._verdicts, d_fields=self._fields, capacity=capacity,
+                                  d_result=r[at:at + 48], sync=False)
+        if read:
+            return _lib.MsjSelectDocumentsResult.from_buffer_copy(r[at:at + 48].cpu().numpy().tobytes())
         return None
 
     def _grow_and_tape(self, d_win, wlen, n, d_flags, tres):
