@@ -3,6 +3,7 @@ JSON pointer of object keys looked up in one document's text.  No tokens, depths
 json with a hook that keeps the FIRST of duplicate keys (at_key's rule; json.loads alone would keep the last), and the
 keys are walked.  tests/test_select_math.py holds the host twin of the kernels' arithmetic against it.
 """
+import functools
 import json
 
 NO_SUCH_FIELD, INCORRECT_TYPE, INVALID_JSON_POINTER = 20, 17, 22
@@ -50,10 +51,15 @@ def segments(pointer):
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def _segments_once(pointer):
+    return tuple(segments(pointer))
+
+
 def lookup(value, pointer):
     """The pointer in a decoded document (decode) -> (code, value): (0, the value), (17, None) where a segment meets
     something that is no object, (20, None) where the object has no such key"""
-    for seg in segments(pointer):
+    for seg in _segments_once(pointer):
         if not isinstance(value, Obj):
             return INCORRECT_TYPE, None
         if seg not in value:

@@ -155,23 +155,26 @@ def check_against_reference(w, got, pointers, texts, codes=None, bits=True):
     assert len(texts) >= w.D
     data = np.frombuffer(w.data, dtype=np.uint8)
     decoded = [None if codes[k] else ref.decode(texts[k]) for k in range(w.D)]
+    starts = w.first[:w.D].tolist()
+    ends = starts[1:] + [w.T]
     out, found, no_bits = {}, 0, 0
     for p, pointer in enumerate(pointers):
-        col = got.column(p)
+        # the column's records as Python values, read once: a window of 260 000 documents is walked here too
+        col = {name: got.column(p)[name][:w.D].tolist() for name in FIELD_DTYPE.names}
         for k in range(w.D):
-            r = col[k]
+            r = {name: col[name][k] for name in FIELD_DTYPE.names}
             where = (pointer, k, texts[k][:100], r)
-            f, e = w.bounds(k)
+            f, e = starts[k], ends[k]
             if codes[k]:
                 want = (codes[k], None)
             else:
                 want = ref.lookup(decoded[k], pointer)
-            assert int(r["code"]) == want[0], where
+            assert r["code"] == want[0], where
             if want[0]:
-                assert (int(r["bits"]), int(r["token"]), int(r["type"]), int(r["flags"])) == (0, NO_TOKEN, 0, 0), where
+                assert (r["bits"], r["token"], r["type"], r["flags"]) == (0, NO_TOKEN, 0, 0), where
                 value = None
             else:
-                assert f <= int(r["token"]) < e and chr(int(r["type"])) in '{["ldtfn', where
+                assert f <= r["token"] < e and chr(r["type"]) in '{["ldtfn', where
                 if bits:
                     assert not r["flags"] & _lib.FIELD_NO_BITS, where
                 value = field_value(r, data, w.idx, w.end)

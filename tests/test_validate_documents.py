@@ -80,17 +80,23 @@ class Chain:
     def verdicts(self, max_depth=100, numbers=True, capacity=None, sync=True):
         """-> ([(code, token)] per document the result counts, result); the rows behind them must be untouched.  sync=False:
         (d_verdicts, d_result), nothing waited for."""
-        import torch
+        return device_verdicts(self, max_depth, numbers, capacity, sync)
 
-        cap = self.n if capacity is None else int(capacity)
-        rows = torch.full((cap + 8, 2), SENTINEL, dtype=torch.int64, device=self.dev.device)
-        d_v, res = self.dev.validate_documents(self.d_buf, self.length, self.d_idx, self.n, self.d_type, self.d_depth, self.d_match,
-                                               self.d_end, self.d_flags, self.d_first, self.d_docs, d_numbers=self.d_numbers,
-                                               numbers_capacity=self.ncap, d_numbers_result=self.d_num if numbers else None,
-                                               max_depth=max_depth, d_verdicts=rows, capacity=cap, sync=sync)
-        if not sync:
-            return d_v, res
-        return unpack(rows, res) + (res,)
+
+def device_verdicts(a, max_depth=100, numbers=True, capacity=None, sync=True):
+    """msj_validate_documents_device over the arrays `a` (a Chain, or the oracles' arrays uploaded with the number call's
+    result: d_num, ncap), d_verdicts filled with SENTINEL and 8 rows longer than its capacity -> as Chain.verdicts"""
+    import torch
+
+    cap = a.n if capacity is None else int(capacity)
+    rows = torch.full((cap + 8, 2), SENTINEL, dtype=torch.int64, device=a.dev.device)
+    d_v, res = a.dev.validate_documents(a.d_buf, a.length, a.d_idx, a.n, a.d_type, a.d_depth, a.d_match, a.d_end, a.d_flags, a.d_first,
+                                        a.d_docs, d_numbers=a.d_numbers, numbers_capacity=a.ncap,
+                                        d_numbers_result=a.d_num if numbers else None, max_depth=max_depth, d_verdicts=rows, capacity=cap,
+                                        sync=sync)
+    if not sync:
+        return d_v, res
+    return unpack(rows, res) + (res,)
 
 
 def unpack(rows, res):
