@@ -979,6 +979,57 @@ int32_t msj_select_documents_device(msj_ctx *ctx, const msj_paths *paths,
 uint64_t msj_select_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity, uint32_t n_paths);
 
 /*
+ * ---- a selected path's strings as one column (DERIVED) ------------------------------------------
+ * msj_string_column_device -- for ONE path of msj_select_documents_device, the string values of every document in the
+ * standard variable-length layout: d_offsets[D + 1], the unescaped bytes back to back in d_bytes, a validity byte per row in
+ * d_valid.  (A numeric column needs no call: an msj_field carries the int64 / binary64 in `bits`, so it is a strided view of
+ * d_fields.)  All on the device, on the caller's stream, no host round trip.
+ * Inputs: d_buf / len, the window the select call ran over; d_column = d_fields + p * (the select call's capacity), path p's
+ * records; d_select, the device msj_select_documents_result of that call.  D = d_select->n_documents is read on the device.
+ * d_select->code != 0: d_result is a zero result with that code and nothing else is written.  D > capacity: MSJ_CAPACITY with
+ * n_rows = D and nothing else is written (a window has fewer than 2^31 tokens: D >= 2^31, which no call writes, is treated
+ * the same whatever the capacity).
+ * Row k (k < D) is a string, d_valid[k] = 1, iff its record has code == 0, type == '"' and its span b = bits & 0xFFFFFFFF,
+ * r = bits >> 32 satisfies b + r <= len: a record whose span does not lie inside the window is no string and is never
+ * dereferenced.  A row that is no string has d_valid[k] = 0 and length 0.  A string's length ulen(k) is r without
+ * MSJ_SPAN_ESCAPED in the record's flags, else what msj_tape_device's ulen gives for the body [b, b + r): the same escapes,
+ * the same UTF-8 of \u, the same surrogate pairs.
+ *   d_offsets[0] = 0, d_offsets[k + 1] = d_offsets[k] + ulen(k) for k < D; uint64, so that no input -- records from anywhere
+ *                included -- has an overflow case.  capacity + 1 entries; those past D are not written
+ *   d_valid      capacity entries; those at or past D are not written
+ *   d_bytes      [d_offsets[k], d_offsets[k + 1]) is row k's unescaped body: no length prefix, no terminator.  Bytes at or past
+ *                min(total_bytes, bytes_capacity) are not written: with total_bytes > bytes_capacity the offsets and d_valid are
+ *                complete, the bytes clipped, the code MSJ_CAPACITY, and total_bytes says what to allocate.  d_bytes == NULL
+ *                (with bytes_capacity 0) is the layout-only form: offsets, d_valid and total_bytes exact, code 0
+ * d_result: code; n_rows = D; n_strings the rows with d_valid = 1, n_escaped those of them that were unescaped; total_bytes =
+ * d_offsets[D]; n_other the rows whose record has code 0 and that are no string (a number, a container, true / false / null);
+ * a row whose record has a code (NO_SUCH_FIELD, INCORRECT_TYPE, an invalid document's) is in neither count.  D == 0 writes
+ * d_offsets[0] = 0 and a zero result.
+ * Arguments: d_column 16-byte aligned; d_offsets, d_select, d_result 8-byte; d_valid, d_bytes any.  NULL d_result / d_select /
+ * d_buf, NULL d_column / d_offsets / d_valid with capacity > 0, NULL d_bytes with bytes_capacity > 0, or an off-grid pointer:
+ * MSJ_ERR_BAD_ARGUMENT; len > MSJ_MAX_SEGMENT_BYTES: MSJ_CAPACITY; nothing is launched on either.  Asynchronous on `stream`,
+ * workspace in the context.  Safe on ANY records: the window is read only inside [0, len), every store to d_bytes is checked
+ * against bytes_capacity, and rows at or past D are not touched.
+ */
+typedef struct msj_string_column_result {   /* 48 bytes */
+    int32_t  code;         /* 0; MSJ_CAPACITY (rows > capacity: nothing else written; or total_bytes > bytes_capacity:
+                              offsets / valid complete, bytes clipped); or d_select->code when that is not 0 */
+    uint32_t flags;        /* 0 */
+    uint64_t n_rows;       /* D */
+    uint64_t n_strings;    /* rows with valid = 1 */
+    uint64_t n_escaped;    /* ... of which were unescaped */
+    uint64_t total_bytes;  /* offsets[D], exact also when clipped and when d_bytes == NULL */
+    uint64_t n_other;      /* rows with code 0 whose value is not a string (number, container, true/false/null) */
+} msj_string_column_result;
+int32_t msj_string_column_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len,
+        const msj_field *d_column, const msj_select_documents_result *d_select,
+        uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+        uint8_t *d_bytes, uint64_t bytes_capacity,
+        msj_string_column_result *d_result, void *stream);
+/* Device workspace of one msj_string_column_device call (the context keeps it): 4 bytes per row of capacity, 8 per 256 rows. */
+uint64_t msj_string_column_workspace_bytes(uint64_t capacity);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

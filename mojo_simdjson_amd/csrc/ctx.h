@@ -109,6 +109,7 @@ struct msj_ctx {
     DeviceBuffer tape_ws;         // msj_tape_device: pos[], element counts, block sums, the table of long strings
     DeviceBuffer tdoc_ws;         // msj_tape_documents_device: the same for a window, and 8 bytes per document
     DeviceBuffer sel_ws;          // msj_select_documents_device: two state words per (path, document)
+    DeviceBuffer scol_ws;         // msj_string_column_device: the counts, a sum per block of rows, a length per row
 };
 
 // ---- api.cpp ----

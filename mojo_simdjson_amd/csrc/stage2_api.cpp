@@ -1,5 +1,5 @@
 // stage2_api.cpp -- extern "C" entry points of everything that runs behind stage 1 (include/msj_stage1.h): tokens, spans,
-// the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a window).  Every call is the same few steps: check
+// the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a window), fields by path and a path's strings as a column.  Every call is the same few steps: check
 // the arguments (the order of the checks is part of the ABI: callers see which error wins), select the device, grow the
 // call's workspace, launch.
 #include <new>
@@ -370,6 +370,20 @@ int32_t msj_select_documents_device(msj_ctx *ctx, const msj_paths *paths, const 
     return launched(msj_launch_select_documents(paths->blob.p, paths->n_paths, paths->max_levels, d_buf, len, d_idx, n, d_type, d_depth, d_match,
                                                 d_end, d_flags, d_doc_first, d_docs, d_numbers, numbers_capacity, d_numbers_result, d_verdicts,
                                                 d_fields, capacity, d_result, ctx->sel_ws.p, stream));
+}
+
+int32_t msj_string_column_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const msj_field *d_column,
+                                 const msj_select_documents_result *d_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+                                 uint8_t *d_bytes, uint64_t bytes_capacity, msj_string_column_result *d_result, void *stream) {
+    if (!ctx || !d_result || !d_select || !d_buf) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && (!d_column || !d_offsets || !d_valid)) return MSJ_ERR_BAD_ARGUMENT;
+    if (bytes_capacity > 0 && !d_bytes) return MSJ_ERR_BAD_ARGUMENT;
+    if (len > MSJ_MAX_SEGMENT_BYTES) return MSJ_CAPACITY;
+    if (!aligned(d_column, 16) || !all_aligned(8, d_offsets, d_select, d_result)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->scol_ws, msj_string_column_workspace_bytes(capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_string_column(d_buf, len, d_column, d_select, d_offsets, d_valid, capacity, d_bytes, bytes_capacity, d_result,
+                                             ctx->scol_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

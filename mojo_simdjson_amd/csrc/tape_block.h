@@ -1,6 +1,7 @@
 // tape_block.h -- the device pieces that tape_kernel.hip (one document) and tape_docs_kernel.hip (every document of a
 // window) share: the geometry of the token passes, the call's state and workspace, the exclusive sum over a workgroup and
-// over the blocks, a string token's body and the checked writer, the wave's walk over a long body, the 8-ary min tree of a
+// over the blocks, a string token's body (the checked writer and the wave's walk over a long body are wave_unescape.h, which
+// string_column_kernel.hip shares), the 8-ary min tree of a
 // block's depths with its two searches, and the bodies of the kernels that are the same in both calls (positions and
 // element counts, the block minima, the pending counts, the long bodies' bytes).  Device code only; the per-token
 // arithmetic is tape_math.h.
@@ -11,6 +12,7 @@
 #include "../../include/msj_stage1.h"
 #include "tape_math.h"
 #include "wave_ops.h"
+#include "wave_unescape.h"
 
 namespace msj_tape {
 
@@ -22,7 +24,6 @@ constexpr int kThreads = 256;
 constexpr int kPer = 4;                        // tokens per lane
 constexpr uint32_t kBlock = kThreads * kPer;   // tokens per workgroup
 constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kLaneBody = 1024;           // bodies up to this many bytes are measured and written by their lane
 constexpr int kListBlocks = 512;               // grid of the list kernels (they loop over what the list holds)
 constexpr int32_t kFar = 0x7FFFFFFF;
 
@@ -83,50 +84,6 @@ __device__ __forceinline__ Body body_of(const uint32_t *__restrict__ idx, const 
     return y;
 }
 
-struct BufWriter {  // byte o of a string's record (its length prefix included): checked against the capacity
-    uint8_t *out;
-    uint64_t base, cap;
-    __device__ __forceinline__ void put(uint64_t o, uint32_t byte) const {
-        const uint64_t a = base + o;
-        if (out && a < cap) out[a] = (uint8_t)byte;
-    }
-};
-
-// One long body by one wave, 64 bytes per step (tape_math.h: unescape_step is the host's form of this loop).  wr.out ==
-// NULL measures.  Returns the unescaped length (in every lane).
-__device__ __forceinline__ uint64_t wave_unescape(const ByteReader &r, const BufWriter &wr, uint64_t b, uint64_t e, bool measure) {
-    const uint32_t lane = threadIdx.x & 63;
-    StepState st = step_begin();
-    for (uint64_t p0 = b; p0 < e; p0 += 64) {
-        const uint64_t p = p0 + lane;
-        const uint32_t c = p < e ? r.at(p) : 0u;
-        const uint64_t bs = __ballot(p < e && c == '\\');
-        uint64_t carry = st.carry;
-        const uint64_t starts = escape_start_mask(bs, carry);
-        const bool is_start = (starts >> lane) & 1u;
-        LaneOut lo{0, 0};
-        if (p < e) {
-            lo.out = 1;
-            if (is_start) lo = step_lane(r, NoWrite{}, b, e, p0, lane, 64, starts, st, 0, true);
-        }
-        // the bytes the step's escapes cover: every escape covers the byte behind it, a \u escape four more
-        const uint64_t six = __ballot(is_start && lo.len == 6);
-        uint64_t cover_lo = st.cover | (starts << 1), cover_hi = starts >> 63;
-#pragma unroll
-        for (int k = 1; k <= 5; k++) cover_lo |= six << k, cover_hi |= six >> (64 - k);
-        if (!is_start && ((cover_lo >> lane) & 1u)) lo.out = 0;
-        const uint32_t inc = wave_scan(lo.out);
-        const uint64_t o = st.out + inc - lo.out;
-        if (!measure && lo.out) {
-            if (is_start)
-                (void)step_lane(r, wr, b, e, p0, lane, 64, starts, st, o, false);
-            else
-                wr.put(o, c);
-        }
-        step_end(st, 64, starts, cover_lo, cover_hi, st.out + (uint32_t)__shfl((int)inc, 63));
-    }
-    return st.out;
-}
 // exclusive sums over the blocks by ONE workgroup of 1 024 lanes: b_words / b_nums / b_nstr / b_sbytes become prefixes, run[]
 // receives the totals (words, number tokens, strings, string bytes) in every lane
 __device__ __forceinline__ void scan_blocks(const Work &w, uint64_t (&s_w)[4][16], uint64_t (&run)[4]) {

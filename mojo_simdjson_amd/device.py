@@ -495,6 +495,53 @@ class Stage1Device:
             return d_result, d_fields
         return _lib.MsjSelectDocumentsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()), d_fields
 
+    def string_column(self, d_buf, length, d_fields, p, d_select_result, d_offsets=None, d_valid=None, d_bytes=None, capacity=None,
+                      bytes_capacity=None, strings=True, d_result=None, sync=True):
+        """One path's string values as a column (``msj_string_column_device``): offsets, the unescaped bytes back to back
+        and a validity byte per row, all on the device.  d_buf / length: the window ``select_documents`` ran over; d_fields:
+        its records, int64 of shape (n_paths, rows, 2); p: the path's index; d_select_result: the device
+        ``msj_select_documents_result`` of that call (``select_documents(..., sync=False)``), read on the device.  d_offsets:
+        int64 tensor of capacity + 1 entries, d_valid: uint8 tensor of capacity entries (default: new ones, capacity = the
+        rows of d_fields); d_bytes: uint8 tensor of ``bytes_capacity`` bytes (default: its size).  Without a d_bytes of the
+        caller's, one of ``bytes_capacity`` bytes is made, and without that number either it is sized from a layout-only
+        first call, whose 48-byte result is waited for.  strings=False: the layout-only form alone (d_bytes None).  Returns
+        (``MsjStringColumnResult``, d_offsets, d_valid, d_bytes) -- blocking for the 48-byte result; with sync=False the
+        device tensor that holds it, nothing waited for."""
+        d_col = d_fields[p]
+        if d_col.stride(-1) != 1 or (d_col.shape[0] > 1 and d_col.stride(0) != 2):
+            raise ValueError("the records of a path must be contiguous")
+        if capacity is None:
+            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_col.shape[0]
+        capacity = int(capacity)
+        if d_offsets is None:
+            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
+        if d_valid is None:
+            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
+        if d_result is None:
+            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
+
+        def call(d_out, room):
+            rc = self.lib.msj_string_column_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_col), _ptr(d_select_result), _ptr(d_offsets),
+                                                   _ptr(d_valid), capacity, _ptr(d_out) if d_out is not None else None, int(room),
+                                                   _ptr(d_result), self._stream())
+            if rc != 0:
+                raise RuntimeError(f"msj_string_column_device failed: {rc}")
+
+        def read():
+            return _lib.MsjStringColumnResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
+
+        if not strings:
+            d_bytes, bytes_capacity = None, 0
+        elif d_bytes is None:
+            if bytes_capacity is None:
+                call(None, 0)
+                bytes_capacity = read().total_bytes
+            d_bytes = torch.empty(max(int(bytes_capacity), 1), dtype=torch.uint8, device=self.device)
+        elif bytes_capacity is None:
+            bytes_capacity = d_bytes.numel()
+        call(d_bytes, bytes_capacity)
+        return (read() if sync else d_result), d_offsets, d_valid, d_bytes
+
     def parse_document(self, d_buf, length, max_depth=100, exact_strings=False):
         """The whole chain for one document in a device buffer: stage 1, ``stage2_prep`` with partners, ``number_values``,
         ``validate`` and ``tape`` enqueued on one stream.  Returns stage 1's code if that is not 0, else

@@ -106,6 +106,8 @@ class Window:
     d_window: torch.Tensor = None      # uint8[length]: the window's bytes (string fields are spans of them)
     paths: object = None               # the compiled paths (Stage1Device.compile_paths)
     n_found: int = None                # records with code 0, over all paths
+    d_select: torch.Tensor = None      # uint8[48]: the select call's msj_select_documents_result, where it lies on the device
+    dev: object = field(default=None, repr=False, compare=False)  # the Stage1Device whose call strings() runs
     _documents: list = field(default=None, repr=False, compare=False)  # what documents() built: host copies, kept
     _host: tuple = field(default=None, repr=False, compare=False)      # what values() reads: host copies, kept
 
@@ -125,6 +127,50 @@ class Window:
         if self._host is None:
             self._host = (self.d_window.cpu().numpy(), self.d_idx.cpu().numpy().view(np.uint32), self.d_end.cpu().numpy().view(np.uint32))
         return [field_value(r, *self._host) for r in col]
+
+    def strings(self, path_or_index, bytes_capacity=None):
+        """The string values of one path as a column ON THE DEVICE (``msj_string_column_device``): (offsets int64[D + 1],
+        bytes uint8[total], valid bool[D]) -- row k's unescaped UTF-8 is bytes[offsets[k]:offsets[k + 1]], empty where valid[k]
+        is False (the value is no string, the key is missing, the document has a verdict code).  The call runs on the
+        window's records and bytes where they lie; only its 48-byte result comes to the host.  The byte buffer starts from
+        a guess (bytes_capacity: the caller's) and, when the call says it was too small, is made as large as the call asks and
+        the call runs once more."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        p = self.paths.index(path_or_index)
+        nd = self.n_documents
+        d_off = torch.empty(nd + 1, dtype=torch.int64, device=self.d_fields.device)
+        d_valid = torch.empty(max(nd, 1), dtype=torch.uint8, device=self.d_fields.device)
+        room = min(self.length, 32 * nd + 4096) if bytes_capacity is None else int(bytes_capacity)
+        for _ in range(2):
+            res, _, _, d_bytes = self.dev.string_column(self.d_window, self.length, self.d_fields, p, self.d_select, d_offsets=d_off,
+                                                        d_valid=d_valid, capacity=nd, bytes_capacity=room)
+            if res.code != errors.CAPACITY or res.n_rows > nd:
+                break
+            room = int(res.total_bytes)
+        if res.code != 0:
+            raise DocumentStreamError(int(res.code), f"window at {self.base}: the strings of path {p} could not be laid out")
+        return d_off, d_bytes[:int(res.total_bytes)], d_valid[:nd].view(torch.bool)
+
+    def number_column(self, path_or_index, dtype=torch.float64):
+        """The numbers of one path as a column ON THE DEVICE, from the records alone (torch operations, no call): (values
+        dtype[D], valid bool[D]).  torch.int64: valid where the value is an integer (tag 'l'); torch.float64: the doubles
+        (tag 'd') as they are and the integers converted.  A number without bits (MSJ_FIELD_NO_BITS), a value of another
+        kind and a record with a code are not valid; their value is 0."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        if dtype not in (torch.int64, torch.float64):
+            raise ValueError("dtype must be torch.int64 or torch.float64")
+        col = self.d_fields[self.paths.index(path_or_index)]
+        bits, meta = col[:, 0].contiguous(), col[:, 1]
+        tag, flags, code = (meta >> 32) & 0xFF, (meta >> 40) & 0xFF, (meta >> 48) & 0xFFFF
+        has_bits = (code == 0) & ((flags & _lib.FIELD_NO_BITS) == 0)
+        is_int, is_double = has_bits & (tag == ord("l")), has_bits & (tag == ord("d"))
+        if dtype == torch.int64:
+            return torch.where(is_int, bits, torch.zeros_like(bits)), is_int
+        values = torch.where(is_double, bits.view(torch.float64), bits.to(torch.float64))
+        valid = is_int | is_double
+        return torch.where(valid, values, torch.zeros_like(values)), valid
 
     def documents(self):
         """A ``Document`` per complete document, None for one with a verdict code (its code: ``d_doc_tapes`` / ``d_verdicts``).
@@ -181,7 +227,8 @@ class DocumentStream:
     calls that need it run again.
 
     select=[pointers...] (implies validate): every window also carries one ``msj_field`` per pointer and document
-    (``msj_select_documents_device``; ``Window.column`` / ``Window.values``).  The pointers are compiled once, here; the
+    (``msj_select_documents_device``; ``Window.column`` / ``Window.values`` on the host, ``Window.strings`` /
+    ``Window.number_column`` as columns on the device).  The pointers are compiled once, here; the
     number call runs with room for its records, the select call follows the verdict call on the same stream and its
     48-byte result comes back in the same read.  A window with more documents than `documents` records per path grows the
     array and runs only that call again.
@@ -342,7 +389,8 @@ class DocumentStream:
                         sres = self._select_call(d_win, wlen, n, read=True)
                     if sres.code != 0:
                         raise DocumentStreamError(int(sres.code), f"window at {base}: the fields do not fit what the call asked for")
-                    extra.update(d_fields=self._columns[:, :nd], d_window=d_win, paths=self.paths, n_found=int(sres.n_found))
+                    extra.update(d_fields=self._columns[:, :nd], d_window=d_win, paths=self.paths, n_found=int(sres.n_found),
+                                 d_select=self._results[self._sel_at:self._sel_at + 48], dev=dev)
             yield Window(base=base, length=wlen, consumed=consumed, n_tokens=nt, n_documents=nd,
                          utf8_error=bool(carry.utf8_error), d_idx=self._idx[:nt], d_type=d_type[:nt],
                          d_depth=d_depth[:nt], d_doc_first=d_first[:nd], **extra)
