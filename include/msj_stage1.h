@@ -1030,6 +1030,74 @@ int32_t msj_string_column_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t le
 uint64_t msj_string_column_workspace_bytes(uint64_t capacity);
 
 /*
+ * ---- a selected path's arrays as a list column (DERIVED) ----------------------------------------
+ * msj_array_column_device -- for ONE path of msj_select_documents_device, the arrays of every document as a list column:
+ * d_offsets[D + 1], a validity byte per row in d_valid, and the elements back to back in d_elements, each an msj_field.  So a
+ * list<int64 / double> is a strided view of d_elements, a list<string> one msj_string_column_device call over the element
+ * records, and element j of row k is d_elements[d_offsets[k] + j] -- which also covers what an array index at the end of a
+ * pointer would have given (the pointer grammar is unchanged: a numeric segment stays a key).  All on the device, on the
+ * caller's stream, no host round trip.
+ * Inputs: the token arrays, the split (d_doc_first, d_docs) and the number records with their result, exactly those the
+ * select call ran over; d_column = d_fields + p * (the select call's capacity), path p's records; d_select, the device
+ * msj_select_documents_result of that call.  D, T, [f_k, e_k) and clipping are msj_select_documents_device's, read on the
+ * device from d_docs.  d_select cross-checks and is never trusted: d_select->code != 0: d_result is a zero result with that
+ * code and nothing else is written; d_select->n_documents != D (a result of another window): a zero result with code
+ * MSJ_ERR_BAD_ARGUMENT in d_result, nothing else written; D > capacity: MSJ_CAPACITY with n_rows = D, nothing else written.
+ * Row k (k < D) is an array, d_valid[k] = 1, iff all of the following hold, each checked on the arrays and not believed from
+ * the record: the record has code == 0 and type == '['; v = token lies in [f_k, e_k); d_type[v] == '['; m = d_match[v] lies in
+ * (v, e_k).  Anything else gives d_valid[k] = 0 and no elements.
+ * The elements of row k are the tokens i in (v, m) with d_depth[i] == d_depth[v] + 1 (a direct child: everything between
+ * partners is deeper), d_type[i - 1] '[' or ',' (the start of a value, not the comma) and d_type[i] neither ']' nor '}' (the
+ * ']' of a nested [] has '[' in front of it and carries its container's depth), in token order.
+ *   d_offsets    d_offsets[k] = the number of elements of the rows in front of k, d_offsets[D] = n_elements; uint64, capacity
+ *                + 1 entries; those past D are not written
+ *   d_valid      capacity entries; those at or past D are not written
+ *   d_elements   d_elements[d_offsets[k] + j] = the record of the j-th element token i of row k as the select call would write
+ *                it for a value at token i: the same tags, spans, number bits (the record found by token, MSJ_FIELD_NO_BITS
+ *                without one), container partners, code 0.  Records at or past min(n_elements, elements_capacity) are not
+ *                written: with n_elements > elements_capacity the offsets and d_valid are complete, the elements clipped, the
+ *                code MSJ_CAPACITY, and n_elements says what to allocate.  d_elements == NULL (with elements_capacity 0) is the
+ *                layout-only form: offsets, d_valid and n_elements exact, code 0
+ *   d_elements_select  NULL, or a msj_select_documents_result for the element records: code = this call's code, n_documents =
+ *                n_found = n_elements, n_paths = 1, n_no_bits as in d_result.  msj_string_column_device(d_buf, len, d_elements,
+ *                d_elements_select, ...) then runs unchanged on the elements, and refuses a clipped list by its code
+ * d_result: code; n_rows = D; n_arrays the rows with d_valid = 1; n_elements; n_other the rows whose record has code 0 and that
+ * are no array; n_no_bits the element records WRITTEN with MSJ_FIELD_NO_BITS (0 in the layout-only form).  D == 0 writes
+ * d_offsets[0] = 0 and a zero result.
+ * Arguments: d_idx, d_depth, d_match, d_end, d_numbers, d_column, d_elements 16-byte aligned; d_type, d_flags, d_docs,
+ * d_numbers_result, d_select, d_offsets, d_result, d_elements_select 8-byte; d_doc_first 4-byte; d_valid any.  NULL d_result /
+ * d_select / d_docs, a NULL token array with n > 0, NULL d_column / d_offsets / d_valid with capacity > 0, NULL d_elements with
+ * elements_capacity > 0, NULL d_numbers with numbers_capacity > 0, or an off-grid pointer: MSJ_ERR_BAD_ARGUMENT; n >= 2^31:
+ * MSJ_CAPACITY; nothing is launched on either.  Asynchronous on `stream`, workspace in the context.  Safe on ANY arrays and
+ * records: every index from a record, d_match or d_doc_first is checked before it is used, every store to d_elements is checked
+ * against elements_capacity, and rows at or past D are not touched.  For a d_doc_first that is not what the split writes the
+ * outputs are unspecified, still in bounds.
+ * Out of scope: rows other than a select column's (so no list of lists in one step -- a nested array is an element record of
+ * type '['), and any change to the pointer grammar.
+ */
+typedef struct msj_array_column_result {   /* 48 bytes */
+    int32_t  code;        /* 0; MSJ_CAPACITY (rows > capacity: nothing else written; or n_elements > elements_capacity: offsets /
+                             valid complete, elements clipped); d_select->code when that is not 0; MSJ_ERR_BAD_ARGUMENT when
+                             d_select is of another window */
+    uint32_t flags;       /* 0 */
+    uint64_t n_rows;      /* D */
+    uint64_t n_arrays;    /* rows with valid = 1 */
+    uint64_t n_elements;  /* offsets[D]; exact also when clipped and when d_elements == NULL */
+    uint64_t n_other;     /* rows whose record has code 0 and that are no array */
+    uint64_t n_no_bits;   /* element records written with MSJ_FIELD_NO_BITS */
+} msj_array_column_result;
+int32_t msj_array_column_device(msj_ctx *ctx,
+        const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
+        const uint32_t *d_end, const uint8_t *d_flags, const uint32_t *d_doc_first, const msj_documents_result *d_docs,
+        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+        const msj_field *d_column, const msj_select_documents_result *d_select,
+        uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+        msj_field *d_elements, uint64_t elements_capacity,
+        msj_array_column_result *d_result, msj_select_documents_result *d_elements_select, void *stream);
+/* Device workspace of one msj_array_column_device call (the context keeps it): 16 bytes per row, 4 per 1 024 tokens. */
+uint64_t msj_array_column_workspace_bytes(uint64_t n, uint64_t capacity);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

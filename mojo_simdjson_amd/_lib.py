@@ -130,6 +130,13 @@ class MsjStringColumnResult(ctypes.Structure):
                 ("n_escaped", ctypes.c_uint64), ("total_bytes", ctypes.c_uint64), ("n_other", ctypes.c_uint64)]
 
 
+class MsjArrayColumnResult(ctypes.Structure):
+    """``msj_array_column_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_arrays", ctypes.c_uint64),
+                ("n_elements", ctypes.c_uint64), ("n_other", ctypes.c_uint64), ("n_no_bits", ctypes.c_uint64)]
+
+
 FIELD_NO_BITS = 64
 NO_SUCH_FIELD, INCORRECT_TYPE, INVALID_JSON_POINTER = 20, 17, 22
 MAX_PATHS, MAX_PATH_SEGMENTS, MAX_SEGMENT_BYTES = 16, 8, 255
@@ -153,7 +160,7 @@ assert ctypes.sizeof(MsjDocumentVerdict) == 16 and ctypes.sizeof(MsjValidateDocu
 
 assert ctypes.sizeof(MsjDocumentTape) == 32 and ctypes.sizeof(MsjTapeDocumentsResult) == 64
 assert ctypes.sizeof(MsjField) == 16 and ctypes.sizeof(MsjSelectDocumentsResult) == 48
-assert ctypes.sizeof(MsjStringColumnResult) == 48
+assert ctypes.sizeof(MsjStringColumnResult) == 48 and ctypes.sizeof(MsjArrayColumnResult) == 48
 
 _lib = None
 
@@ -295,6 +302,12 @@ def load():
                                              ctypes.c_void_p]
     lib.msj_string_column_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_string_column_workspace_bytes.argtypes = [ctypes.c_uint64]
+    lib.msj_array_column_device.restype = ctypes.c_int32
+    lib.msj_array_column_device.argtypes = [ctypes.c_void_p, u32p, ctypes.c_uint64] + [ctypes.c_void_p] * 8 + \
+        [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_array_column_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_array_column_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

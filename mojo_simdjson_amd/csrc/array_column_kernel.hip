@@ -1,0 +1,321 @@
+// One selected path's arrays as a list column -- msj_array_column_device (include/msj_stage1.h): from the msj_field records
+// msj_select_documents_device wrote for a path, offsets[D + 1], a validity byte per row and one msj_field per element back
+// to back.  The arithmetic -- the row test, the descriptor, the element test, the codes -- is array_column_math.h, host +
+// device and checked on the CPU by tests/test_array_column_math.py; an element's record is select_math.h's value_field.
+// D = d_docs->n_complete and T = d_docs->tokens_complete are read on the device by every kernel, d_select only to be
+// checked against them: the host never learns them.
+//
+// No walk: the arrays of one column lie in document order, so an element's place in the output is the number of element
+// tokens in front of it in the window, and offsets[k] is that number at document k's first token.  Launches, all on the
+// caller's stream, behind a 64-byte memset of the call's counters:
+//   ac_rows   a lane per row: the 16-byte record as one load, the row test, d_valid, and a 16-byte descriptor {v, m, depth of
+//             v's children} to the workspace, so that a candidate token makes one gather; the counts by wave and block, two
+//             atomics per block
+//   ac_count  a block of 1 024 tokens, 4 per lane; the type word as one 4-byte load, the depths as one 16-byte load, one
+//             token of halo in FRONT of the block for the predecessor.  A candidate (behind '[' or ',', no closer) finds its
+//             document as td_emit does (docs_block.h) and tests itself against that document's descriptor.  The block's
+//             element count goes to the workspace; a block without a candidate writes its 0 and ends there
+//   ac_scan   one workgroup of 1 024: the exclusive sum over the blocks' counts in chunks of 1 024, then the result -- the
+//             code, n_elements, the counts --, d_offsets[D] and d_elements_select
+//   ac_emit   the same block shape.  An element's position is the block's prefix + the exclusive sum inside the block; its
+//             record leaves as one 16-byte store when the position is below elements_capacity.  The lane that holds a
+//             document's first token writes d_offsets[k], also in a block that holds no element.  n_no_bits: one atomic per
+//             block that has any
+// Safety: a row's token is used only when it lies in its document; every index from d_match or d_doc_first is checked before
+// it is used; tokens are below T <= n; rows are below D <= capacity; every store to d_elements is checked against
+// elements_capacity.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/msj_stage1.h"
+#include "array_column_math.h"
+#include "docs_block.h"
+#include "launch.h"
+
+namespace msj_acol {
+
+using namespace msj_tdocs;
+using namespace msj::acol;
+
+constexpr int kRowBlocks = 1024;  // most blocks of ac_rows (it loops over what D needs)
+
+static_assert(sizeof(msj_field) == 16 && sizeof(msj_array_column_result) == 48 && sizeof(Desc) == 16, "ABI");
+
+struct ColState {  // cleared by a memset per call
+    unsigned long long n_arrays, n_other;
+    uint64_t reserved[6];
+};
+struct ColWork {
+    ColState *st;
+    Desc *desc;       // per row
+    uint32_t *bsum;   // per block of tokens: its elements, then (ac_scan) the elements in front of the block
+};
+
+__host__ __device__ inline uint64_t most_rows(uint64_t n, uint64_t capacity) { return n < capacity ? n : capacity; }
+__host__ __device__ inline uint64_t token_blocks(uint64_t tokens) { return (tokens + kBlock - 1) / kBlock; }
+static inline ColWork col_layout(void *ws, uint64_t n, uint64_t capacity) {
+    uint8_t *p = static_cast<uint8_t *>(ws);
+    ColWork w;
+    w.st = reinterpret_cast<ColState *>(p);
+    w.desc = reinterpret_cast<Desc *>(p + sizeof(ColState));
+    w.bsum = reinterpret_cast<uint32_t *>(p + sizeof(ColState) + sizeof(Desc) * most_rows(n, capacity));
+    return w;
+}
+
+// what every kernel reads of the window and of d_select.  stop: nothing but the results is written
+struct Head {
+    Window win;
+    uint64_t n_rows;
+    int32_t code;
+    bool stop;
+};
+__device__ __forceinline__ Head load_head(const msj_documents_result *__restrict__ docs, const uint32_t *__restrict__ first, uint64_t n,
+                                          uint64_t capacity, const msj_select_documents_result *__restrict__ sel) {
+    Head h;
+    h.win = load_window(docs, first, n, capacity);
+    h.code = head_code(sel->code, sel->n_documents, h.win, h.n_rows);
+    h.stop = h.code != 0;
+    return h;
+}
+
+__device__ __forceinline__ msj_field load_field(const msj_field *__restrict__ column, uint64_t k) {
+    const uint4 q = *reinterpret_cast<const uint4 *>(column + k);  // (16-byte aligned: checked by the entry point)
+    msj_field f;
+    f.bits = (uint64_t)q.x | ((uint64_t)q.y << 32);
+    f.token = q.z;
+    f.type = (uint8_t)(q.w & 0xFFu), f.flags = (uint8_t)((q.w >> 8) & 0xFFu), f.code = (uint16_t)(q.w >> 16);
+    return f;
+}
+__device__ __forceinline__ void store_field(msj_field *__restrict__ out, uint64_t at, const msj_field &f) {
+    uint4 q;
+    q.x = (uint32_t)f.bits, q.y = (uint32_t)(f.bits >> 32), q.z = f.token;
+    q.w = (uint32_t)f.type | ((uint32_t)f.flags << 8) | ((uint32_t)f.code << 16);
+    *reinterpret_cast<uint4 *>(out + at) = q;
+}
+
+__global__ __launch_bounds__(kThreads) void ac_rows(uint64_t n, const uint8_t *__restrict__ type, const int32_t *__restrict__ depth,
+                                                    const uint32_t *__restrict__ match, const uint32_t *__restrict__ first,
+                                                    const msj_documents_result *__restrict__ docs, const msj_field *__restrict__ column,
+                                                    const msj_select_documents_result *__restrict__ sel, uint64_t capacity, const ColWork w,
+                                                    uint8_t *__restrict__ valid) {
+    __shared__ uint32_t s_arrays[kWaves], s_other[kWaves];
+    const Head h = load_head(docs, first, n, capacity, sel);
+    if (h.stop) return;
+    const uint64_t lanes = (uint64_t)gridDim.x * kThreads;
+    uint32_t n_arrays = 0, n_other = 0;
+    for (uint64_t k = (uint64_t)blockIdx.x * kThreads + threadIdx.x; k < h.win.D; k += lanes) {
+        uint64_t f, e;
+        const bool ok = document_bounds(first, h.win, k, f, e);
+        bool other;
+        const Desc d = row_of(load_field(column, k), ok, f, e, type, depth, match, other);
+        valid[k] = (uint8_t)d.valid;  // (k < D <= capacity)
+        *reinterpret_cast<uint4 *>(w.desc + k) = make_uint4(d.v, d.m, (uint32_t)d.child_depth, d.valid);
+        n_arrays += d.valid, n_other += other;
+    }
+    n_arrays = wave_sum(n_arrays), n_other = wave_sum(n_other);
+    if ((threadIdx.x & 63) == 0) s_arrays[threadIdx.x >> 6] = n_arrays, s_other[threadIdx.x >> 6] = n_other;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int v = 1; v < kWaves; v++) n_arrays += s_arrays[v], n_other += s_other[v];
+    if (n_arrays) atomicAdd(&w.st->n_arrays, (unsigned long long)n_arrays);
+    if (n_other) atomicAdd(&w.st->n_other, (unsigned long long)n_other);
+}
+
+// A lane's four tokens of the block at `base`: types, depths and the candidates among them (bit k: token mine + k)
+struct Lane {
+    uint32_t tw, cand;
+    int32_t dk[kPer];
+};
+// s_type: kThreads words of LDS that nothing else uses (a lane reads its neighbour's word behind the barrier)
+__device__ __forceinline__ Lane load_lane(const Window &win, uint64_t base, const uint8_t *__restrict__ type, const int32_t *__restrict__ depth,
+                                          uint32_t *s_type) {
+    Lane l;
+    const uint64_t mine = base + (uint64_t)threadIdx.x * kPer;
+    // tokens at or past T read as nothing: they belong to the cut document
+    l.tw = load_byte_quad(type, mine, win.T);
+    s_type[threadIdx.x] = l.tw;
+    l.dk[0] = l.dk[1] = l.dk[2] = l.dk[3] = 0;
+    if (mine + kPer <= win.T) {
+        const int4 q = *reinterpret_cast<const int4 *>(depth + mine);
+        l.dk[0] = q.x, l.dk[1] = q.y, l.dk[2] = q.z, l.dk[3] = q.w;
+    } else {
+        for (int k = 0; k < kPer && mine + k < win.T; k++) l.dk[k] = depth[mine + k];
+    }
+    __syncthreads();
+    // the token in front of this lane's first: the lane before's last, or the halo, one token in front of the block
+    uint32_t prev = threadIdx.x > 0 ? s_type[threadIdx.x - 1] >> 24 : (base > 0 ? (uint32_t)type[base - 1] : 0u);  // (base - 1 < T)
+    l.cand = 0;
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const uint64_t i = mine + k;
+        const uint32_t t = (l.tw >> (8 * k)) & 0xFFu;
+        if (in_documents(win, i) && is_candidate(prev, t)) l.cand |= 1u << k;
+        prev = t;
+    }
+    return l;
+}
+// the candidates that are elements of their document's row: one 16-byte gather each
+__device__ __forceinline__ uint32_t elements_of(const Lane &l, const BlockDocs &bd, const Window &win, uint64_t base, const Desc *__restrict__ desc) {
+    const uint64_t mine = base + (uint64_t)threadIdx.x * kPer;
+    uint32_t elem = 0;
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        if (!((l.cand >> k) & 1u)) continue;
+        const uint64_t doc = (uint64_t)bd.k0 + bd.rank[k];  // 1 + the document's number
+        if (doc == 0 || doc > win.D) continue;               // (<= capacity)
+        const uint4 q = *reinterpret_cast<const uint4 *>(desc + (doc - 1));
+        const Desc d{q.x, q.y, (int32_t)q.z, q.w};
+        if (is_element_of(mine + k, l.dk[k], d)) elem |= 1u << k;
+    }
+    return elem;
+}
+
+__global__ __launch_bounds__(kThreads) void ac_count(uint64_t n, const uint8_t *__restrict__ type, const int32_t *__restrict__ depth,
+                                                     const uint32_t *__restrict__ first, const msj_documents_result *__restrict__ docs,
+                                                     const msj_select_documents_result *__restrict__ sel, uint64_t capacity, const ColWork w) {
+    __shared__ uint32_t s_type[kThreads], s_flag[kThreads], s_k[2], s_w32[kWaves];
+    const Head h = load_head(docs, first, n, capacity, sel);
+    const uint64_t base = (uint64_t)blockIdx.x * kBlock;
+    if (h.stop || base >= h.win.T) return;
+    const Lane l = load_lane(h.win, base, type, depth, s_type);
+    if (!__syncthreads_or((int)l.cand)) {  // (the whole block: no value behind '[' or ',' in it)
+        if (threadIdx.x == 0) w.bsum[blockIdx.x] = 0;
+        return;
+    }
+    const BlockDocs bd = block_docs(first, h.win, base, s_flag, s_k, s_w32);
+    const uint32_t elem = elements_of(l, bd, h.win, base, w.desc);
+    uint32_t total;
+    (void)block_scan((uint32_t)__popc(elem), s_w32, total);
+    if (threadIdx.x == 0) w.bsum[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(1024) void ac_scan(uint64_t n, const uint32_t *__restrict__ first, const msj_documents_result *__restrict__ docs,
+                                                const msj_select_documents_result *__restrict__ sel, uint64_t capacity, const ColWork w,
+                                                uint64_t *__restrict__ offsets, bool have_elements, uint64_t elements_capacity,
+                                                msj_array_column_result *__restrict__ result,
+                                                msj_select_documents_result *__restrict__ elements_select) {
+    __shared__ uint64_t s_w[16];
+    const Head h = load_head(docs, first, n, capacity, sel);
+    const uint64_t blocks = h.stop ? 0 : token_blocks(h.win.T);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t run = 0;
+    for (uint64_t v0 = 0; v0 < blocks; v0 += 1024) {
+        const uint64_t v = v0 + threadIdx.x;
+        const uint64_t x = v < blocks ? w.bsum[v] : 0, inc = wave_scan(x);
+        __syncthreads();
+        if (lane == 63) s_w[wave] = inc;
+        __syncthreads();
+        uint64_t before = 0, all = 0;
+#pragma unroll 4
+        for (uint32_t j = 0; j < 16; j++) {
+            const uint64_t t = s_w[j];
+            if (j < wave) before += t;
+            all += t;
+        }
+        if (v < blocks) w.bsum[v] = (uint32_t)(run + before + inc - x);  // (fewer elements than tokens: below 2^31)
+        run += all;
+    }
+    if (threadIdx.x != 0) return;
+    msj_array_column_result r;
+    r.code = h.stop ? h.code : elements_code(run, have_elements, elements_capacity);
+    r.flags = 0;
+    r.n_rows = h.n_rows;
+    r.n_arrays = h.stop ? 0 : w.st->n_arrays;
+    r.n_elements = run;
+    r.n_other = h.stop ? 0 : w.st->n_other;
+    r.n_no_bits = 0;  // (ac_emit's)
+    *result = r;
+    if (!h.stop && offsets) offsets[h.win.D] = run;  // (NULL only with capacity 0: D is 0 then)
+    if (elements_select) {
+        msj_select_documents_result e;
+        e.code = r.code;
+        e.flags = 0;
+        e.n_documents = e.n_found = run;
+        e.n_paths = 1;
+        e.n_no_bits = e.reserved = 0;
+        *elements_select = e;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void ac_emit(const uint32_t *__restrict__ idx, uint64_t n, const uint8_t *__restrict__ type,
+                                                    const int32_t *__restrict__ depth, const uint32_t *__restrict__ match,
+                                                    const uint32_t *__restrict__ end, const uint8_t *__restrict__ flags,
+                                                    const uint32_t *__restrict__ first, const msj_documents_result *__restrict__ docs,
+                                                    const msj_number *__restrict__ numbers, uint64_t numbers_capacity,
+                                                    const msj_numbers_result *__restrict__ nr, const msj_select_documents_result *__restrict__ sel,
+                                                    uint64_t capacity, const ColWork w, uint64_t *__restrict__ offsets,
+                                                    msj_field *__restrict__ elements, uint64_t elements_capacity,
+                                                    msj_array_column_result *__restrict__ result,
+                                                    msj_select_documents_result *__restrict__ elements_select) {
+    __shared__ uint32_t s_type[kThreads], s_flag[kThreads], s_k[2], s_w32[kWaves];
+    const Head h = load_head(docs, first, n, capacity, sel);
+    const uint64_t base = (uint64_t)blockIdx.x * kBlock;
+    if (h.stop || base >= h.win.T) return;
+    const Lane l = load_lane(h.win, base, type, depth, s_type);
+    // (no exit for a block without a candidate: the documents that start in it still need their offsets)
+    const BlockDocs bd = block_docs(first, h.win, base, s_flag, s_k, s_w32);
+    const uint32_t elem = elements_of(l, bd, h.win, base, w.desc);
+    uint32_t total;
+    uint64_t pos = (uint64_t)w.bsum[blockIdx.x] + block_scan((uint32_t)__popc(elem), s_w32, total);
+    uint64_t n_records = 0;
+    if (numbers && nr) n_records = umin64(nr->n_numbers, numbers_capacity);
+    const msj_number *records = n_records ? numbers : nullptr;
+    const uint64_t mine = base + (uint64_t)threadIdx.x * kPer;
+    uint32_t n_nobits = 0;
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        if ((bd.starts >> k) & 1u) {
+            const uint64_t doc = (uint64_t)bd.k0 + bd.rank[k];
+            if (doc >= 1 && doc <= h.win.D) offsets[doc - 1] = pos;  // (D <= capacity; a first token is no element)
+        }
+        if (!((elem >> k) & 1u)) continue;
+        if (elements && pos < elements_capacity) {
+            const msj_field r = value_field<msj_field, msj_number>(mine + k, idx, type, match, end, flags, records, n_records);
+            store_field(elements, pos, r);
+            n_nobits += (r.flags & kFieldNoBits) != 0;
+        }
+        pos++;
+    }
+    if (!elements || !__syncthreads_or((int)n_nobits)) return;
+    n_nobits = wave_sum(n_nobits);  // (s_w32 is free: the scan's reads lie in front of that barrier)
+    if ((threadIdx.x & 63) == 0) s_w32[threadIdx.x >> 6] = n_nobits;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int v = 1; v < kWaves; v++) n_nobits += s_w32[v];
+    atomicAdd(reinterpret_cast<unsigned long long *>(&result->n_no_bits), (unsigned long long)n_nobits);
+    if (elements_select) atomicAdd(reinterpret_cast<unsigned long long *>(&elements_select->n_no_bits), (unsigned long long)n_nobits);
+}
+
+}  // namespace msj_acol
+
+extern "C" uint64_t msj_array_column_workspace_bytes(uint64_t n, uint64_t capacity) {
+    using namespace msj_acol;
+    return sizeof(ColState) + sizeof(Desc) * most_rows(n, capacity) + up16(4 * token_blocks(n)) + 64;
+}
+
+extern "C" int msj_launch_array_column(const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
+                                       const uint32_t *d_end, const uint8_t *d_flags, const uint32_t *d_doc_first,
+                                       const msj_documents_result *d_docs, const msj_number *d_numbers, uint64_t numbers_capacity,
+                                       const msj_numbers_result *d_numbers_result, const msj_field *d_column,
+                                       const msj_select_documents_result *d_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+                                       msj_field *d_elements, uint64_t elements_capacity, msj_array_column_result *d_result,
+                                       msj_select_documents_result *d_elements_select, void *d_ws, void *stream) {
+    using namespace msj_acol;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const ColWork w = col_layout(d_ws, n, capacity);
+    const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(ColState), s);
+    if (cleared != hipSuccess) return (int)cleared;
+    const uint64_t rb = (most_rows(n, capacity) + kThreads - 1) / kThreads;
+    const uint32_t nb = (uint32_t)token_blocks(n);
+    if (rb)
+        hipLaunchKernelGGL(ac_rows, dim3((uint32_t)(rb > (uint64_t)kRowBlocks ? (uint64_t)kRowBlocks : rb)), dim3(kThreads), 0, s, n, d_type, d_depth,
+                           d_match, d_doc_first, d_docs, d_column, d_select, capacity, w, d_valid);
+    if (nb) hipLaunchKernelGGL(ac_count, dim3(nb), dim3(kThreads), 0, s, n, d_type, d_depth, d_doc_first, d_docs, d_select, capacity, w);
+    hipLaunchKernelGGL(ac_scan, dim3(1), dim3(1024), 0, s, n, d_doc_first, d_docs, d_select, capacity, w, d_offsets, d_elements != nullptr,
+                       elements_capacity, d_result, d_elements_select);
+    if (nb)
+        hipLaunchKernelGGL(ac_emit, dim3(nb), dim3(kThreads), 0, s, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs,
+                           d_numbers, numbers_capacity, d_numbers_result, d_select, capacity, w, d_offsets, d_elements, elements_capacity, d_result,
+                           d_elements_select);
+    return (int)hipGetLastError();
+}

@@ -110,6 +110,7 @@ struct msj_ctx {
     DeviceBuffer tdoc_ws;         // msj_tape_documents_device: the same for a window, and 8 bytes per document
     DeviceBuffer sel_ws;          // msj_select_documents_device: two state words per (path, document)
     DeviceBuffer scol_ws;         // msj_string_column_device: the counts, a sum per block of rows, a length per row
+    DeviceBuffer acol_ws;         // msj_array_column_device: the counts, a descriptor per row, a count per block of tokens
 };
 
 // ---- api.cpp ----

@@ -1,5 +1,5 @@
 // launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 / f2 /
-// f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip, validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip.  Every
+// f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip, validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip, array_column_kernel.hip.  Every
 // launcher and every internal workspace size is declared here and nowhere else; the file that defines one and the file
 // that calls it both include this header, so the compiler compares the two signatures (C linkage alone would not).
 // (stage 1 has stage1_kernel.h; the exported *_workspace_bytes are declared in include/msj_stage1.h.)
@@ -113,3 +113,12 @@ extern "C" int msj_launch_select_documents(const void *d_paths, uint32_t n_paths
 extern "C" int msj_launch_string_column(const uint8_t *d_buf, uint64_t len, const msj_field *d_column, const msj_select_documents_result *d_select,
                                         uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity, uint8_t *d_bytes, uint64_t bytes_capacity,
                                         msj_string_column_result *d_result, void *d_ws, void *stream);
+
+// ---- array_column_kernel.hip ----
+extern "C" int msj_launch_array_column(const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
+                                       const uint32_t *d_end, const uint8_t *d_flags, const uint32_t *d_doc_first,
+                                       const msj_documents_result *d_docs, const msj_number *d_numbers, uint64_t numbers_capacity,
+                                       const msj_numbers_result *d_numbers_result, const msj_field *d_column,
+                                       const msj_select_documents_result *d_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+                                       msj_field *d_elements, uint64_t elements_capacity, msj_array_column_result *d_result,
+                                       msj_select_documents_result *d_elements_select, void *d_ws, void *stream);

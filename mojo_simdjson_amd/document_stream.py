@@ -66,6 +66,78 @@ def field_value(rec, data, idx, end):
     raise ValueError(f"not a tape tag: {t}")
 
 
+def number_column(col, dtype=torch.float64):
+    """The numbers among ``msj_field`` records (int64 of shape (rows, 2)) as a column ON THE DEVICE, from the records alone
+    (torch operations, no call): (values dtype[rows], valid bool[rows]).  torch.int64: valid where the value is an integer
+    (tag 'l'); torch.float64: the doubles (tag 'd') as they are and the integers converted.  A number without bits
+    (MSJ_FIELD_NO_BITS), a value of another kind and a record with a code are not valid; their value is 0."""
+    if dtype not in (torch.int64, torch.float64):
+        raise ValueError("dtype must be torch.int64 or torch.float64")
+    bits, meta = col[:, 0].contiguous(), col[:, 1]
+    tag, flags, code = (meta >> 32) & 0xFF, (meta >> 40) & 0xFF, (meta >> 48) & 0xFFFF
+    has_bits = (code == 0) & ((flags & _lib.FIELD_NO_BITS) == 0)
+    is_int, is_double = has_bits & (tag == ord("l")), has_bits & (tag == ord("d"))
+    if dtype == torch.int64:
+        return torch.where(is_int, bits, torch.zeros_like(bits)), is_int
+    values = torch.where(is_double, bits.view(torch.float64), bits.to(torch.float64))
+    valid = is_int | is_double
+    return torch.where(valid, values, torch.zeros_like(values)), valid
+
+
+def _string_column(dev, d_window, length, d_fields, p, d_select, rows, bytes_capacity, what):
+    """``string_column`` over `rows` records with a byte buffer that starts from a guess and, when the call says it was too
+    small, is made as large as the call asks once -> (offsets int64[rows + 1], bytes uint8[total], valid bool[rows])"""
+    d_off = torch.empty(rows + 1, dtype=torch.int64, device=d_fields.device)
+    d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=d_fields.device)
+    room = min(length, 32 * rows + 4096) if bytes_capacity is None else int(bytes_capacity)
+    for _ in range(2):
+        res, _, _, d_bytes = dev.string_column(d_window, length, d_fields, p, d_select, d_offsets=d_off, d_valid=d_valid, capacity=rows,
+                                               bytes_capacity=room)
+        if res.code != errors.CAPACITY or res.n_rows > rows:
+            break
+        room = int(res.total_bytes)
+    if res.code != 0:
+        raise DocumentStreamError(int(res.code), f"{what} could not be laid out")
+    return d_off, d_bytes[:int(res.total_bytes)], d_valid[:rows].view(torch.bool)
+
+
+class ListColumn:
+    """One path's arrays as a list column ON THE DEVICE (``Window.elements``).  offsets int64[D + 1]; fields int64[n_elements,
+    2], one ``msj_field`` per element back to back -- row k's elements are fields[offsets[k]:offsets[k + 1]]; valid bool[D],
+    False where the value is no array, the key is missing or the document has a verdict code (the row is empty then);
+    d_select uint8[48], the ``msj_select_documents_result`` of the element records.  Like every array a Window carries, the
+    window's own arrays are reused by the next window: use the column before the iterator advances."""
+
+    def __init__(self, window, offsets, fields, valid, d_select):
+        self.window, self.offsets, self.fields, self.valid, self.d_select = window, offsets, fields, valid, d_select
+
+    @property
+    def n_elements(self):
+        return self.fields.shape[0]
+
+    def numbers(self, dtype=torch.float64):
+        """The elements that are numbers, as ``Window.number_column`` gives them: (values dtype[n_elements], valid
+        bool[n_elements])."""
+        return number_column(self.fields, dtype)
+
+    def strings(self, bytes_capacity=None):
+        """The elements that are strings as a column on the device (``msj_string_column_device`` over the element records):
+        (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements])."""
+        w = self.window
+        d_fields = self.fields if self.n_elements else torch.zeros((1, 2), dtype=torch.int64, device=self.fields.device)
+        return _string_column(w.dev, w.d_window, w.length, d_fields.unsqueeze(0), 0, self.d_select, self.n_elements, bytes_capacity,
+                              f"window at {w.base}: the strings of the elements")
+
+    def to_python(self):
+        """A list per row, None where the row is no array; the elements as ``field_value`` gives them.  The element records
+        come to the host, and the window's bytes, d_idx and d_end once per window."""
+        w = self.window
+        off, ok = self.offsets.cpu().tolist(), self.valid.cpu().tolist()
+        recs = np.ascontiguousarray(self.fields.cpu().numpy()).view(FIELD_DTYPE).reshape(-1)
+        host = w._host_arrays()
+        return [[field_value(r, *host) for r in recs[off[k]:off[k + 1]]] if ok[k] else None for k in range(len(ok))]
+
+
 def _skip_flag(n):
     return (n & 15) << 24
 
@@ -107,6 +179,9 @@ class Window:
     paths: object = None               # the compiled paths (Stage1Device.compile_paths)
     n_found: int = None                # records with code 0, over all paths
     d_select: torch.Tensor = None      # uint8[48]: the select call's msj_select_documents_result, where it lies on the device
+    d_docs: torch.Tensor = None        # uint8[32]: the split's msj_documents_result, where it lies on the device
+    d_numbers: torch.Tensor = None     # int64[records, 2]: the number call's msj_number records over the window
+    d_numbers_result: torch.Tensor = None  # uint8[32]: its msj_numbers_result, where it lies on the device
     dev: object = field(default=None, repr=False, compare=False)  # the Stage1Device whose call strings() runs
     _documents: list = field(default=None, repr=False, compare=False)  # what documents() built: host copies, kept
     _host: tuple = field(default=None, repr=False, compare=False)      # what values() reads: host copies, kept
@@ -124,9 +199,13 @@ class Window:
         NO_SUCH_FIELD, 17 INCORRECT_TYPE, an invalid document's), see ``field_value``.  The window's bytes, d_idx and d_end
         come to the host once per window."""
         col = self.column(path_or_index)
+        host = self._host_arrays()
+        return [field_value(r, *host) for r in col]
+
+    def _host_arrays(self):
         if self._host is None:
             self._host = (self.d_window.cpu().numpy(), self.d_idx.cpu().numpy().view(np.uint32), self.d_end.cpu().numpy().view(np.uint32))
-        return [field_value(r, *self._host) for r in col]
+        return self._host
 
     def strings(self, path_or_index, bytes_capacity=None):
         """The string values of one path as a column ON THE DEVICE (``msj_string_column_device``): (offsets int64[D + 1],
@@ -138,19 +217,36 @@ class Window:
         if self.d_fields is None:
             raise ValueError("no fields: the stream was not created with select=[...]")
         p = self.paths.index(path_or_index)
-        nd = self.n_documents
-        d_off = torch.empty(nd + 1, dtype=torch.int64, device=self.d_fields.device)
-        d_valid = torch.empty(max(nd, 1), dtype=torch.uint8, device=self.d_fields.device)
-        room = min(self.length, 32 * nd + 4096) if bytes_capacity is None else int(bytes_capacity)
+        return _string_column(self.dev, self.d_window, self.length, self.d_fields, p, self.d_select, self.n_documents, bytes_capacity,
+                              f"window at {self.base}: the strings of path {p}")
+
+    def elements(self, path_or_index, elements_capacity=None):
+        """The arrays of one path as a list column ON THE DEVICE (``msj_array_column_device``) -> ``ListColumn``: offsets
+        int64[D + 1], one ``msj_field`` per element back to back, valid bool[D].  The call runs on the window's arrays and
+        records where they lie; only its 48-byte result comes to the host.  The element buffer starts from a guess
+        (elements_capacity: the caller's) and, when the call says it was too small, is made as large as the call asks and the
+        call runs once more."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        p = self.paths.index(path_or_index)
+        nd, nt = self.n_documents, self.n_tokens
+        dvc = self.d_fields.device
+        d_off = torch.empty(nd + 1, dtype=torch.int64, device=dvc)
+        d_valid = torch.empty(max(nd, 1), dtype=torch.uint8, device=dvc)
+        d_esel = torch.zeros(48, dtype=torch.uint8, device=dvc)
+        room = min(nt, 4 * nd + 4096) if elements_capacity is None else int(elements_capacity)
         for _ in range(2):
-            res, _, _, d_bytes = self.dev.string_column(self.d_window, self.length, self.d_fields, p, self.d_select, d_offsets=d_off,
-                                                        d_valid=d_valid, capacity=nd, bytes_capacity=room)
+            res, _, _, d_elements, _ = self.dev.array_column(
+                self.d_idx, nt, self.d_type, self.d_depth, self.d_match, self.d_end, self.d_flags, self.d_doc_first, self.d_docs,
+                self.d_fields, p, self.d_select, d_numbers=self.d_numbers, numbers_capacity=self.d_numbers.shape[0],
+                d_numbers_result=self.d_numbers_result, d_offsets=d_off, d_valid=d_valid, capacity=nd, elements_capacity=room,
+                d_elements_select=d_esel)
             if res.code != errors.CAPACITY or res.n_rows > nd:
                 break
-            room = int(res.total_bytes)
+            room = int(res.n_elements)
         if res.code != 0:
-            raise DocumentStreamError(int(res.code), f"window at {self.base}: the strings of path {p} could not be laid out")
-        return d_off, d_bytes[:int(res.total_bytes)], d_valid[:nd].view(torch.bool)
+            raise DocumentStreamError(int(res.code), f"window at {self.base}: the arrays of path {p} could not be laid out")
+        return ListColumn(self, d_off, d_elements[:int(res.n_elements)], d_valid[:nd].view(torch.bool), d_esel)
 
     def number_column(self, path_or_index, dtype=torch.float64):
         """The numbers of one path as a column ON THE DEVICE, from the records alone (torch operations, no call): (values
@@ -161,16 +257,7 @@ class Window:
             raise ValueError("no fields: the stream was not created with select=[...]")
         if dtype not in (torch.int64, torch.float64):
             raise ValueError("dtype must be torch.int64 or torch.float64")
-        col = self.d_fields[self.paths.index(path_or_index)]
-        bits, meta = col[:, 0].contiguous(), col[:, 1]
-        tag, flags, code = (meta >> 32) & 0xFF, (meta >> 40) & 0xFF, (meta >> 48) & 0xFFFF
-        has_bits = (code == 0) & ((flags & _lib.FIELD_NO_BITS) == 0)
-        is_int, is_double = has_bits & (tag == ord("l")), has_bits & (tag == ord("d"))
-        if dtype == torch.int64:
-            return torch.where(is_int, bits, torch.zeros_like(bits)), is_int
-        values = torch.where(is_double, bits.view(torch.float64), bits.to(torch.float64))
-        valid = is_int | is_double
-        return torch.where(valid, values, torch.zeros_like(values)), valid
+        return number_column(self.d_fields[self.paths.index(path_or_index)], dtype)
 
     def documents(self):
         """A ``Document`` per complete document, None for one with a verdict code (its code: ``d_doc_tapes`` / ``d_verdicts``).
@@ -228,7 +315,7 @@ class DocumentStream:
 
     select=[pointers...] (implies validate): every window also carries one ``msj_field`` per pointer and document
     (``msj_select_documents_device``; ``Window.column`` / ``Window.values`` on the host, ``Window.strings`` /
-    ``Window.number_column`` as columns on the device).  The pointers are compiled once, here; the
+    ``Window.number_column`` / ``Window.elements`` as columns on the device).  The pointers are compiled once, here; the
     number call runs with room for its records, the select call follows the verdict call on the same stream and its
     48-byte result comes back in the same read.  A window with more documents than `documents` records per path grows the
     array and runs only that call again.
@@ -390,7 +477,8 @@ class DocumentStream:
                     if sres.code != 0:
                         raise DocumentStreamError(int(sres.code), f"window at {base}: the fields do not fit what the call asked for")
                     extra.update(d_fields=self._columns[:, :nd], d_window=d_win, paths=self.paths, n_found=int(sres.n_found),
-                                 d_select=self._results[self._sel_at:self._sel_at + 48], dev=dev)
+                                 d_select=self._results[self._sel_at:self._sel_at + 48], dev=dev, d_docs=self._results[32:64],
+                                 d_numbers=self._numbers, d_numbers_result=self._results[64:96])
             yield Window(base=base, length=wlen, consumed=consumed, n_tokens=nt, n_documents=nd,
                          utf8_error=bool(carry.utf8_error), d_idx=self._idx[:nt], d_type=d_type[:nt],
                          d_depth=d_depth[:nt], d_doc_first=d_first[:nd], **extra)
