@@ -1098,6 +1098,62 @@ int32_t msj_array_column_device(msj_ctx *ctx,
 uint64_t msj_array_column_workspace_bytes(uint64_t n, uint64_t capacity);
 
 /*
+ * ---- fields by path inside the elements of a list column (DERIVED) ------------------------------
+ * msj_select_elements_device -- msj_select_documents_device with ELEMENTS as the rows instead of documents: for up to 16
+ * paths and every element record of an array column, one msj_field per (path, row), path-major.  For "items":[{"sku":..,
+ * "qty":..,"dims":{"w":..}}, ...] the paths /sku, /qty and /dims/w are columns on the device, aligned with the list
+ * column's d_offsets: a list of structs.  Everything downstream composes as it does for a document column: a numeric column
+ * is a strided view of d_fields, a string column one msj_string_column_device call, a nested array one more
+ * msj_array_column_device-style record of type '['.  The pointer grammar is unchanged (msj_paths_create; no '*', no indices).
+ * Inputs: the window, the token arrays and the number records with their result, exactly those the array-column call ran
+ * over; d_rows = that call's d_elements, d_rows_select = its d_elements_select.  R = d_rows_select->n_documents is read on
+ * the device.  The window's n stands where a document's e_k stood.
+ *   d_rows_select->code != 0 (a clipped element list arrives this way): d_result is a zero result with that code and nothing
+ *                else is written
+ *   R > capacity: MSJ_CAPACITY with n_documents = R (n_paths kept), no record written
+ *   order:       the records' `token` fields must ascend strictly over r = 0 .. R-1, compared as uint32 (array-column output
+ *                always does).  Checked on the device, not believed: on a violation code = MSJ_ERR_BAD_ARGUMENT, n_documents = R
+ *                (n_paths kept), no record written
+ * Row r is USABLE iff all of the following hold, each re-checked on the arrays: its record has code == 0 and type == '{'; v =
+ * token < n; d_type[v] == '{'; m = d_match[v] lies in (v, n).
+ * Lookup of path p (segments s_0 .. s_(L-1)) in row r:
+ *   the record has a code != 0: that code is copied (an array-column record never has one)
+ *   L == 0 and v < n: the record is that of the value at token v, re-derived from the arrays (the row's own value)
+ *   otherwise a row that is not usable: code 17 (INCORRECT_TYPE)
+ *   otherwise the loop of msj_select_documents_device from lo = v, with n in the place of e_k: the members of the object lo
+ *   are the tokens i in (lo, d_match[lo]) with d_type[i] == '"', d_depth[i] == d_depth[lo] + 1 and d_type[i + 1] == ':' -- the
+ *   depth is that of the OBJECT, rows sit at whatever depth their array does -- the SMALLEST i whose unescaped body equals
+ *   s_l wins, none: code 20 (NO_SUCH_FIELD); the value is token i + 2, which before the last segment must be a '{' with its
+ *   partner in (i + 2, n), else code 17
+ * Which row a key can belong to: key token i belongs to the LAST row r with token_r < i, and is a member for that row alone.
+ * For true element records that is the enclosing element (siblings are disjoint and ascending); for any other records --
+ * one row inside another, say -- it makes the output a function of the input: row r sees the keys i <= token_(r+1) only.
+ * The key compare, the unescape, the raw-length rule, the number-record search and MSJ_FIELD_NO_BITS are
+ * msj_select_documents_device's, unchanged.
+ * d_fields[p * capacity + r] for r < R; records at or past R are not written.  d_result: a msj_select_documents_result with
+ * code, n_documents = R, n_paths, n_found, n_no_bits -- so msj_string_column_device(d_buf, len, d_fields + p * capacity,
+ * d_result, ...) runs unchanged on any of the new columns.  R == 0 and n == 0 need no special case: with n == 0 no row is
+ * usable.
+ * Arguments: d_idx, d_depth, d_match, d_end, d_numbers, d_rows, d_fields 16-byte aligned; d_type, d_flags, d_numbers_result,
+ * d_rows_select, d_result 8-byte.  NULL ctx / paths / d_result / d_rows_select, paths of another device, d_result ==
+ * d_rows_select, a NULL window or token array with n > 0, NULL d_rows / d_fields with capacity > 0, NULL d_numbers with
+ * numbers_capacity > 0, or an off-grid pointer: MSJ_ERR_BAD_ARGUMENT; n >= 2^31 or len > MSJ_MAX_SEGMENT_BYTES: MSJ_CAPACITY;
+ * nothing is launched on either.  Asynchronous on `stream`, no host round trip, workspace in the context.  Safe on ANY arrays
+ * and records: every index from a record, d_match or d_end is checked before it is used, the window is read only inside
+ * [0, len), and rows at or past R are not touched.
+ * Out of scope: a list of lists in one step, rows other than ascending element records, any change to the pointer grammar.
+ */
+int32_t msj_select_elements_device(msj_ctx *ctx, const msj_paths *paths,
+        const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+        const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
+        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+        const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
+        msj_field *d_fields, uint64_t capacity, msj_select_documents_result *d_result, void *stream);
+/* Device workspace of one msj_select_elements_device call (the context keeps it): two state words per (path, row) and 4 bytes
+ * per row, for min(n, capacity) rows. */
+uint64_t msj_select_elements_workspace_bytes(uint64_t n, uint64_t capacity, uint32_t n_paths);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

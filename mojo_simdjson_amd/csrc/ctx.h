@@ -111,6 +111,7 @@ struct msj_ctx {
     DeviceBuffer sel_ws;          // msj_select_documents_device: two state words per (path, document)
     DeviceBuffer scol_ws;         // msj_string_column_device: the counts, a sum per block of rows, a length per row
     DeviceBuffer acol_ws;         // msj_array_column_device: the counts, a descriptor per row, a count per block of tokens
+    DeviceBuffer selem_ws;        // msj_select_elements_device: two state words per (path, row), a start token per row
 };
 
 // ---- api.cpp ----

@@ -1,5 +1,5 @@
 // launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 / f2 /
-// f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip, validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip, array_column_kernel.hip.  Every
+// f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip, validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip, array_column_kernel.hip, select_elements_kernel.hip.  Every
 // launcher and every internal workspace size is declared here and nowhere else; the file that defines one and the file
 // that calls it both include this header, so the compiler compares the two signatures (C linkage alone would not).
 // (stage 1 has stage1_kernel.h; the exported *_workspace_bytes are declared in include/msj_stage1.h.)
@@ -122,3 +122,12 @@ extern "C" int msj_launch_array_column(const uint32_t *d_idx, uint64_t n, const 
                                        const msj_select_documents_result *d_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
                                        msj_field *d_elements, uint64_t elements_capacity, msj_array_column_result *d_result,
                                        msj_select_documents_result *d_elements_select, void *d_ws, void *stream);
+
+// ---- select_elements_kernel.hip ----
+// d_paths / n_paths / max_levels as for msj_launch_select_documents; d_rows / d_rows_select: the element records of an array column
+extern "C" int msj_launch_select_elements(const void *d_paths, uint32_t n_paths, uint32_t max_levels, const uint8_t *d_buf, uint64_t len,
+                                          const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth,
+                                          const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags, const msj_number *d_numbers,
+                                          uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result, const msj_field *d_rows,
+                                          const msj_select_documents_result *d_rows_select, msj_field *d_fields, uint64_t capacity,
+                                          msj_select_documents_result *d_result, void *d_ws, void *stream);

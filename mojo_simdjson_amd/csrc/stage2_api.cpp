@@ -1,5 +1,5 @@
 // stage2_api.cpp -- extern "C" entry points of everything that runs behind stage 1 (include/msj_stage1.h): tokens, spans,
-// the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a window), fields by path, a path's strings as a column and its arrays as a list column.  Every call is the same few steps: check
+// the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list elements.  Every call is the same few steps: check
 // the arguments (the order of the checks is part of the ABI: callers see which error wins), select the device, grow the
 // call's workspace, launch.
 #include <new>
@@ -406,6 +406,26 @@ int32_t msj_array_column_device(msj_ctx *ctx, const uint32_t *d_idx, uint64_t n,
     return launched(msj_launch_array_column(d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_numbers, numbers_capacity,
                                             d_numbers_result, d_column, d_select, d_offsets, d_valid, capacity, d_elements, elements_capacity,
                                             d_result, d_elements_select, ctx->acol_ws.p, stream));
+}
+
+int32_t msj_select_elements_device(msj_ctx *ctx, const msj_paths *paths, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
+                                   const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end,
+                                   const uint8_t *d_flags, const msj_number *d_numbers, uint64_t numbers_capacity,
+                                   const msj_numbers_result *d_numbers_result, const msj_field *d_rows,
+                                   const msj_select_documents_result *d_rows_select, msj_field *d_fields, uint64_t capacity,
+                                   msj_select_documents_result *d_result, void *stream) {
+    if (!ctx || !paths || paths->device != ctx->device || !d_result || !d_rows_select || d_result == d_rows_select) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((capacity > 0 && (!d_rows || !d_fields)) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(len, n)) return MSJ_CAPACITY;
+    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers, d_rows, d_fields) ||
+        !all_aligned(8, d_type, d_flags, d_numbers_result, d_rows_select, d_result))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->selem_ws, msj_select_elements_workspace_bytes(n, capacity, paths->n_paths));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_select_elements(paths->blob.p, paths->n_paths, paths->max_levels, d_buf, len, d_idx, n, d_type, d_depth, d_match,
+                                               d_end, d_flags, d_numbers, numbers_capacity, d_numbers_result, d_rows, d_rows_select, d_fields,
+                                               capacity, d_result, ctx->selem_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

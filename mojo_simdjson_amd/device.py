@@ -598,6 +598,37 @@ class Stage1Device:
         call(d_elements, elements_capacity)
         return (read() if sync else d_result), d_offsets, d_valid, d_elements, d_elements_select
 
+    def select_elements(self, paths, d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_rows, d_rows_select,
+                        d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_fields=None, capacity=None, d_result=None,
+                        sync=True):
+        """Fields by path inside the elements of a list column (``msj_select_elements_device``): one 16-byte ``msj_field``
+        per (path, element), path-major, aligned with the list column's offsets.  paths: from ``compile_paths``; the window,
+        the token arrays and the number records with their result: those ``array_column`` ran over; d_rows: its d_elements,
+        int64 of shape (rows, 2); d_rows_select: its d_elements_select, read on the device.  d_fields: int64 tensor of shape
+        (n_paths, capacity, 2) as for ``select_documents`` -- default one row per record of d_rows.  Returns
+        (``MsjSelectDocumentsResult``, d_fields) -- blocking for the 48-byte result; with sync=False the device tensor that
+        holds it, nothing waited for.  That tensor is what ``string_column`` takes as d_select_result for any of the columns."""
+        if d_rows.stride(-1) != 1 or (d_rows.shape[0] > 1 and d_rows.stride(0) != 2):
+            raise ValueError("the element records must be contiguous")
+        n, length, numbers_capacity = int(n), int(length), int(numbers_capacity)
+        if d_fields is None:
+            capacity = d_rows.shape[0] if capacity is None else int(capacity)
+            d_fields = torch.empty((paths.n_paths, max(capacity, 1), 2), dtype=torch.int64, device=self.device)
+        elif capacity is None:
+            capacity = d_fields.shape[1]
+        if d_result is None:
+            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        rc = self.lib.msj_select_elements_device(
+            self.ctx, paths.handle, _ptr(d_buf), length, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
+            _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
+            _ptr(d_numbers_result) if d_numbers_result is not None else None, _ptr(d_rows), _ptr(d_rows_select), _ptr(d_fields),
+            int(capacity), _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_select_elements_device failed: {rc}")
+        if not sync:
+            return d_result, d_fields
+        return _lib.MsjSelectDocumentsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()), d_fields
+
     def parse_document(self, d_buf, length, max_depth=100, exact_strings=False):
         """The whole chain for one document in a device buffer: stage 1, ``stage2_prep`` with partners, ``number_values``,
         ``validate`` and ``tape`` enqueued on one stream.  Returns stage 1's code if that is not 0, else

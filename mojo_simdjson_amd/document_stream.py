@@ -137,6 +137,71 @@ class ListColumn:
         host = w._host_arrays()
         return [[field_value(r, *host) for r in recs[off[k]:off[k + 1]]] if ok[k] else None for k in range(len(ok))]
 
+    def select(self, pointers_or_paths):
+        """Fields by path inside the elements -- ``items[*].sku`` -- ON THE DEVICE (``msj_select_elements_device``) ->
+        ``ElementFields``: one ``msj_field`` per (path, element), each path a column aligned with this column's offsets.
+        pointers_or_paths: JSON pointers (object keys only, "" the element itself) or what ``compile_paths`` made of them.
+        The call runs on the window's arrays and the element records where they lie; only its 48-byte result comes to the
+        host."""
+        w = self.window
+        paths = pointers_or_paths if hasattr(pointers_or_paths, "handle") else w.dev.compile_paths(list(pointers_or_paths))
+        d_rows = self.fields if self.n_elements else torch.zeros((1, 2), dtype=torch.int64, device=self.fields.device)
+        res, d_fields = w.dev.select_elements(
+            paths, w.d_window, w.length, w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_rows, self.d_select,
+            d_numbers=w.d_numbers, numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, capacity=self.n_elements,
+            sync=False)
+        code = int(res[:4].view(torch.int32).item())
+        if code != 0:
+            raise DocumentStreamError(code, f"window at {w.base}: the fields of the elements could not be selected")
+        return ElementFields(self, paths, d_fields[:, :self.n_elements], res)
+
+
+class ElementFields:
+    """Fields by path inside the elements of a ``ListColumn`` ON THE DEVICE (``ListColumn.select``).  fields int64[n_paths,
+    n_elements, 2], one ``msj_field`` per (path, element): element j of row k of the list column is fields[p, offsets[k] + j],
+    so every path is a column of a list of structs.  d_select uint8[48], the call's ``msj_select_documents_result``; paths,
+    the compiled paths; column, the list column the rows came from."""
+
+    def __init__(self, column, paths, fields, d_select):
+        self.list_column, self.paths, self.fields, self.d_select = column, paths, fields, d_select
+
+    @property
+    def n_elements(self):
+        return self.fields.shape[1]
+
+    def column(self, path_or_index):
+        """The records of one path as a numpy structured array (FIELD_DTYPE), one per element: one host copy."""
+        p = self.paths.index(path_or_index)
+        return np.ascontiguousarray(self.fields[p].cpu().numpy()).view(FIELD_DTYPE).reshape(-1)
+
+    def numbers(self, path_or_index, dtype=torch.float64):
+        """The numbers of one path as ``number_column`` gives them: (values dtype[n_elements], valid bool[n_elements])."""
+        return number_column(self.fields[self.paths.index(path_or_index)], dtype)
+
+    def strings(self, path_or_index, bytes_capacity=None):
+        """The strings of one path as a column on the device (``msj_string_column_device`` over the path's records):
+        (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements])."""
+        w, p = self.list_column.window, self.paths.index(path_or_index)
+        d_fields = self.fields if self.n_elements else torch.zeros((self.fields.shape[0], 1, 2), dtype=torch.int64, device=self.fields.device)
+        return _string_column(w.dev, w.d_window, w.length, d_fields, p, self.d_select, self.n_elements, bytes_capacity,
+                              f"window at {w.base}: the strings of path {p} of the elements")
+
+    def values(self, path_or_index):
+        """The values of one path as a Python list, one per element: None where the record has a code, see ``field_value``."""
+        host = self.list_column.window._host_arrays()
+        return [field_value(r, *host) for r in self.column(path_or_index)]
+
+    def to_python(self):
+        """A list per row of the list column, None where the row is no array; per element a dict {pointer: value} over the
+        fields that were found (code 0).  The records come to the host, and the window's bytes, d_idx and d_end once per
+        window."""
+        col = self.list_column
+        off, ok = col.offsets.cpu().tolist(), col.valid.cpu().tolist()
+        host = col.window._host_arrays()
+        cols = [(pointer, self.column(p)) for p, pointer in enumerate(self.paths.pointers)]
+        struct_of = lambda j: {pointer: field_value(c[j], *host) for pointer, c in cols if c[j]["code"] == 0}
+        return [[struct_of(j) for j in range(off[k], off[k + 1])] if ok[k] else None for k in range(len(ok))]
+
 
 def _skip_flag(n):
     return (n & 15) << 24
