@@ -37,12 +37,10 @@ namespace msj_acol {
 using namespace msj_tdocs;
 using namespace msj::acol;
 
-constexpr int kRowBlocks = 1024;  // most blocks of ac_rows (it loops over what D needs)
-
 static_assert(sizeof(msj_field) == 16 && sizeof(msj_array_column_result) == 48 && sizeof(Desc) == 16, "ABI");
 
 struct ColState {  // cleared by a memset per call
-    unsigned long long n_arrays, n_other;
+    uint64_t n_arrays, n_other;
     uint64_t reserved[6];
 };
 struct ColWork {
@@ -78,21 +76,6 @@ __device__ __forceinline__ Head load_head(const msj_documents_result *__restrict
     return h;
 }
 
-__device__ __forceinline__ msj_field load_field(const msj_field *__restrict__ column, uint64_t k) {
-    const uint4 q = *reinterpret_cast<const uint4 *>(column + k);  // (16-byte aligned: checked by the entry point)
-    msj_field f;
-    f.bits = (uint64_t)q.x | ((uint64_t)q.y << 32);
-    f.token = q.z;
-    f.type = (uint8_t)(q.w & 0xFFu), f.flags = (uint8_t)((q.w >> 8) & 0xFFu), f.code = (uint16_t)(q.w >> 16);
-    return f;
-}
-__device__ __forceinline__ void store_field(msj_field *__restrict__ out, uint64_t at, const msj_field &f) {
-    uint4 q;
-    q.x = (uint32_t)f.bits, q.y = (uint32_t)(f.bits >> 32), q.z = f.token;
-    q.w = (uint32_t)f.type | ((uint32_t)f.flags << 8) | ((uint32_t)f.code << 16);
-    *reinterpret_cast<uint4 *>(out + at) = q;
-}
-
 __global__ __launch_bounds__(kThreads) void ac_rows(uint64_t n, const uint8_t *__restrict__ type, const int32_t *__restrict__ depth,
                                                     const uint32_t *__restrict__ match, const uint32_t *__restrict__ first,
                                                     const msj_documents_result *__restrict__ docs, const msj_field *__restrict__ column,
@@ -112,35 +95,22 @@ __global__ __launch_bounds__(kThreads) void ac_rows(uint64_t n, const uint8_t *_
         *reinterpret_cast<uint4 *>(w.desc + k) = make_uint4(d.v, d.m, (uint32_t)d.child_depth, d.valid);
         n_arrays += d.valid, n_other += other;
     }
-    n_arrays = wave_sum(n_arrays), n_other = wave_sum(n_other);
-    if ((threadIdx.x & 63) == 0) s_arrays[threadIdx.x >> 6] = n_arrays, s_other[threadIdx.x >> 6] = n_other;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int v = 1; v < kWaves; v++) n_arrays += s_arrays[v], n_other += s_other[v];
-    if (n_arrays) atomicAdd(&w.st->n_arrays, (unsigned long long)n_arrays);
-    if (n_other) atomicAdd(&w.st->n_other, (unsigned long long)n_other);
+    (void)block_counter_add(n_arrays, s_arrays, &w.st->n_arrays);
+    (void)block_counter_add(n_other, s_other, &w.st->n_other);
 }
 
 // A lane's four tokens of the block at `base`: types, depths and the candidates among them (bit k: token mine + k)
 struct Lane {
-    uint32_t tw, cand;
-    int32_t dk[kPer];
+    TokenQuad t;
+    uint32_t cand;
 };
 // s_type: kThreads words of LDS that nothing else uses (a lane reads its neighbour's word behind the barrier)
 __device__ __forceinline__ Lane load_lane(const Window &win, uint64_t base, const uint8_t *__restrict__ type, const int32_t *__restrict__ depth,
                                           uint32_t *s_type) {
     Lane l;
     const uint64_t mine = base + (uint64_t)threadIdx.x * kPer;
-    // tokens at or past T read as nothing: they belong to the cut document
-    l.tw = load_byte_quad(type, mine, win.T);
-    s_type[threadIdx.x] = l.tw;
-    l.dk[0] = l.dk[1] = l.dk[2] = l.dk[3] = 0;
-    if (mine + kPer <= win.T) {
-        const int4 q = *reinterpret_cast<const int4 *>(depth + mine);
-        l.dk[0] = q.x, l.dk[1] = q.y, l.dk[2] = q.z, l.dk[3] = q.w;
-    } else {
-        for (int k = 0; k < kPer && mine + k < win.T; k++) l.dk[k] = depth[mine + k];
-    }
+    l.t = load_token_quad(type, depth, mine, win.T);  // tokens at or past T read as nothing: they belong to the cut document
+    s_type[threadIdx.x] = l.t.tw;
     __syncthreads();
     // the token in front of this lane's first: the lane before's last, or the halo, one token in front of the block
     uint32_t prev = threadIdx.x > 0 ? s_type[threadIdx.x - 1] >> 24 : (base > 0 ? (uint32_t)type[base - 1] : 0u);  // (base - 1 < T)
@@ -148,7 +118,7 @@ __device__ __forceinline__ Lane load_lane(const Window &win, uint64_t base, cons
 #pragma unroll
     for (int k = 0; k < kPer; k++) {
         const uint64_t i = mine + k;
-        const uint32_t t = (l.tw >> (8 * k)) & 0xFFu;
+        const uint32_t t = (l.t.tw >> (8 * k)) & 0xFFu;
         if (in_documents(win, i) && is_candidate(prev, t)) l.cand |= 1u << k;
         prev = t;
     }
@@ -165,7 +135,7 @@ __device__ __forceinline__ uint32_t elements_of(const Lane &l, const BlockDocs &
         if (doc == 0 || doc > win.D) continue;               // (<= capacity)
         const uint4 q = *reinterpret_cast<const uint4 *>(desc + (doc - 1));
         const Desc d{q.x, q.y, (int32_t)q.z, q.w};
-        if (is_element_of(mine + k, l.dk[k], d)) elem |= 1u << k;
+        if (is_element_of(mine + k, l.t.dk[k], d)) elem |= 1u << k;
     }
     return elem;
 }
@@ -197,24 +167,7 @@ __global__ __launch_bounds__(1024) void ac_scan(uint64_t n, const uint32_t *__re
     __shared__ uint64_t s_w[16];
     const Head h = load_head(docs, first, n, capacity, sel);
     const uint64_t blocks = h.stop ? 0 : token_blocks(h.win.T);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t run = 0;
-    for (uint64_t v0 = 0; v0 < blocks; v0 += 1024) {
-        const uint64_t v = v0 + threadIdx.x;
-        const uint64_t x = v < blocks ? w.bsum[v] : 0, inc = wave_scan(x);
-        __syncthreads();
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        uint64_t before = 0, all = 0;
-#pragma unroll 4
-        for (uint32_t j = 0; j < 16; j++) {
-            const uint64_t t = s_w[j];
-            if (j < wave) before += t;
-            all += t;
-        }
-        if (v < blocks) w.bsum[v] = (uint32_t)(run + before + inc - x);  // (fewer elements than tokens: below 2^31)
-        run += all;
-    }
+    const uint64_t run = scan_in_place(w.bsum, blocks, s_w);  // (fewer elements than tokens: a prefix is below 2^31)
     if (threadIdx.x != 0) return;
     msj_array_column_result r;
     r.code = h.stop ? h.code : elements_code(run, have_elements, elements_capacity);
@@ -257,9 +210,7 @@ __global__ __launch_bounds__(kThreads) void ac_emit(const uint32_t *__restrict__
     const uint32_t elem = elements_of(l, bd, h.win, base, w.desc);
     uint32_t total;
     uint64_t pos = (uint64_t)w.bsum[blockIdx.x] + block_scan((uint32_t)__popc(elem), s_w32, total);
-    uint64_t n_records = 0;
-    if (numbers && nr) n_records = umin64(nr->n_numbers, numbers_capacity);
-    const msj_number *records = n_records ? numbers : nullptr;
+    const NumberRecords rec = number_records(numbers, numbers_capacity, nr);
     const uint64_t mine = base + (uint64_t)threadIdx.x * kPer;
     uint32_t n_nobits = 0;
 #pragma unroll
@@ -270,20 +221,16 @@ __global__ __launch_bounds__(kThreads) void ac_emit(const uint32_t *__restrict__
         }
         if (!((elem >> k) & 1u)) continue;
         if (elements && pos < elements_capacity) {
-            const msj_field r = value_field<msj_field, msj_number>(mine + k, idx, type, match, end, flags, records, n_records);
+            const msj_field r = value_field<msj_field, msj_number>(mine + k, idx, type, match, end, flags, rec.records, rec.n);
             store_field(elements, pos, r);
             n_nobits += (r.flags & kFieldNoBits) != 0;
         }
         pos++;
     }
     if (!elements || !__syncthreads_or((int)n_nobits)) return;
-    n_nobits = wave_sum(n_nobits);  // (s_w32 is free: the scan's reads lie in front of that barrier)
-    if ((threadIdx.x & 63) == 0) s_w32[threadIdx.x >> 6] = n_nobits;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int v = 1; v < kWaves; v++) n_nobits += s_w32[v];
-    atomicAdd(reinterpret_cast<unsigned long long *>(&result->n_no_bits), (unsigned long long)n_nobits);
-    if (elements_select) atomicAdd(reinterpret_cast<unsigned long long *>(&elements_select->n_no_bits), (unsigned long long)n_nobits);
+    // (s_w32 is free: the scan's reads lie in front of that barrier)
+    const uint32_t all = block_counter_add(n_nobits, s_w32, &result->n_no_bits);
+    if (all && elements_select) atomicAdd(reinterpret_cast<unsigned long long *>(&elements_select->n_no_bits), (unsigned long long)all);
 }
 
 }  // namespace msj_acol
@@ -293,29 +240,26 @@ extern "C" uint64_t msj_array_column_workspace_bytes(uint64_t n, uint64_t capaci
     return sizeof(ColState) + sizeof(Desc) * most_rows(n, capacity) + up16(4 * token_blocks(n)) + 64;
 }
 
-extern "C" int msj_launch_array_column(const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
-                                       const uint32_t *d_end, const uint8_t *d_flags, const uint32_t *d_doc_first,
-                                       const msj_documents_result *d_docs, const msj_number *d_numbers, uint64_t numbers_capacity,
-                                       const msj_numbers_result *d_numbers_result, const msj_field *d_column,
+extern "C" int msj_launch_array_column(const msj_token_view &t, const msj_split_view &sp, const msj_number_view &nv, const msj_field *d_column,
                                        const msj_select_documents_result *d_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
                                        msj_field *d_elements, uint64_t elements_capacity, msj_array_column_result *d_result,
                                        msj_select_documents_result *d_elements_select, void *d_ws, void *stream) {
     using namespace msj_acol;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t n = t.n;
     const ColWork w = col_layout(d_ws, n, capacity);
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(ColState), s);
     if (cleared != hipSuccess) return (int)cleared;
-    const uint64_t rb = (most_rows(n, capacity) + kThreads - 1) / kThreads;
-    const uint32_t nb = (uint32_t)token_blocks(n);
+    const uint32_t rb = row_grid_blocks(most_rows(n, capacity)), nb = (uint32_t)token_blocks(n);
     if (rb)
-        hipLaunchKernelGGL(ac_rows, dim3((uint32_t)(rb > (uint64_t)kRowBlocks ? (uint64_t)kRowBlocks : rb)), dim3(kThreads), 0, s, n, d_type, d_depth,
-                           d_match, d_doc_first, d_docs, d_column, d_select, capacity, w, d_valid);
-    if (nb) hipLaunchKernelGGL(ac_count, dim3(nb), dim3(kThreads), 0, s, n, d_type, d_depth, d_doc_first, d_docs, d_select, capacity, w);
-    hipLaunchKernelGGL(ac_scan, dim3(1), dim3(1024), 0, s, n, d_doc_first, d_docs, d_select, capacity, w, d_offsets, d_elements != nullptr,
+        hipLaunchKernelGGL(ac_rows, dim3(rb), dim3(kThreads), 0, s, n, t.d_type, t.d_depth, t.d_match, sp.d_doc_first, sp.d_docs, d_column, d_select,
+                           capacity, w, d_valid);
+    if (nb) hipLaunchKernelGGL(ac_count, dim3(nb), dim3(kThreads), 0, s, n, t.d_type, t.d_depth, sp.d_doc_first, sp.d_docs, d_select, capacity, w);
+    hipLaunchKernelGGL(ac_scan, dim3(1), dim3(1024), 0, s, n, sp.d_doc_first, sp.d_docs, d_select, capacity, w, d_offsets, d_elements != nullptr,
                        elements_capacity, d_result, d_elements_select);
     if (nb)
-        hipLaunchKernelGGL(ac_emit, dim3(nb), dim3(kThreads), 0, s, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs,
-                           d_numbers, numbers_capacity, d_numbers_result, d_select, capacity, w, d_offsets, d_elements, elements_capacity, d_result,
-                           d_elements_select);
+        hipLaunchKernelGGL(ac_emit, dim3(nb), dim3(kThreads), 0, s, t.d_idx, n, t.d_type, t.d_depth, t.d_match, t.d_end, t.d_flags, sp.d_doc_first,
+                           sp.d_docs, nv.d_numbers, nv.numbers_capacity, nv.d_numbers_result, d_select, capacity, w, d_offsets, d_elements,
+                           elements_capacity, d_result, d_elements_select);
     return (int)hipGetLastError();
 }

@@ -1,7 +1,10 @@
-// launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 / f2 /
-// f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip, validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip, array_column_kernel.hip, select_elements_kernel.hip.  Every
-// launcher and every internal workspace size is declared here and nowhere else; the file that defines one and the file
-// that calls it both include this header, so the compiler compares the two signatures (C linkage alone would not).
+// launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 /
+// f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
+// validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
+// array_column_kernel.hip, select_elements_kernel.hip.  Every launcher and every internal workspace size is declared
+// here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
+// compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
+// (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.
 // (stage 1 has stage1_kernel.h; the exported *_workspace_bytes are declared in include/msj_stage1.h.)
 #pragma once
 #include <stdint.h>
@@ -69,45 +72,54 @@ extern "C" int msj_launch_documents(const uint8_t *d_buf, uint64_t len, int is_f
 extern "C" int msj_launch_number_values(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_flags,
                                         msj_number *d_numbers, uint64_t capacity, msj_numbers_result *d_result, void *d_ws, void *stream);
 
+// ---- what the calls over a window read, members in the ABI's order: the token arrays (msj_stage2_prep_device's outputs
+// over d_buf / d_idx), the split into documents (msj_documents_device), the number records (msj_number_values_device) ----
+struct msj_token_view {
+    const uint8_t *d_buf;
+    uint64_t len;
+    const uint32_t *d_idx;
+    uint64_t n;
+    const uint8_t *d_type;
+    const int32_t *d_depth;
+    const uint32_t *d_match, *d_end;
+    const uint8_t *d_flags;
+};
+struct msj_split_view {
+    const uint32_t *d_doc_first;
+    const msj_documents_result *d_docs;
+};
+struct msj_number_view {
+    const msj_number *d_numbers;
+    uint64_t numbers_capacity;
+    const msj_numbers_result *d_numbers_result;
+};
+
 // ---- validate_kernel.hip ----
-extern "C" int msj_launch_validate(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
-                                   const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
-                                   const msj_numbers_result *d_numbers, uint32_t max_depth, msj_validate_result *d_result, void *d_ws,
-                                   void *stream);
+extern "C" int msj_launch_validate(const msj_token_view &t, const msj_number_view &nv, uint32_t max_depth, msj_validate_result *d_result,
+                                   void *d_ws, void *stream);
 
 // ---- validate_docs_kernel.hip ----
-extern "C" int msj_launch_validate_documents(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
-                                             const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
-                                             const uint32_t *d_doc_first, const msj_documents_result *d_docs, const msj_number *d_numbers,
-                                             uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result, uint32_t max_depth,
+extern "C" int msj_launch_validate_documents(const msj_token_view &t, const msj_split_view &sp, const msj_number_view &nv, uint32_t max_depth,
                                              msj_document_verdict *d_verdicts, uint64_t capacity, msj_validate_documents_result *d_result,
                                              void *d_ws, void *stream);
 
 // ---- tape_kernel.hip ----
-extern "C" int msj_launch_tape(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
-                               const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
-                               const msj_number *d_numbers, uint64_t numbers_capacity, const msj_validate_result *d_verdict,
-                               uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf, uint64_t string_capacity,
-                               msj_tape_result *d_result, void *d_ws, void *stream);
+extern "C" int msj_launch_tape(const msj_token_view &t, const msj_number_view &nv, const msj_validate_result *d_verdict, uint64_t *d_tape,
+                               uint64_t tape_capacity, uint8_t *d_string_buf, uint64_t string_capacity, msj_tape_result *d_result,
+                               void *d_ws, void *stream);
 
 // ---- tape_docs_kernel.hip ----
-extern "C" int msj_launch_tape_documents(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
-                                         const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
-                                         const uint32_t *d_doc_first, const msj_documents_result *d_docs, const msj_number *d_numbers,
-                                         uint64_t numbers_capacity, const msj_document_verdict *d_verdicts, uint64_t *d_tape,
-                                         uint64_t tape_capacity, uint8_t *d_string_buf, uint64_t string_capacity,
-                                         msj_document_tape *d_doc_tapes, uint64_t capacity, msj_tape_documents_result *d_result, void *d_ws,
-                                         void *stream);
+extern "C" int msj_launch_tape_documents(const msj_token_view &t, const msj_split_view &sp, const msj_number_view &nv,
+                                         const msj_document_verdict *d_verdicts, uint64_t *d_tape, uint64_t tape_capacity,
+                                         uint8_t *d_string_buf, uint64_t string_capacity, msj_document_tape *d_doc_tapes, uint64_t capacity,
+                                         msj_tape_documents_result *d_result, void *d_ws, void *stream);
 
 // ---- select_kernel.hip ----
 // d_paths: the compiled paths (select_math.h: Paths) in device memory; n_paths / max_levels: what the host knows of them
-extern "C" int msj_launch_select_documents(const void *d_paths, uint32_t n_paths, uint32_t max_levels, const uint8_t *d_buf, uint64_t len,
-                                           const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth,
-                                           const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
-                                           const uint32_t *d_doc_first, const msj_documents_result *d_docs, const msj_number *d_numbers,
-                                           uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
-                                           const msj_document_verdict *d_verdicts, msj_field *d_fields, uint64_t capacity,
-                                           msj_select_documents_result *d_result, void *d_ws, void *stream);
+extern "C" int msj_launch_select_documents(const void *d_paths, uint32_t n_paths, uint32_t max_levels, const msj_token_view &t,
+                                           const msj_split_view &sp, const msj_number_view &nv, const msj_document_verdict *d_verdicts,
+                                           msj_field *d_fields, uint64_t capacity, msj_select_documents_result *d_result, void *d_ws,
+                                           void *stream);
 
 // ---- string_column_kernel.hip ----
 extern "C" int msj_launch_string_column(const uint8_t *d_buf, uint64_t len, const msj_field *d_column, const msj_select_documents_result *d_select,
@@ -115,19 +127,16 @@ extern "C" int msj_launch_string_column(const uint8_t *d_buf, uint64_t len, cons
                                         msj_string_column_result *d_result, void *d_ws, void *stream);
 
 // ---- array_column_kernel.hip ----
-extern "C" int msj_launch_array_column(const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
-                                       const uint32_t *d_end, const uint8_t *d_flags, const uint32_t *d_doc_first,
-                                       const msj_documents_result *d_docs, const msj_number *d_numbers, uint64_t numbers_capacity,
-                                       const msj_numbers_result *d_numbers_result, const msj_field *d_column,
+// (t.d_buf / t.len are not read)
+extern "C" int msj_launch_array_column(const msj_token_view &t, const msj_split_view &sp, const msj_number_view &nv, const msj_field *d_column,
                                        const msj_select_documents_result *d_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
                                        msj_field *d_elements, uint64_t elements_capacity, msj_array_column_result *d_result,
                                        msj_select_documents_result *d_elements_select, void *d_ws, void *stream);
 
 // ---- select_elements_kernel.hip ----
-// d_paths / n_paths / max_levels as for msj_launch_select_documents; d_rows / d_rows_select: the element records of an array column
-extern "C" int msj_launch_select_elements(const void *d_paths, uint32_t n_paths, uint32_t max_levels, const uint8_t *d_buf, uint64_t len,
-                                          const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth,
-                                          const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags, const msj_number *d_numbers,
-                                          uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result, const msj_field *d_rows,
-                                          const msj_select_documents_result *d_rows_select, msj_field *d_fields, uint64_t capacity,
-                                          msj_select_documents_result *d_result, void *d_ws, void *stream);
+// d_paths / n_paths / max_levels as for msj_launch_select_documents; d_rows / d_rows_select: the element records of an
+// array column
+extern "C" int msj_launch_select_elements(const void *d_paths, uint32_t n_paths, uint32_t max_levels, const msj_token_view &t,
+                                          const msj_number_view &nv, const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
+                                          msj_field *d_fields, uint64_t capacity, msj_select_documents_result *d_result, void *d_ws,
+                                          void *stream);

@@ -22,22 +22,18 @@
 //               found" (the two word arrays alternate)
 //   sel_finish  per (p, k), coalesced along k: the record; n_found / n_no_bits by wave and block, one atomic per block
 // Every index from d_match, d_end or d_doc_first is checked before it is used; a state word that is a token is below T.
+// The steps select_elements_kernel.hip takes in the same way are select_block.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
-#include "docs_block.h"
 #include "launch.h"
-#include "select_math.h"
+#include "select_block.h"
 
 namespace msj_sel {
 
-using namespace msj_tdocs;
-using namespace msj::sel;
+using namespace msj_selblock;
 
-constexpr int kGridBlocks = 1024;  // most blocks along k of the kernels over (p, k)
-
-static_assert(sizeof(msj_field) == 16 && sizeof(msj_select_documents_result) == 48, "ABI");
 static_assert(sizeof(Paths) % 8 == 0, "the blob is copied as it is");
 
 // the two state words of (p, k): level l's in word[l & 1]
@@ -82,62 +78,30 @@ __global__ __launch_bounds__(kThreads) void sel_level(const Paths *__restrict__ 
                                                       const uint32_t *__restrict__ match, const uint32_t *__restrict__ end,
                                                       const uint8_t *__restrict__ flags, const uint32_t *__restrict__ first,
                                                       const msj_documents_result *__restrict__ docs, uint64_t capacity, const Words ws) {
-    __shared__ uint8_t s_seg[kMaxPaths][256];
-    __shared__ uint32_t s_len[kMaxPaths];
+    __shared__ Segments s_seg;
     __shared__ uint32_t s_type[kThreads + 1];
     __shared__ uint32_t s_flag[kThreads], s_k[2], s_w32[kWaves];
     const Window win = load_window(docs, first, n, capacity);
     const uint64_t base = (uint64_t)blockIdx.x * kBlock, mine = base + (uint64_t)threadIdx.x * kPer;
     if (win.over || win.D == 0 || base >= win.T) return;
-    // tokens at or past T read as nothing: they belong to the cut document
-    const uint32_t tw = load_byte_quad(type, mine, win.T);
-    s_type[threadIdx.x] = tw;
-    if (threadIdx.x == 0) s_type[kThreads] = load_byte_quad(type, base + kBlock, win.T);  // the halo: one token is needed
-    int32_t dk[kPer] = {0, 0, 0, 0};
-    if (mine + kPer <= win.T) {
-        const int4 q = *reinterpret_cast<const int4 *>(depth + mine);
-        dk[0] = q.x, dk[1] = q.y, dk[2] = q.z, dk[3] = q.w;
-    } else {
-        for (int k = 0; k < kPer && mine + k < win.T; k++) dk[k] = depth[mine + k];
-    }
-    if (threadIdx.x < kMaxPaths) s_len[threadIdx.x] = threadIdx.x < paths->n_paths ? paths->len[level][threadIdx.x] : kNoLevel;
-    __syncthreads();
-    const uint32_t behind = s_type[threadIdx.x + 1];
-    uint32_t cand = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; k++) {
-        const uint64_t i = mine + k;
-        const uint32_t t = (tw >> (8 * k)) & 0xFFu, t_next = k + 1 < kPer ? (tw >> (8 * (k + 1))) & 0xFFu : behind & 0xFFu;
-        if (i >= win.f0 && i < win.T && is_key_at(t, t_next, dk[k], level)) cand |= 1u << k;
-    }
-    if (!__syncthreads_or((int)cand)) return;  // (the whole block: no key of this level in it)
-    const uint32_t n_paths = paths->n_paths;
-    for (uint32_t p = 0; p < n_paths; p++) {
-        const uint32_t sl = s_len[p];
-        if (sl != kNoLevel)
-            for (uint32_t x = threadIdx.x; x < sl; x += kThreads) s_seg[p][x] = paths->bytes[level][p][x];
-    }
+    // tokens at or past T read as nothing: they belong to the cut document.  A candidate: a string at depth level + 1 with
+    // ':' behind it
+    const TokenQuad t = load_block(paths, level, type, depth, base, win.T, s_type, s_seg);
+    uint32_t cand;
+    if (!key_candidates(t, base, win.T, s_type, cand,
+                        [&](uint64_t i, uint32_t ty, uint32_t t_next, int32_t d) { return i >= win.f0 && is_key_at(ty, t_next, d, level); }))
+        return;
+    stage_segments(paths, level, s_seg);
     const BlockDocs bd = block_docs(first, win, base, s_flag, s_k, s_w32);  // (its barriers publish the segments)
     const ByteReader r{buf, len};
-    const uint32_t *at = ws.word[level & 1];
-    uint32_t *found = ws.word[(level + 1) & 1];
+    const uint32_t n_paths = paths->n_paths;
 #pragma unroll
     for (int k = 0; k < kPer; k++) {
         if (!((cand >> k) & 1u)) continue;
         const uint64_t i = mine + k;
         const uint64_t doc = (uint64_t)bd.k0 + bd.rank[k];  // 1 + the document's number
         if (doc == 0 || doc > win.D) continue;               // (<= capacity)
-        const uint64_t b = (uint64_t)idx[i] + 1, q = end[i];
-        const bool escaped = (flags[i] & kSpanEscaped) != 0;
-        if (q < b || q > len) continue;  // not what the span call writes: never read
-        for (uint32_t p = 0; p < n_paths; p++) {
-            const uint32_t sl = s_len[p];
-            if (sl == kNoLevel || !length_may_match(q - b, escaped, sl)) continue;
-            const uint64_t w = p * ws.stride + doc - 1;
-            const uint32_t lo = at[w];
-            if (!state_is_token(lo) || !is_member_of(i, lo, match[lo])) continue;  // (a token state is below T <= n)
-            if (key_equals(r, b, q, escaped, s_seg[p], sl)) atomicMin(found + w, (uint32_t)i);
-        }
+        match_key(r, idx, match, end, flags, i, doc - 1, n_paths, level, s_seg, ws, [&](uint32_t lo, uint32_t m) { return is_member_of(i, lo, m); });
     }
 }
 
@@ -145,17 +109,12 @@ __global__ __launch_bounds__(kThreads) void sel_step(const Paths *__restrict__ p
                                                      const uint32_t *__restrict__ match, uint64_t n, const uint32_t *__restrict__ first,
                                                      const msj_documents_result *__restrict__ docs, uint64_t capacity, const Words ws) {
     const Window win = load_window(docs, first, n, capacity);
-    const uint32_t p = blockIdx.y, levels = paths->levels[p];
-    if (win.over || levels <= level) return;  // (the path ended at or in front of this level: its word stays)
-    uint32_t *at = ws.word[level & 1], *next = ws.word[(level + 1) & 1];
-    const uint64_t lanes = (uint64_t)gridDim.x * kThreads;
-    for (uint64_t k = (uint64_t)blockIdx.x * kThreads + threadIdx.x; k < win.D; k += lanes) {
+    if (win.over) return;
+    step_rows(paths, level, type, match, ws, win.D, [&](uint64_t k) {
         uint64_t f, e;
         (void)document_bounds(first, win, k, f, e);  // (judged by sel_init: a document out of bounds has a code)
-        const uint64_t w = p * ws.stride + k;
-        next[w] = next_state(at[w], next[w], levels == level + 1, e, type, match);
-        if (levels > level + 1) at[w] = kNotFound;  // the word of level + 2
-    }
+        return e;
+    });
 }
 
 __global__ __launch_bounds__(kThreads) void sel_finish(const Paths *__restrict__ paths, const uint32_t *__restrict__ idx, uint64_t n,
@@ -166,69 +125,43 @@ __global__ __launch_bounds__(kThreads) void sel_finish(const Paths *__restrict__
                                                        const msj_numbers_result *__restrict__ nr, const Words ws,
                                                        msj_field *__restrict__ fields, uint64_t capacity,
                                                        msj_select_documents_result *__restrict__ result) {
-    __shared__ uint32_t w_found[kWaves], w_nobits[kWaves];
     const Window win = load_window(docs, first, n, capacity);
     if (win.over || win.D == 0) return;
-    const uint32_t p = blockIdx.y;
-    const uint32_t *word = ws.word[paths->levels[p] & 1];
-    uint64_t n_records = 0;
-    if (numbers && nr) n_records = umin64(nr->n_numbers, numbers_capacity);
-    const msj_number *records = n_records ? numbers : nullptr;
-    const uint64_t lanes = (uint64_t)gridDim.x * kThreads;
-    uint32_t n_found = 0, n_nobits = 0;
-    for (uint64_t k = (uint64_t)blockIdx.x * kThreads + threadIdx.x; k < win.D; k += lanes) {
-        const msj_field r = field_of_state<msj_field, msj_number>(word[p * ws.stride + k], idx, type, match, end, flags, records, n_records);
-        fields[p * capacity + k] = r;  // (k < D <= capacity)
-        n_found += r.code == 0;
-        n_nobits += (r.flags & kFieldNoBits) != 0;
-    }
-    n_found = wave_sum(n_found), n_nobits = wave_sum(n_nobits);
-    if ((threadIdx.x & 63) == 0) w_found[threadIdx.x >> 6] = n_found, w_nobits[threadIdx.x >> 6] = n_nobits;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int v = 1; v < kWaves; v++) n_found += w_found[v], n_nobits += w_nobits[v];
-    if (n_found) atomicAdd(reinterpret_cast<unsigned long long *>(&result->n_found), (unsigned long long)n_found);
-    if (n_nobits) atomicAdd(reinterpret_cast<unsigned long long *>(&result->n_no_bits), (unsigned long long)n_nobits);
-}
-
-static uint64_t most_documents(uint64_t n, uint64_t capacity) {
-    const uint64_t d = n < capacity ? n : capacity;
-    return d ? d : 1;
+    const uint32_t *word = ws.word[paths->levels[blockIdx.y] & 1] + blockIdx.y * ws.stride;
+    finish_rows(idx, type, match, end, flags, number_records(numbers, numbers_capacity, nr), win.D, fields, capacity, result,
+                [&](uint64_t k) { return word[k]; });
 }
 
 }  // namespace msj_sel
 
 extern "C" uint64_t msj_select_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity, uint32_t n_paths) {
     (void)len;
-    return 2ull * 4ull * n_paths * msj_sel::most_documents(n, capacity) + 64;
+    return 2ull * 4ull * n_paths * msj_tdocs::most_documents(n, capacity) + 64;
 }
 
-extern "C" int msj_launch_select_documents(const void *d_paths, uint32_t n_paths, uint32_t max_levels, const uint8_t *d_buf, uint64_t len,
-                                           const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth,
-                                           const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
-                                           const uint32_t *d_doc_first, const msj_documents_result *d_docs, const msj_number *d_numbers,
-                                           uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
-                                           const msj_document_verdict *d_verdicts, msj_field *d_fields, uint64_t capacity,
-                                           msj_select_documents_result *d_result, void *d_ws, void *stream) {
+extern "C" int msj_launch_select_documents(const void *d_paths, uint32_t n_paths, uint32_t max_levels, const msj_token_view &t,
+                                           const msj_split_view &sp, const msj_number_view &nv, const msj_document_verdict *d_verdicts,
+                                           msj_field *d_fields, uint64_t capacity, msj_select_documents_result *d_result, void *d_ws,
+                                           void *stream) {
     using namespace msj_sel;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Paths *paths = static_cast<const Paths *>(d_paths);
-    const uint64_t most = most_documents(n, capacity);
+    const uint64_t most = most_documents(t.n, capacity);
     Words ws;
     ws.word[0] = static_cast<uint32_t *>(d_ws);
     ws.word[1] = ws.word[0] + (uint64_t)n_paths * most;
     ws.stride = most;
-    const uint32_t gb = (uint32_t)((most + kThreads - 1) / kThreads);
-    const dim3 doc_grid(gb > (uint32_t)kGridBlocks ? (uint32_t)kGridBlocks : gb, n_paths);
-    hipLaunchKernelGGL(sel_init, doc_grid, dim3(kThreads), 0, s, paths, d_type, d_match, n, d_doc_first, d_docs, capacity, d_verdicts, ws, d_result);
-    if (n == 0) return (int)hipGetLastError();  // no document: the zero result is all there is
-    const uint32_t nb = (uint32_t)((n + kBlock - 1) / kBlock);
+    const dim3 doc_grid(row_grid_blocks(most), n_paths);
+    hipLaunchKernelGGL(sel_init, doc_grid, dim3(kThreads), 0, s, paths, t.d_type, t.d_match, t.n, sp.d_doc_first, sp.d_docs, capacity, d_verdicts, ws,
+                       d_result);
+    if (t.n == 0) return (int)hipGetLastError();  // no document: the zero result is all there is
+    const uint32_t nb = (uint32_t)((t.n + kBlock - 1) / kBlock);
     for (uint32_t l = 0; l < max_levels; l++) {
-        hipLaunchKernelGGL(sel_level, dim3(nb), dim3(kThreads), 0, s, paths, l, d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags,
-                           d_doc_first, d_docs, capacity, ws);
-        hipLaunchKernelGGL(sel_step, doc_grid, dim3(kThreads), 0, s, paths, l, d_type, d_match, n, d_doc_first, d_docs, capacity, ws);
+        hipLaunchKernelGGL(sel_level, dim3(nb), dim3(kThreads), 0, s, paths, l, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_depth, t.d_match, t.d_end,
+                           t.d_flags, sp.d_doc_first, sp.d_docs, capacity, ws);
+        hipLaunchKernelGGL(sel_step, doc_grid, dim3(kThreads), 0, s, paths, l, t.d_type, t.d_match, t.n, sp.d_doc_first, sp.d_docs, capacity, ws);
     }
-    hipLaunchKernelGGL(sel_finish, doc_grid, dim3(kThreads), 0, s, paths, d_idx, n, d_type, d_match, d_end, d_flags, d_doc_first, d_docs, d_numbers,
-                       numbers_capacity, d_numbers_result, ws, d_fields, capacity, d_result);
+    hipLaunchKernelGGL(sel_finish, doc_grid, dim3(kThreads), 0, s, paths, t.d_idx, t.n, t.d_type, t.d_match, t.d_end, t.d_flags, sp.d_doc_first,
+                       sp.d_docs, nv.d_numbers, nv.numbers_capacity, nv.d_numbers_result, ws, d_fields, capacity, d_result);
     return (int)hipGetLastError();
 }

@@ -1,7 +1,8 @@
 // stage2_api.cpp -- extern "C" entry points of everything that runs behind stage 1 (include/msj_stage1.h): tokens, spans,
-// the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list elements.  Every call is the same few steps: check
-// the arguments (the order of the checks is part of the ABI: callers see which error wins), select the device, grow the
-// call's workspace, launch.
+// the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
+// window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
+// elements.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
 #include <new>
 
 #include "ctx.h"
@@ -20,6 +21,15 @@ constexpr uint64_t kMaxTokens = 1ull << 31;  // token numbers are uint32 with th
 bool too_big(uint64_t len, uint64_t n) { return len > MSJ_MAX_SEGMENT_BYTES || n >= kMaxTokens; }
 template <class... P>
 bool all_aligned(uintptr_t a, P... p) { return (aligned(p, a) && ...); }  // (null pointers are aligned)
+
+// what the calls over a window ask of their views (launch.h): the entry point decides the code and the order
+bool arrays_present(const msj_token_view &t) { return t.d_idx && t.d_type && t.d_depth && t.d_match && t.d_end && t.d_flags; }
+bool all_present(const msj_token_view &t) { return t.d_buf && arrays_present(t); }
+bool too_big(const msj_token_view &t) { return too_big(t.len, t.n); }
+bool is_aligned(const msj_token_view &t) { return all_aligned(16, t.d_idx, t.d_depth, t.d_match, t.d_end) && all_aligned(8, t.d_type, t.d_flags); }
+bool is_aligned(const msj_split_view &sp) { return aligned(sp.d_docs, 8) && aligned(sp.d_doc_first, 4); }
+bool records_present(const msj_number_view &nv) { return nv.numbers_capacity == 0 || nv.d_numbers; }
+bool is_aligned(const msj_number_view &nv) { return aligned(nv.d_numbers, 16) && aligned(nv.d_numbers_result, 8); }
 
 // behind the argument checks of a device call: its device selected, its workspace at least `need` bytes
 int32_t begin_call(msj_ctx *ctx, DeviceBuffer &ws, uint64_t need) {
@@ -254,14 +264,15 @@ int32_t msj_validate_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, co
                             const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
                             const uint32_t *d_end, const uint8_t *d_flags, const msj_numbers_result *d_numbers,
                             uint32_t max_depth, msj_validate_result *d_result, void *stream) {
-    if (!ctx || !d_result || !d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags) return MSJ_ERR_BAD_ARGUMENT;
+    const msj_token_view t{d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags};
+    const msj_number_view nv{nullptr, 0, d_numbers};
+    if (!ctx || !d_result || !all_present(t)) return MSJ_ERR_BAD_ARGUMENT;
     if (n == 0 || max_depth == 0) return MSJ_ERR_BAD_ARGUMENT;
-    if (too_big(len, n)) return MSJ_CAPACITY;
-    if (!all_aligned(16, d_idx, d_depth, d_match, d_end) || !all_aligned(8, d_type, d_flags, d_numbers, d_result)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(t)) return MSJ_CAPACITY;
+    if (!is_aligned(t) || !is_aligned(nv) || !aligned(d_result, 8)) return MSJ_ERR_BAD_ARGUMENT;
     const int32_t rc = begin_call(ctx, ctx->val_ws, msj_validate_workspace_bytes(n, len));
     if (rc != MSJ_SUCCESS) return rc;
-    return launched(msj_launch_validate(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, max_depth, d_result,
-                                        ctx->val_ws.p, stream));
+    return launched(msj_launch_validate(t, nv, max_depth, d_result, ctx->val_ws.p, stream));
 }
 
 int32_t msj_validate_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
@@ -270,18 +281,17 @@ int32_t msj_validate_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64
                                       const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
                                       uint32_t max_depth, msj_document_verdict *d_verdicts, uint64_t capacity,
                                       msj_validate_documents_result *d_result, void *stream) {
+    const msj_token_view t{d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags};
+    const msj_split_view sp{d_doc_first, d_docs};
+    const msj_number_view nv{d_numbers, numbers_capacity, d_numbers_result};
     if (!ctx || !d_result || !d_docs || max_depth == 0) return MSJ_ERR_BAD_ARGUMENT;
-    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
-    if ((capacity > 0 && !d_verdicts) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
-    if (too_big(len, n)) return MSJ_CAPACITY;
-    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers) || !all_aligned(8, d_type, d_flags, d_docs, d_numbers_result, d_verdicts, d_result) ||
-        !aligned(d_doc_first, 4))
-        return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!all_present(t) || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((capacity > 0 && !d_verdicts) || !records_present(nv)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(t)) return MSJ_CAPACITY;
+    if (!is_aligned(t) || !is_aligned(sp) || !is_aligned(nv) || !all_aligned(8, d_verdicts, d_result)) return MSJ_ERR_BAD_ARGUMENT;
     const int32_t rc = begin_call(ctx, ctx->vdoc_ws, msj_validate_documents_workspace_bytes(n, len, capacity));
     if (rc != MSJ_SUCCESS) return rc;
-    return launched(msj_launch_validate_documents(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_numbers,
-                                                  numbers_capacity, d_numbers_result, max_depth, d_verdicts, capacity, d_result, ctx->vdoc_ws.p,
-                                                  stream));
+    return launched(msj_launch_validate_documents(t, sp, nv, max_depth, d_verdicts, capacity, d_result, ctx->vdoc_ws.p, stream));
 }
 
 int32_t msj_tape_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
@@ -289,17 +299,16 @@ int32_t msj_tape_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const 
                         const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
                         const msj_validate_result *d_verdict, uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf,
                         uint64_t string_capacity, msj_tape_result *d_result, void *stream) {
-    if (!ctx || !d_result || !d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags) return MSJ_ERR_BAD_ARGUMENT;
-    if ((tape_capacity > 0 && !d_tape) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
+    const msj_token_view t{d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags};
+    const msj_number_view nv{d_numbers, numbers_capacity, d_numbers_result};
+    if (!ctx || !d_result || !all_present(t)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((tape_capacity > 0 && !d_tape) || !records_present(nv)) return MSJ_ERR_BAD_ARGUMENT;
     if (n == 0) return MSJ_ERR_BAD_ARGUMENT;
-    if (too_big(len, n)) return MSJ_CAPACITY;
-    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers, d_tape) ||
-        !all_aligned(8, d_type, d_flags, d_numbers_result, d_verdict, d_result))
-        return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(t)) return MSJ_CAPACITY;
+    if (!is_aligned(t) || !is_aligned(nv) || !aligned(d_tape, 16) || !all_aligned(8, d_verdict, d_result)) return MSJ_ERR_BAD_ARGUMENT;
     const int32_t rc = begin_call(ctx, ctx->tape_ws, msj_tape_workspace_bytes(n, len));
     if (rc != MSJ_SUCCESS) return rc;
-    return launched(msj_launch_tape(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_numbers, numbers_capacity, d_verdict, d_tape,
-                                    tape_capacity, d_string_buf, string_capacity, d_result, ctx->tape_ws.p, stream));
+    return launched(msj_launch_tape(t, nv, d_verdict, d_tape, tape_capacity, d_string_buf, string_capacity, d_result, ctx->tape_ws.p, stream));
 }
 
 int32_t msj_tape_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
@@ -309,18 +318,19 @@ int32_t msj_tape_documents_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t l
                                   const msj_document_verdict *d_verdicts, uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf,
                                   uint64_t string_capacity, msj_document_tape *d_doc_tapes, uint64_t capacity,
                                   msj_tape_documents_result *d_result, void *stream) {
+    const msj_token_view t{d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags};
+    const msj_split_view sp{d_doc_first, d_docs};
+    const msj_number_view nv{d_numbers, numbers_capacity, d_numbers_result};
     if (!ctx || !d_result || !d_docs) return MSJ_ERR_BAD_ARGUMENT;
-    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
-    if ((tape_capacity > 0 && !d_tape) || (capacity > 0 && !d_doc_tapes) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
-    if (too_big(len, n)) return MSJ_CAPACITY;
-    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers, d_tape) ||
-        !all_aligned(8, d_type, d_flags, d_docs, d_numbers_result, d_verdicts, d_doc_tapes, d_result) || !aligned(d_doc_first, 4))
+    if (n > 0 && (!all_present(t) || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((tape_capacity > 0 && !d_tape) || (capacity > 0 && !d_doc_tapes) || !records_present(nv)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(t)) return MSJ_CAPACITY;
+    if (!is_aligned(t) || !is_aligned(sp) || !is_aligned(nv) || !aligned(d_tape, 16) || !all_aligned(8, d_verdicts, d_doc_tapes, d_result))
         return MSJ_ERR_BAD_ARGUMENT;
     const int32_t rc = begin_call(ctx, ctx->tdoc_ws, msj_tape_documents_workspace_bytes(n, len, capacity));
     if (rc != MSJ_SUCCESS) return rc;
-    return launched(msj_launch_tape_documents(d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_numbers,
-                                              numbers_capacity, d_verdicts, d_tape, tape_capacity, d_string_buf, string_capacity, d_doc_tapes,
-                                              capacity, d_result, ctx->tdoc_ws.p, stream));
+    return launched(msj_launch_tape_documents(t, sp, nv, d_verdicts, d_tape, tape_capacity, d_string_buf, string_capacity, d_doc_tapes, capacity,
+                                              d_result, ctx->tdoc_ws.p, stream));
 }
 
 int32_t msj_paths_create(msj_ctx *ctx, const char *const *pointers, uint32_t n_paths, msj_paths **out) {
@@ -358,18 +368,19 @@ int32_t msj_select_documents_device(msj_ctx *ctx, const msj_paths *paths, const 
                                     const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
                                     const msj_document_verdict *d_verdicts, msj_field *d_fields, uint64_t capacity,
                                     msj_select_documents_result *d_result, void *stream) {
+    const msj_token_view t{d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags};
+    const msj_split_view sp{d_doc_first, d_docs};
+    const msj_number_view nv{d_numbers, numbers_capacity, d_numbers_result};
     if (!ctx || !paths || paths->device != ctx->device || !d_result || !d_docs) return MSJ_ERR_BAD_ARGUMENT;
-    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
-    if ((capacity > 0 && !d_fields) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
-    if (too_big(len, n)) return MSJ_CAPACITY;
-    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers, d_fields) ||
-        !all_aligned(8, d_type, d_flags, d_docs, d_numbers_result, d_verdicts, d_result) || !aligned(d_doc_first, 4))
+    if (n > 0 && (!all_present(t) || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((capacity > 0 && !d_fields) || !records_present(nv)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(t)) return MSJ_CAPACITY;
+    if (!is_aligned(t) || !is_aligned(sp) || !is_aligned(nv) || !aligned(d_fields, 16) || !all_aligned(8, d_verdicts, d_result))
         return MSJ_ERR_BAD_ARGUMENT;
     const int32_t rc = begin_call(ctx, ctx->sel_ws, msj_select_documents_workspace_bytes(n, len, capacity, paths->n_paths));
     if (rc != MSJ_SUCCESS) return rc;
-    return launched(msj_launch_select_documents(paths->blob.p, paths->n_paths, paths->max_levels, d_buf, len, d_idx, n, d_type, d_depth, d_match,
-                                                d_end, d_flags, d_doc_first, d_docs, d_numbers, numbers_capacity, d_numbers_result, d_verdicts,
-                                                d_fields, capacity, d_result, ctx->sel_ws.p, stream));
+    return launched(msj_launch_select_documents(paths->blob.p, paths->n_paths, paths->max_levels, t, sp, nv, d_verdicts, d_fields, capacity,
+                                                d_result, ctx->sel_ws.p, stream));
 }
 
 int32_t msj_string_column_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const msj_field *d_column,
@@ -393,19 +404,21 @@ int32_t msj_array_column_device(msj_ctx *ctx, const uint32_t *d_idx, uint64_t n,
                                 const msj_select_documents_result *d_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
                                 msj_field *d_elements, uint64_t elements_capacity, msj_array_column_result *d_result,
                                 msj_select_documents_result *d_elements_select, void *stream) {
+    const msj_token_view t{nullptr, 0, d_idx, n, d_type, d_depth, d_match, d_end, d_flags};  // (the call reads no byte of the window)
+    const msj_split_view sp{d_doc_first, d_docs};
+    const msj_number_view nv{d_numbers, numbers_capacity, d_numbers_result};
     if (!ctx || !d_result || !d_select || !d_docs) return MSJ_ERR_BAD_ARGUMENT;
-    if (n > 0 && (!d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!arrays_present(t) || !d_doc_first)) return MSJ_ERR_BAD_ARGUMENT;
     if (capacity > 0 && (!d_column || !d_offsets || !d_valid)) return MSJ_ERR_BAD_ARGUMENT;
-    if ((elements_capacity > 0 && !d_elements) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
-    if (n >= kMaxTokens) return MSJ_CAPACITY;
-    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers, d_column, d_elements) ||
-        !all_aligned(8, d_type, d_flags, d_docs, d_numbers_result, d_select, d_offsets, d_result, d_elements_select) || !aligned(d_doc_first, 4))
+    if ((elements_capacity > 0 && !d_elements) || !records_present(nv)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(t)) return MSJ_CAPACITY;
+    if (!is_aligned(t) || !is_aligned(sp) || !is_aligned(nv) || !all_aligned(16, d_column, d_elements) ||
+        !all_aligned(8, d_select, d_offsets, d_result, d_elements_select))
         return MSJ_ERR_BAD_ARGUMENT;
     const int32_t rc = begin_call(ctx, ctx->acol_ws, msj_array_column_workspace_bytes(n, capacity));
     if (rc != MSJ_SUCCESS) return rc;
-    return launched(msj_launch_array_column(d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_numbers, numbers_capacity,
-                                            d_numbers_result, d_column, d_select, d_offsets, d_valid, capacity, d_elements, elements_capacity,
-                                            d_result, d_elements_select, ctx->acol_ws.p, stream));
+    return launched(msj_launch_array_column(t, sp, nv, d_column, d_select, d_offsets, d_valid, capacity, d_elements, elements_capacity, d_result,
+                                            d_elements_select, ctx->acol_ws.p, stream));
 }
 
 int32_t msj_select_elements_device(msj_ctx *ctx, const msj_paths *paths, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
@@ -414,18 +427,18 @@ int32_t msj_select_elements_device(msj_ctx *ctx, const msj_paths *paths, const u
                                    const msj_numbers_result *d_numbers_result, const msj_field *d_rows,
                                    const msj_select_documents_result *d_rows_select, msj_field *d_fields, uint64_t capacity,
                                    msj_select_documents_result *d_result, void *stream) {
+    const msj_token_view t{d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags};
+    const msj_number_view nv{d_numbers, numbers_capacity, d_numbers_result};
     if (!ctx || !paths || paths->device != ctx->device || !d_result || !d_rows_select || d_result == d_rows_select) return MSJ_ERR_BAD_ARGUMENT;
-    if (n > 0 && (!d_buf || !d_idx || !d_type || !d_depth || !d_match || !d_end || !d_flags)) return MSJ_ERR_BAD_ARGUMENT;
-    if ((capacity > 0 && (!d_rows || !d_fields)) || (numbers_capacity > 0 && !d_numbers)) return MSJ_ERR_BAD_ARGUMENT;
-    if (too_big(len, n)) return MSJ_CAPACITY;
-    if (!all_aligned(16, d_idx, d_depth, d_match, d_end, d_numbers, d_rows, d_fields) ||
-        !all_aligned(8, d_type, d_flags, d_numbers_result, d_rows_select, d_result))
+    if (n > 0 && !all_present(t)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((capacity > 0 && (!d_rows || !d_fields)) || !records_present(nv)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(t)) return MSJ_CAPACITY;
+    if (!is_aligned(t) || !is_aligned(nv) || !all_aligned(16, d_rows, d_fields) || !all_aligned(8, d_rows_select, d_result))
         return MSJ_ERR_BAD_ARGUMENT;
     const int32_t rc = begin_call(ctx, ctx->selem_ws, msj_select_elements_workspace_bytes(n, capacity, paths->n_paths));
     if (rc != MSJ_SUCCESS) return rc;
-    return launched(msj_launch_select_elements(paths->blob.p, paths->n_paths, paths->max_levels, d_buf, len, d_idx, n, d_type, d_depth, d_match,
-                                               d_end, d_flags, d_numbers, numbers_capacity, d_numbers_result, d_rows, d_rows_select, d_fields,
-                                               capacity, d_result, ctx->selem_ws.p, stream));
+    return launched(msj_launch_select_elements(paths->blob.p, paths->n_paths, paths->max_levels, t, nv, d_rows, d_rows_select, d_fields, capacity,
+                                               d_result, ctx->selem_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

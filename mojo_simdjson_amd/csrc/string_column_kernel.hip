@@ -28,21 +28,18 @@
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
+#include "docs_block.h"
 #include "launch.h"
 #include "string_column_math.h"
-#include "wave_unescape.h"
 
 namespace msj_scol {
 
 using namespace msj::scol;
 using namespace msj::wave;
 using msj::val::ByteReader;
-using msj_tape::BufWriter;
-using msj_tape::kLaneBody;
-using msj_tape::wave_unescape;
+using msj_tape::block_scan, msj_tape::BufWriter, msj_tape::kLaneBody, msj_tape::kThreads, msj_tape::kWaves, msj_tape::up16, msj_tape::wave_unescape;
+using msj_tdocs::load_field;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr uint32_t kRows = kThreads;   // rows per block: one per lane
 constexpr uint32_t kGridBlocks = 4096; // most blocks of the kernels over the rows (they loop over what D needs)
 
@@ -59,7 +56,6 @@ struct Work {
 };
 
 __host__ __device__ inline uint64_t most_rows(uint64_t capacity) { return capacity < kMaxRows ? capacity : kMaxRows; }
-__host__ __device__ inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 static inline Work layout(void *ws, uint64_t capacity) {
     const uint64_t rows = most_rows(capacity), nb = rows / kRows + 1;
     uint8_t *p = static_cast<uint8_t *>(ws);
@@ -85,32 +81,6 @@ __device__ __forceinline__ Head load_head(const msj_select_documents_result *__r
     h.stop = h.skip || h.over;
     h.blocks = h.stop ? 0 : (h.D + kRows - 1) / kRows;
     return h;
-}
-
-__device__ __forceinline__ msj_field load_field(const msj_field *__restrict__ column, uint64_t k) {
-    const uint4 q = *reinterpret_cast<const uint4 *>(column + k);  // (16-byte aligned: checked by the entry point)
-    msj_field f;
-    f.bits = (uint64_t)q.x | ((uint64_t)q.y << 32);
-    f.token = q.z;
-    f.type = (uint8_t)(q.w & 0xFFu), f.flags = (uint8_t)((q.w >> 8) & 0xFFu), f.code = (uint16_t)(q.w >> 16);
-    return f;
-}
-
-// exclusive sum over the workgroup (s_w: kWaves words of LDS, free again behind the next barrier); total: the sum
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t *s_w, uint64_t &total) {
-    const uint64_t inc = wave_scan(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; w++) {
-        const uint64_t x = s_w[w];
-        if (w < (int)(threadIdx.x >> 6)) before += x;
-        all += x;
-    }
-    total = all;
-    return before + inc - v;
 }
 
 __global__ __launch_bounds__(kThreads) void sc_lengths(const uint8_t *__restrict__ buf, uint64_t len, const msj_field *__restrict__ column,
@@ -160,24 +130,7 @@ __global__ __launch_bounds__(1024) void sc_scan(const msj_select_documents_resul
                                                 msj_string_column_result *__restrict__ result) {
     __shared__ uint64_t s_w[16];
     const Head h = load_head(sel, capacity);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t run = 0;
-    for (uint64_t v0 = 0; v0 < h.blocks; v0 += 1024) {
-        const uint64_t v = v0 + threadIdx.x;
-        const uint64_t x = v < h.blocks ? w.bsum[v] : 0, inc = wave_scan(x);
-        __syncthreads();
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        uint64_t before = 0, all = 0;
-#pragma unroll 4
-        for (uint32_t j = 0; j < 16; j++) {
-            const uint64_t t = s_w[j];
-            if (j < wave) before += t;
-            all += t;
-        }
-        if (v < h.blocks) w.bsum[v] = run + before + inc - x;
-        run += all;
-    }
+    const uint64_t run = scan_in_place(w.bsum, h.blocks, s_w);
     if (threadIdx.x != 0) return;
     msj_string_column_result r;
     r.code = h.skip ? h.code : h.over ? MSJ_CAPACITY : bytes_code(run, have_bytes, bytes_capacity);

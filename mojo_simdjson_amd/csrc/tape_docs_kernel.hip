@@ -381,45 +381,40 @@ __global__ __launch_bounds__(kThreads) void td_long_out(const uint8_t *__restric
     long_out_body(buf, len, idx, end, flags, string_buf, string_capacity, w);
 }
 
-static uint64_t most_documents(uint64_t n, uint64_t capacity) {
-    const uint64_t d = n < capacity ? n : capacity;
-    return d ? d : 1;
-}
-
 }  // namespace msj_tdocs
 
 extern "C" uint64_t msj_tape_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity) {
     return msj_tape::layout(nullptr, n, len, msj_tdocs::most_documents(n, capacity)).bytes + 64;
 }
 
-extern "C" int msj_launch_tape_documents(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
-                                         const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
-                                         const uint32_t *d_doc_first, const msj_documents_result *d_docs, const msj_number *d_numbers,
-                                         uint64_t numbers_capacity, const msj_document_verdict *d_verdicts, uint64_t *d_tape,
-                                         uint64_t tape_capacity, uint8_t *d_string_buf, uint64_t string_capacity,
-                                         msj_document_tape *d_doc_tapes, uint64_t capacity, msj_tape_documents_result *d_result, void *d_ws,
-                                         void *stream) {
+extern "C" int msj_launch_tape_documents(const msj_token_view &t, const msj_split_view &sp, const msj_number_view &nv,
+                                         const msj_document_verdict *d_verdicts, uint64_t *d_tape, uint64_t tape_capacity,
+                                         uint8_t *d_string_buf, uint64_t string_capacity, msj_document_tape *d_doc_tapes, uint64_t capacity,
+                                         msj_tape_documents_result *d_result, void *d_ws, void *stream) {
     using namespace msj_tdocs;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Work w = layout(d_ws, n, len, most_documents(n, capacity));
+    const Work w = layout(d_ws, t.n, t.len, most_documents(t.n, capacity));
     const uint32_t nb = w.nb, nb64 = (nb + 63) / 64, nb4096 = (nb64 + 63) / 64;
     if (hipMemsetAsync(w.st, 0, (size_t)(reinterpret_cast<uint8_t *>(w.pos) - reinterpret_cast<uint8_t *>(w.st)), s) != hipSuccess)
         return (int)hipGetLastError();
-    if (n > 0) {
-        hipLaunchKernelGGL(td_sums, dim3(nb), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_type, d_end, d_flags, d_doc_first, d_docs, capacity, w);
-        hipLaunchKernelGGL(td_long_len, dim3(kListBlocks), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_end, d_flags, d_doc_first, d_docs,
-                           capacity, w);
+    if (t.n > 0) {
+        hipLaunchKernelGGL(td_sums, dim3(nb), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_end, t.d_flags, sp.d_doc_first,
+                           sp.d_docs, capacity, w);
+        hipLaunchKernelGGL(td_long_len, dim3(kListBlocks), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_end, t.d_flags, sp.d_doc_first,
+                           sp.d_docs, capacity, w);
     }
-    hipLaunchKernelGGL(td_scan, dim3(1), dim3(1024), 0, s, w, n, d_doc_first, d_docs, capacity, tape_capacity, d_string_buf, string_capacity,
-                       numbers_capacity, d_result);
-    if (n == 0) return (int)hipGetLastError();  // no document: the zero result is all there is
-    hipLaunchKernelGGL(td_pos, dim3(nb), dim3(kThreads), 0, s, n, d_type, d_depth, d_match, d_flags, d_doc_first, d_docs, capacity, w);
+    hipLaunchKernelGGL(td_scan, dim3(1), dim3(1024), 0, s, w, t.n, sp.d_doc_first, sp.d_docs, capacity, tape_capacity, d_string_buf, string_capacity,
+                       nv.numbers_capacity, d_result);
+    if (t.n == 0) return (int)hipGetLastError();  // no document: the zero result is all there is
+    hipLaunchKernelGGL(td_pos, dim3(nb), dim3(kThreads), 0, s, t.n, t.d_type, t.d_depth, t.d_match, t.d_flags, sp.d_doc_first, sp.d_docs, capacity,
+                       w);
     hipLaunchKernelGGL(td_min64, dim3((nb64 + kWaves - 1) / kWaves), dim3(kThreads), 0, s, w.b_min, nb, w.b_min64, w.st);
     hipLaunchKernelGGL(td_min64, dim3((nb4096 + kWaves - 1) / kWaves), dim3(kThreads), 0, s, w.b_min64, nb64, w.b_min4096, w.st);
-    hipLaunchKernelGGL(td_span, dim3((nb + kWaves - 1) / kWaves), dim3(kThreads), 0, s, n, d_type, d_depth, w);
-    hipLaunchKernelGGL(td_emit, dim3(nb), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_type, d_match, d_end, d_flags, d_doc_first, d_docs,
-                       capacity, d_verdicts, d_numbers, numbers_capacity, d_tape, tape_capacity, d_string_buf, string_capacity, d_doc_tapes, w);
-    hipLaunchKernelGGL(td_long_out, dim3(kListBlocks), dim3(kThreads), 0, s, d_buf, len, d_idx, d_end, d_flags, d_string_buf, string_capacity,
-                       d_result, w);
+    hipLaunchKernelGGL(td_span, dim3((nb + kWaves - 1) / kWaves), dim3(kThreads), 0, s, t.n, t.d_type, t.d_depth, w);
+    hipLaunchKernelGGL(td_emit, dim3(nb), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_match, t.d_end, t.d_flags, sp.d_doc_first,
+                       sp.d_docs, capacity, d_verdicts, nv.d_numbers, nv.numbers_capacity, d_tape, tape_capacity, d_string_buf, string_capacity,
+                       d_doc_tapes, w);
+    hipLaunchKernelGGL(td_long_out, dim3(kListBlocks), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.d_end, t.d_flags, d_string_buf,
+                       string_capacity, d_result, w);
     return (int)hipGetLastError();
 }

@@ -260,28 +260,26 @@ extern "C" uint64_t msj_tape_workspace_bytes(uint64_t n, uint64_t len) {
     return msj_tape::layout(nullptr, n, len).bytes + 64;
 }
 
-extern "C" int msj_launch_tape(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
-                               const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
-                               const msj_number *d_numbers, uint64_t numbers_capacity, const msj_validate_result *d_verdict,
-                               uint64_t *d_tape, uint64_t tape_capacity, uint8_t *d_string_buf, uint64_t string_capacity,
-                               msj_tape_result *d_result, void *d_ws, void *stream) {
+extern "C" int msj_launch_tape(const msj_token_view &t, const msj_number_view &nv, const msj_validate_result *d_verdict, uint64_t *d_tape,
+                               uint64_t tape_capacity, uint8_t *d_string_buf, uint64_t string_capacity, msj_tape_result *d_result,
+                               void *d_ws, void *stream) {
     using namespace msj_tape;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Work w = layout(d_ws, n, len);
+    const Work w = layout(d_ws, t.n, t.len);
     const uint32_t nb = w.nb, nb64 = (nb + 63) / 64, nb4096 = (nb64 + 63) / 64;
     if (hipMemsetAsync(w.st, 0, (size_t)(reinterpret_cast<uint8_t *>(w.pos) - reinterpret_cast<uint8_t *>(w.st)), s) != hipSuccess)
         return (int)hipGetLastError();
-    hipLaunchKernelGGL(tape_sums, dim3(nb), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_type, d_end, d_flags, w);
-    hipLaunchKernelGGL(tape_long_len, dim3(kListBlocks), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_end, d_flags, w);
-    hipLaunchKernelGGL(tape_scan, dim3(1), dim3(1024), 0, s, w, n, d_verdict, d_tape, tape_capacity, d_string_buf, string_capacity,
-                       numbers_capacity, d_result);
-    hipLaunchKernelGGL(tape_pos, dim3(nb), dim3(kThreads), 0, s, n, d_type, d_depth, d_match, d_flags, w);
+    hipLaunchKernelGGL(tape_sums, dim3(nb), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_end, t.d_flags, w);
+    hipLaunchKernelGGL(tape_long_len, dim3(kListBlocks), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_end, t.d_flags, w);
+    hipLaunchKernelGGL(tape_scan, dim3(1), dim3(1024), 0, s, w, t.n, d_verdict, d_tape, tape_capacity, d_string_buf, string_capacity,
+                       nv.numbers_capacity, d_result);
+    hipLaunchKernelGGL(tape_pos, dim3(nb), dim3(kThreads), 0, s, t.n, t.d_type, t.d_depth, t.d_match, t.d_flags, w);
     hipLaunchKernelGGL(tape_min64, dim3((nb64 + kWaves - 1) / kWaves), dim3(kThreads), 0, s, w.b_min, nb, w.b_min64, w.st);
     hipLaunchKernelGGL(tape_min64, dim3((nb4096 + kWaves - 1) / kWaves), dim3(kThreads), 0, s, w.b_min64, nb64, w.b_min4096, w.st);
-    hipLaunchKernelGGL(tape_span, dim3((nb + kWaves - 1) / kWaves), dim3(kThreads), 0, s, n, d_type, d_depth, w);
-    hipLaunchKernelGGL(tape_emit, dim3(nb), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_type, d_match, d_end, d_flags, d_numbers,
-                       numbers_capacity, d_tape, tape_capacity, d_string_buf, string_capacity, w);
-    hipLaunchKernelGGL(tape_long_out, dim3(kListBlocks), dim3(kThreads), 0, s, d_buf, len, d_idx, d_end, d_flags, d_string_buf,
+    hipLaunchKernelGGL(tape_span, dim3((nb + kWaves - 1) / kWaves), dim3(kThreads), 0, s, t.n, t.d_type, t.d_depth, w);
+    hipLaunchKernelGGL(tape_emit, dim3(nb), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_match, t.d_end, t.d_flags, nv.d_numbers,
+                       nv.numbers_capacity, d_tape, tape_capacity, d_string_buf, string_capacity, w);
+    hipLaunchKernelGGL(tape_long_out, dim3(kListBlocks), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.d_end, t.d_flags, d_string_buf,
                        string_capacity, w);
     return (int)hipGetLastError();
 }

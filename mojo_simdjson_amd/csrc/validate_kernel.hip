@@ -217,24 +217,22 @@ extern "C" uint64_t msj_validate_workspace_bytes(uint64_t n, uint64_t len) {
     return sizeof(msj_val::State) + 4ull * msj_validate_long_capacity(len) + 4ull * msj_validate_huge_capacity(len) + 4ull * nb + 64;
 }
 
-extern "C" int msj_launch_validate(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
-                                   const int32_t *d_depth, const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags,
-                                   const msj_numbers_result *d_numbers, uint32_t max_depth, msj_validate_result *d_result, void *d_ws,
-                                   void *stream) {
+extern "C" int msj_launch_validate(const msj_token_view &t, const msj_number_view &nv, uint32_t max_depth, msj_validate_result *d_result,
+                                   void *d_ws, void *stream) {
     using namespace msj_val;
     hipStream_t s = static_cast<hipStream_t>(stream);
     State *st = static_cast<State *>(d_ws);
-    const uint32_t long_cap = msj_validate_long_capacity(len), huge_cap = msj_validate_huge_capacity(len);
+    const uint32_t long_cap = msj_validate_long_capacity(t.len), huge_cap = msj_validate_huge_capacity(t.len);
     uint32_t *long_list = reinterpret_cast<uint32_t *>(st + 1);
     uint32_t *huge_list = long_list + long_cap;
     uint32_t *block_esc = huge_list + huge_cap;  // one count per block of val_tokens
-    const uint32_t nb = (uint32_t)((n + 1 + kBlock - 1) / kBlock);  // token n, the end of the stream, is judged too
+    const uint32_t nb = (uint32_t)((t.n + 1 + kBlock - 1) / kBlock);  // token n, the end of the stream, is judged too
     hipLaunchKernelGGL(val_init, dim3(1), dim3(1), 0, s, st);
-    hipLaunchKernelGGL(val_tokens, dim3(nb), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, max_depth,
-                       st, long_list, long_cap, huge_list, huge_cap, block_esc);
-    hipLaunchKernelGGL(val_strings, dim3(kListBlocks), dim3(kThreads), 0, s, d_buf, len, d_idx, d_end, st, long_list, long_cap, huge_list,
+    hipLaunchKernelGGL(val_tokens, dim3(nb), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_depth, t.d_match, t.d_end, t.d_flags,
+                       max_depth, st, long_list, long_cap, huge_list, huge_cap, block_esc);
+    hipLaunchKernelGGL(val_strings, dim3(kListBlocks), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.d_end, st, long_list, long_cap, huge_list,
                        huge_cap);
-    hipLaunchKernelGGL(val_count, dim3(kListBlocks * 4), dim3(kThreads), 0, s, d_type, d_depth, n, st);
-    hipLaunchKernelGGL(val_finish, dim3(1), dim3(kThreads), 0, s, st, d_idx, n, len, d_numbers, block_esc, nb, d_result);
+    hipLaunchKernelGGL(val_count, dim3(kListBlocks * 4), dim3(kThreads), 0, s, t.d_type, t.d_depth, t.n, st);
+    hipLaunchKernelGGL(val_finish, dim3(1), dim3(kThreads), 0, s, st, t.d_idx, t.n, t.len, nv.d_numbers_result, block_esc, nb, d_result);
     return (int)hipGetLastError();
 }

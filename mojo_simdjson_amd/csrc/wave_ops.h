@@ -1,5 +1,6 @@
 // wave_ops.h -- reductions and scans over one wave64 and the padded four-byte load that documents_kernel.hip,
-// numbers_kernel.hip, validate_kernel.hip, validate_docs_kernel.hip and tape_kernel.hip share.  Device code only.
+// numbers_kernel.hip, validate_kernel.hip, validate_docs_kernel.hip and tape_kernel.hip share; a workgroup's counter and
+// the running sum over an array by one workgroup, which the select and column kernels share.  Device code only.
 // (tokens_kernel.hip has its own DPP scans.)  The device code of the four older files is pinned instruction for
 // instruction: see the notes on the forms below.
 #pragma once
@@ -71,6 +72,44 @@ template <class A, class T, int N>
 __device__ __forceinline__ A add_waves_before(__attribute__((maybe_undef)) A sum, const T (&s_w)[N], int wave) {
     for (int w = 0; w < wave; w++) sum += s_w[w];
     return sum;
+}
+
+// One counter for the workgroup, every lane calls: v summed by wave, through s_w (a word per wave no lane still reads; free
+// behind the next barrier) to lane 0, which adds the sum to *counter with one atomic, none when it is 0, and returns it.
+// (One barrier per call: a kernel with two counters calls twice and meets twice, once per workgroup at its end.)
+template <int N>
+__device__ __forceinline__ uint32_t block_counter_add(uint32_t v, uint32_t (&s_w)[N], uint64_t *counter) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x != 0) return 0;
+    for (int w = 1; w < N; w++) v += s_w[w];
+    if (v) atomicAdd(reinterpret_cast<unsigned long long *>(counter), (unsigned long long)v);
+    return v;
+}
+
+// a[0 .. count) becomes its exclusive running sum, by ONE workgroup of 1 024 lanes in chunks of 1 024; -> the total
+template <class T>
+__device__ __forceinline__ uint64_t scan_in_place(T *__restrict__ a, uint64_t count, uint64_t (&s_w)[16]) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t run = 0;
+    for (uint64_t v0 = 0; v0 < count; v0 += 1024) {
+        const uint64_t v = v0 + threadIdx.x;
+        const uint64_t x = v < count ? a[v] : 0, inc = wave_scan(x);
+        __syncthreads();
+        if (lane == 63) s_w[wave] = inc;
+        __syncthreads();
+        uint64_t before = 0, all = 0;
+#pragma unroll 4
+        for (uint32_t j = 0; j < 16; j++) {
+            const uint64_t t = s_w[j];
+            if (j < wave) before += t;
+            all += t;
+        }
+        if (v < count) a[v] = (T)(run + before + inc - x);
+        run += all;
+    }
+    return run;
 }
 
 // bytes a[j .. j + 4) as one word, j a multiple of 4; bytes from n on read as 0
