@@ -367,7 +367,10 @@ def _body(length, unit, bad_at):
 @pytest.mark.parametrize("length", [1023, 1024, 1025, 1026, 4096, 4097, 70000, 1 << 20, (1 << 20) + 1, (1 << 20) + 4097, 3 << 20])
 def test_long_escaped_bodies(dev, oracle, twin, nm, length):
     """Bodies walked by their lane (<= 1024 bytes), by a wave (<= 1 MiB) and by the grid, the bad escape first, last and
-    in the middle; surrogate pairs at every phase of the 64-byte steps and the 4 KiB chunks."""
+    in the middle.  The units repeat from the body's first byte, so the 5- and 7-byte ones reach every phase of the 64-byte
+    steps, but a surrogate pair only ever starts at a multiple of 4 (12 j mod 64), and the damaged pairs sit at j = 0, k // 2
+    and k - 1: three phases.  Every kind of escape at every phase, in front of the closing quote and around the 4 KiB piece
+    borders of a body over 1 MiB is tests/test_escape_phases.py."""
     pair = b"\\ud83d\\ude00"
     for unit in (b"\\nab", b"\\\\\\tq", pair, b"\\u00e9z"):
         for bad_at in (None, "first", "middle", "last"):

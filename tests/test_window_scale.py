@@ -1,12 +1,15 @@
 """The per-window calls -- msj_validate_documents_device, msj_tape_documents_device, msj_select_documents_device -- at the
 sizes where their launches wrap: more blocks than the scan takes in one chunk, more documents than the grid over the
 documents has lanes, more number records and more long bodies than the list kernels have lanes and waves, and a container
-that climbs every level of the minimum tree inside a window of several documents.
+that climbs every level of the minimum tree inside a window of several documents.  And the column calls --
+msj_string_column_device, msj_array_column_device -- past their grids: more blocks of rows than sc_scan takes in one chunk,
+more rows than sc_lengths / sc_copy and ac_rows reach in one trip, a block whose rows are all long escaped bodies.
 
 Nothing here is new machinery: the windows' arrays (tdm.WindowArrays), the host twins (tdm.twin_documents, tdk.twin_window,
 tsm.twin_select), the two ways in (Uploaded / FromChain), the device calls and the whole-array comparisons are those of
-tests/test_validate_documents.py, tests/test_tape_documents.py and tests/test_select_documents.py, and the one-document calls
-go through tests/test_tape.py, tests/test_validate.py and tests/test_numbers.py.  Every comparison is exact.  Every test
+tests/test_validate_documents.py, tests/test_tape_documents.py, tests/test_select_documents.py, tests/test_string_column.py and
+tests/test_array_column.py, and the one-document calls go through tests/test_tape.py, tests/test_validate.py and
+tests/test_numbers.py.  Every comparison is exact.  Every test
 asserts that its input is past the threshold it is named for.  The constants below are mirrors of the kernels' values,
 written by hand: a constant changed here makes the test fail and not pass on an input that no longer reaches it; a constant
 changed in a kernel has to be changed here too.  The expected values of a window are computed once and shared.
@@ -19,11 +22,17 @@ import numpy as np
 import pytest
 
 from mojo_simdjson_amd.document import Document
+from tests import escape_phases as ep
 from tests import helpers
+from tests import tape_reference
+from tests import test_array_column as tacd
+from tests import test_array_column_math as tac
 from tests import test_number_math as tnm
 from tests import test_numbers as tnum
 from tests import test_select_documents as tsd
 from tests import test_select_math as tsm
+from tests import test_string_column as tsc
+from tests import test_string_column_math as tcm
 from tests import test_tape as tt
 from tests import test_tape_documents as ttd
 from tests import test_tape_documents_math as tdk
@@ -35,10 +44,12 @@ from tests import test_validate_math as tvm
 
 BLOCK = 1024                 # tape_block.h: kBlock = kThreads * kPer, the tokens of a workgroup
 SCAN_BLOCKS = 1024           # tape_block.h, scan_blocks: `for (b0 = 0; b0 < w.nb; b0 += 1024)`, blocks per chunk of the running carry
-DOC_GRID = 1024 * 256        # select_kernel.hip / validate_docs_kernel.hip: kGridBlocks = 1024 blocks of kThreads = 256 lanes along k
+DOC_GRID = 1024 * 256        # docs_block.h: row_grid_blocks / validate_docs_kernel.hip: kGridBlocks = 1024 blocks of kThreads = 256 lanes along k
 RECORD_LANES = 512 * 256     # validate_docs_kernel.hip: vd_records is launched with dim3(kListBlocks) = 512 blocks of kThreads lanes
 LIST_WAVES = 512 * 4         # tape_block.h / validate_block.h: kListBlocks = 512 blocks of kWaves = 4 waves, `j += waves`
 NUM_LONG_WAVES = 128 * 4     # numbers_kernel.hip: num_long is launched with dim3(kListBlocks / 4) = 128 blocks of 4 waves
+ROW_BLOCK = 256              # string_column_kernel.hip: kRows, the rows of a workgroup of sc_lengths / sc_copy
+ROW_GRID = 4096 * ROW_BLOCK  # string_column_kernel.hip: kGridBlocks = 4096 blocks of kRows rows, `v += gridDim.x`
 LANE_BODY = 1024             # tape_block.h / validate_block.h: kLaneBody; numbers_kernel.hip: MSJ_SPAN_LONG is over 1024 characters
 
 UINT64_MAX = tvm.UINT64_MAX
@@ -475,3 +486,272 @@ def test_long_numbers_past_the_list_grid(dev):
     want = [tnm.ERR_SYNTAX if j % 7 == 0 else (tnm.ERR_RANGE, tnm.DOUBLE, tnm.DOUBLE, tnm.DOUBLE)[j % 4] for j in range(count)]
     assert kinds.tolist() == want and res.first_error == 1
     assert res.n_errors == sum(1 for k in want if k in tnum.ERRORS)
+
+
+# ---- 4. the column calls past their grids ------------------------------------------------------------------------------------
+
+def device_select_fields(env, x, pointers, capacity):
+    """The real chain and the real select call over the window `x`, verdicts given, nothing waited for -> (arrays, d_sel, d_fields)"""
+    a = tsd.FromChain(env.dev, x.data, False, True)
+    assert a.n == x.w.n
+    d_sel, d_fields = env.dev.select_documents(env.paths(pointers), a.d_buf, a.length, a.d_idx, a.n, a.d_type, a.d_depth, a.d_match, a.d_end,
+                                               a.d_flags, a.d_first, a.d_docs, d_numbers=a.d_numbers, numbers_capacity=a.ncap,
+                                               d_numbers_result=a.d_num, d_verdicts=a.d_verdicts, capacity=capacity, sync=False)
+    return a, d_sel, d_fields
+
+
+@pytest.mark.gpu
+def test_string_column_second_scan_chunk(env):
+    """msj_string_column_device over the scale window: 1 030 blocks of rows, more than the 1 024 block sums scan_in_place
+    takes in sc_scan's first chunk.  "/u/n" (an escaped string on every fifth row, no such field elsewhere, an invalid
+    document every thousandth) and "/id" (numbers, one string at row 3), the select twin's records uploaded and the real
+    chain's, layout-only and with bytes: the whole arrays are the twin's, and every row is the reference's value
+    (scale_selected).  The rows around index 262 144, where the second chunk begins, by name."""
+    x = scale()
+    check_scale_input(x)
+    D = x.w.D
+    assert (D + ROW_BLOCK - 1) // ROW_BLOCK == 1030 > SCAN_BLOCKS and D < ROW_GRID
+    selected, out = scale_selected()
+    ctwin = tcm.load_twin()
+    a, d_sel, d_fields = device_select_fields(env, x, SCALE_PATHS, D + 37)
+    d_buf = tvd.upload(env.dev, x.data)
+    edge = SCAN_BLOCKS * ROW_BLOCK
+    for p, pointer in ((1, "/u/n"), (0, "/id")):
+        assert SCALE_PATHS[p] == pointer
+        records = selected.column(p)[:D].copy()
+        values = [out[(p, k)] for k in range(D)]
+        up_fields, up_sel = tsc.upload_records(env.dev, records)
+        for layout_only in (True, False):
+            want = tcm.twin_column(ctwin, x.data, records, D, layout_only=layout_only)
+            tcm.check_against_definition(want, values, records)
+            tsc.same(tsc.device_column(env.dev, d_buf, len(x.data), up_fields, 0, up_sel, want), want, (pointer, "uploaded", layout_only))
+            tsc.same(tsc.device_column(env.dev, a.d_buf, len(x.data), d_fields, p, d_sel, want), want, (pointer, "chain", layout_only))
+        rows = want.rows()
+        if pointer == "/u/n":
+            assert want.res.n_strings == want.res.n_escaped == len(range(0, D, 5)) and want.res.n_other == 0
+            assert rows[edge - 4:edge + 2] == [b"x\n%d" % (edge - 4), None, None, None, None, b"x\n%d" % (edge + 1)]
+            assert int(want.offsets[edge]) == int(want.offsets[edge + 1]) == sum(len(b"x\n%d" % k) for k in range(0, edge, 5))
+        else:
+            assert rows[:5] == [None, None, None, b"dup", None] and rows[edge - 1:edge + 2] == [None] * 3
+            assert (want.res.n_strings, want.res.total_bytes, want.res.n_other) == (1, 3, D - 1 - int(x.res.n_invalid))
+            assert want.offsets[4:D + 1].tolist() == [3] * (D - 3)
+
+
+WRAP_ROWS = ROW_GRID + 300
+WRAP_PAST = 789                    # k % 1001 of the rows whose span runs past len: (ROW_GRID + 260) % 1001, and no multiple of 11 or 13
+WRAP_UNIT = b"ab\\n\\u00e9cd\\ud83d\\ude00\\\\e"   # an escaped row names 1 .. 3 of these from a unit's first byte: 13 bytes (9 characters) each in the output
+
+
+@functools.lru_cache(maxsize=None)
+def wrap_records():
+    """-> (data, length, records, long_at): WRAP_ROWS hand-made records over a buffer of some 80 KB: plain spans of 0 .. 40
+    bytes cycling; an escaped short span every 11th; a record that is no string (a number's tag, or a code) every 13th; a
+    span past `length` every 1 001st, at k % 1001 == WRAP_PAST -- 1 001 = 7 x 11 x 13, so at a multiple of 1 001 the record
+    would be no string anyway; at this residue (no multiple of 11 or 13 either) it is a string's but for its span, every
+    third of them flagged escaped, and they end past `length` and start past it in turn; 300 empty rows across index ROW_GRID; one plain row of 70 000 bytes and one
+    long escaped row (a body of tests/escape_phases.py) in the second trip.  `length` is 1 000 bytes short of the buffer."""
+    plain = b"abcdefghijklmnopqrstuvwxyz0123456789" * 100
+    units = WRAP_UNIT * 40
+    big = (b"0123456789 plain row " * 3400)[:70000]
+    body = ep.body_of(ep.CARRIED + 61, ep.ESCAPES["pair_twice"], 333)
+    data = plain + units + big + body + b"#" * 1200
+    length = len(data) - 1000
+    E0, P0, L0 = len(plain), len(plain) + len(units), len(plain) + len(units) + len(big)
+    k = np.arange(WRAP_ROWS, dtype=np.int64)
+    b, r = (k * 7) % (len(plain) - 41), k % 41
+    typ, flags, code = np.full(WRAP_ROWS, ord('"'), dtype=np.uint8), np.zeros(WRAP_ROWS, dtype=np.uint8), np.zeros(WRAP_ROWS, dtype=np.uint16)
+    esc = k % 11 == 0
+    b, r = np.where(esc, E0 + ((k // 11) % 30) * len(WRAP_UNIT), b), np.where(esc, (1 + (k // 11) % 3) * len(WRAP_UNIT), r)
+    flags[esc] = tcm.ESCAPED
+    other, coded = k % 26 == 0, k % 26 == 13
+    typ[other], typ[coded], code[coded] = ord("l"), 0, 20
+    flags[other | coded] = 0
+    past = k % 1001 == WRAP_PAST
+    b, r = np.where(past, np.where((k // 1001) % 2 == 0, length - 5, length + 3), b), np.where(past, 10, r)
+    flags[past & ((k // 1001) % 3 == 0)] = tcm.ESCAPED
+    run = (k >= ROW_GRID - 150) & (k < ROW_GRID + 150)
+    b, r = np.where(run, 5 + k % 100, b), np.where(run, 0, r)
+    typ[run], flags[run], code[run] = ord('"'), 0, 0
+    long_at = (ROW_GRID + 200, ROW_GRID + 230)
+    b[long_at[0]], r[long_at[0]], b[long_at[1]], r[long_at[1]] = P0, len(big), L0, len(body)
+    typ[list(long_at)], flags[list(long_at)], code[list(long_at)] = ord('"'), (0, tcm.ESCAPED), 0
+    records = np.zeros(WRAP_ROWS, dtype=tsm.FIELD_DTYPE)
+    records["bits"], records["type"], records["flags"], records["code"] = b.astype(np.uint64) | (r.astype(np.uint64) << np.uint64(32)), typ, flags, code
+    return data, length, records, long_at
+
+
+def restated_column(data, length, records):
+    """The definition of the column in numpy, from the records alone: a row is a string when its record has no code, the
+    string's tag and a span inside `length`; its bytes are its span's, unescaped (tests/tape_reference.py) when the record
+    says escaped; offsets are the running sum of the valid rows' lengths, the bytes their concatenation
+    -> (offsets, valid, bytes)"""
+    b = (records["bits"] & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    r = (records["bits"] >> np.uint64(32)).astype(np.int64)
+    valid = (records["code"] == 0) & (records["type"] == ord('"')) & (b + r <= length)
+    escaped = valid & ((records["flags"] & tcm.ESCAPED) != 0)
+    pool, at = [np.frombuffer(data, dtype=np.uint8)], len(data)
+    src, size = np.where(valid, b, 0), np.where(valid, r, 0)
+    spans = {}
+    for j in np.nonzero(escaped)[0].tolist():   # (a few dozen distinct spans, named over and over)
+        key = (int(b[j]), int(r[j]))
+        if key not in spans:
+            out = tape_reference.unescape(b'"' + data[key[0]:key[0] + key[1]] + b'"', 0)
+            spans[key] = (at, len(out))
+            pool.append(np.frombuffer(out, dtype=np.uint8))
+            at += len(out)
+        src[j], size[j] = spans[key]
+    offsets = np.concatenate([[0], np.cumsum(size)])
+    pool = np.concatenate(pool)
+    take = np.repeat(src - offsets[:-1], size) + np.arange(int(offsets[-1]), dtype=np.int64)
+    return offsets.astype(np.uint64), valid.astype(np.uint8), pool[take]
+
+
+def check_restated(col, data, length, records):
+    offsets, valid, out = restated_column(data, length, records)
+    D = len(records)
+    assert np.array_equal(col.offsets[:D + 1], offsets) and np.array_equal(col.valid[:D], valid)
+    assert (col.res.code, col.res.n_rows, col.res.n_strings, col.res.total_bytes) == (0, D, int(valid.sum()), out.size)
+    assert col.res.n_other == int(((records["code"] == 0) & (valid == 0)).sum())
+    assert col.res.n_escaped == int(((valid == 1) & ((records["flags"] & tcm.ESCAPED) != 0)).sum())
+    if col.data is not None:
+        assert np.array_equal(col.data[:out.size], out)
+    assert col.untouched(D, out.size)
+    return out.size
+
+
+@pytest.mark.gpu
+def test_string_column_grid_wrap(env):
+    """More rows than sc_lengths / sc_copy reach in one trip of `v += gridDim.x` (4 096 blocks of 256 rows), and 4 098 block
+    sums for sc_scan: hand-made records, uploaded.  The whole arrays are the twin's, layout-only and with bytes, and the
+    twin's are the definition's restated in numpy.  With bytes_capacity one short: MSJ_CAPACITY, the true total, nothing
+    written behind the capacity."""
+    data, length, records, long_at = wrap_records()
+    R = len(records)
+    assert R == WRAP_ROWS > ROW_GRID and min(long_at) > ROW_GRID and length + 1000 == len(data)
+    r = (records["bits"] >> np.uint64(32)).astype(np.int64)
+    assert int(r[long_at[0]]) == 70000 and int(r[long_at[1]]) > LANE_BODY and int(records["flags"][long_at[1]]) == tcm.ESCAPED
+    assert bool((r[ROW_GRID - 150:ROW_GRID + 150] == 0).all()) and int((records["code"] != 0).sum()) > R // 30
+    # rows that are no strings through their span alone: a string's record without a code, plain and escaped, in both trips
+    b = (records["bits"] & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    by_span = (records["code"] == 0) & (records["type"] == ord('"')) & (b + r > length)
+    named = ROW_GRID + 260
+    assert named % 1001 == WRAP_PAST and bool(by_span[named]) and int(by_span.sum()) > 900
+    assert int(records["flags"][named]) == tcm.ESCAPED and int((by_span & ((records["flags"] & tcm.ESCAPED) != 0)).sum()) > 300 and int((by_span & (b > length)).sum()) > 400
+    assert int(by_span[:ROW_GRID].sum()) > 900 and bool((b[by_span] + r[by_span] <= len(data)).all())
+    ctwin = tcm.load_twin()
+    d_buf = tvd.upload(env.dev, data)
+    d_fields, d_sel = tsc.upload_records(env.dev, records)
+    for layout_only in (True, False):
+        want = tcm.twin_column(ctwin, data, records, R, length=length, layout_only=layout_only)
+        total = check_restated(want, data, length, records)
+        tsc.same(tsc.device_column(env.dev, d_buf, length, d_fields, 0, d_sel, want), want, layout_only)
+    rows = want.rows()
+    assert rows[long_at[0]] == data[3600 + 40 * len(WRAP_UNIT):][:70000] and rows[ROW_GRID] == b"" and rows[1001] is None
+    assert rows[named] is None and rows[named - 1] is not None and all(rows[j] is None for j in np.nonzero(by_span)[0].tolist())
+    assert want.res.n_other == int(by_span.sum()) + int((records["type"] == ord("l")).sum())
+    assert rows[long_at[1]] == b"x" * (ep.CARRIED + 61) + "\U0001F600\U0001F600".encode() + b"y" * 333
+    assert rows[11] == b"ab\n\xc3\xa9cd\xf0\x9f\x98\x80\\e" * 2 and rows[R - 1] == data[int(records["bits"][R - 1]) & 0xFFFFFFFF:][:(R - 1) % 41]
+    short = tcm.twin_column(ctwin, data, records, R, length=length, bytes_capacity=total - 1)
+    tsc.same(tsc.device_column(env.dev, d_buf, length, d_fields, 0, d_sel, short), short, "one short")
+    assert (short.res.code, short.res.total_bytes) == (MSJ_CAPACITY, total) and short.untouched(R, total - 1)
+    assert np.array_equal(short.offsets, want.offsets) and np.array_equal(short.data[:total - 1], want.data[:total - 1])
+
+
+@pytest.mark.gpu
+def test_string_column_block_of_long_rows(env):
+    """256 + 70 records across a block border that ALL name long escaped spans -- five bodies of 1 025 .. 5 000 raw bytes with
+    their escapes at odd phases (tests/escape_phases.py), each named some 65 times, so every lane of every wave of the first
+    block waits its turn in the ballot loop of sc_lengths / sc_copy, and the same span is walked again and again: the whole
+    arrays are the twin's, and every row is Python's."""
+    bodies = [ep.body_of(63, ep.ESCAPES["pair"], 950), ep.body_of(ep.CARRIED + 57, ep.ESCAPES["pair_twice"], 83),
+              ep.body_of(61, ep.ESCAPES["five_n"], 2400), ep.body_of(ep.CARRIED + 59, ep.ESCAPES["u20ac_twice"], 2900),
+              ep.body_of(4801, ep.ESCAPES["u00e9"], 193)]
+    assert [len(x) for x in bodies] == [1025, 1252, 2467, 4059, 5000]
+    data, starts = b"", []
+    for body in bodies:
+        starts.append(len(data) + 1)
+        data += b'"' + body + b'"'
+    R = ROW_BLOCK + 70
+    records = np.concatenate([tcm.record(starts[k % 5], len(bodies[k % 5]), flags=tcm.ESCAPED) for k in range(R)])
+    ctwin = tcm.load_twin()
+    assert all(ctwin.scm_is_long(records[k:k + 1].ctypes.data, len(data), LANE_BODY) == 1 for k in range(R))
+    d_buf = tvd.upload(env.dev, data)
+    d_fields, d_sel = tsc.upload_records(env.dev, records)
+    texts = [json.loads(b'"' + body + b'"').encode("utf-8") for body in bodies]
+    for layout_only in (True, False):
+        want = tcm.twin_column(ctwin, data, records, R, layout_only=layout_only)
+        assert (want.res.code, want.res.n_strings, want.res.n_escaped) == (0, R, R)
+        assert want.offsets[:R + 1].tolist() == [sum(len(texts[j % 5]) for j in range(k)) for k in range(R + 1)]
+        tsc.same(tsc.device_column(env.dev, d_buf, len(data), d_fields, 0, d_sel, want), want, layout_only)
+    assert want.rows() == [texts[k % 5] for k in range(R)]
+
+
+ARRAY_LINES = DOC_GRID + 700
+
+
+def array_line(k):
+    """Line k of the array window: [] inside the run of 600 rows across DOC_GRID; every 1 000th, at offset 11, invalid;
+    every 9th without "a"; every 7th an "a" that is no array; else k % 4 elements, numbers and short strings (every third
+    string escaped)"""
+    if DOC_GRID - 300 <= k < DOC_GRID + 300:
+        return b'{"a":[]}'
+    if k % 1000 == 11:
+        return b'{"a":[1,tru]}'
+    if k % 9 == 0:
+        return b'{"b":%d}' % k
+    if k % 7 == 0:
+        return (b'{"a":%d}' % k, b'{"a":"s%d"}' % k, b'{"a":{"a":[%d]}}' % k)[k % 3]
+    elements = [b"%d" % (k + j) if (k + j) % 2 else (b'"e\\n%d"' % k if (k + j) % 3 == 0 else b'"s%d"' % (k + j)) for j in range(k % 4)]
+    return b'{"a":[' + b",".join(elements) + b"]}"
+
+
+@functools.lru_cache(maxsize=None)
+def array_window():
+    """-> (Expected, select twin's Selected for "/a" with the verdicts given, {(0, k): (code, value)} held against the reference)"""
+    lines = [array_line(k) for k in range(ARRAY_LINES)]
+    x = Expected(b"\n".join(lines) + b"\n", lines)
+    selected = tsm.twin_select(tsm.load_twin(), x.w, ["/a"], verdicts=x.rows)
+    return x, selected, tsm.check_against_reference(x.w, selected, ["/a"], lines, codes=x.codes)
+
+
+@pytest.mark.gpu
+def test_array_column_row_wrap(env):
+    """More documents than ac_rows has lanes (row_grid_blocks: 1 024 blocks of 256), so its loop makes a second trip and
+    block_counter_add adds a workgroup's counts once behind it; 600 rows without an element across index 262 144.  The select
+    twin's records uploaded and the real chain's: offsets, validity, elements and both results are the twin's, whole arrays
+    with canaries, the twin's are the definition's on every row, and n_arrays, n_other and n_elements are counted in numpy.
+    Then msj_string_column_device over the elements (more than 262 144 of them): the strings of the definition."""
+    x, selected, values = array_window()
+    D = x.w.D
+    assert D == ARRAY_LINES > DOC_GRID and len(x.data) < 8 << 20
+    k = np.arange(D)
+    run = (k >= DOC_GRID - 300) & (k < DOC_GRID + 300)
+    invalid = ~run & (k % 1000 == 11)
+    missing = ~run & ~invalid & (k % 9 == 0)
+    other = ~run & ~invalid & ~missing & (k % 7 == 0)
+    arrays = ~invalid & ~missing & ~other
+    n_elements = int((k % 4)[arrays & ~run].sum())
+    assert [c != 0 for c in x.codes] == invalid.tolist() and int(run.sum()) == 600
+    records = selected.column(0)[:D].copy()
+    vals = [values[(0, j)] for j in range(D)]
+    atwin, ctwin = tac.load_twin(), tcm.load_twin()
+    full = tac.twin_lists(atwin, x.w, records)
+    _, valid, items = tac.check_against_definition(x.w, full, vals)
+    assert valid == arrays.astype(int).tolist() and len(items) == n_elements > DOC_GRID
+    assert (full.res.n_arrays, full.res.n_other, full.res.n_elements) == (int(arrays.sum()), int(other.sum()), n_elements)
+    assert int(full.offsets[DOC_GRID - 300]) == int(full.offsets[DOC_GRID + 300]) and int(full.offsets[DOC_GRID + 302]) > int(full.offsets[DOC_GRID])
+    for chain in (False, True):
+        if chain:
+            a, d_sel, d_fields = device_select_fields(env, x, ["/a"], D + 3)
+        else:
+            a = tsd.Uploaded(env.dev, x.w, x.rows)
+            d_fields, d_sel = tacd.upload_records(env.dev, [records], D)
+        lay = tac.twin_lists(atwin, x.w, records, layout_only=True)
+        assert lay.summary() == full.summary()
+        tacd.same(tacd.device_lists(a, d_fields, 0, d_sel, lay)[0], lay, (chain, "layout only"))
+        got, d_el, d_esel = tacd.device_lists(a, d_fields, 0, d_sel, full)
+        tacd.same(got, full, chain)
+        # the string column over the elements
+        col = tcm.twin_column(ctwin, x.data, full.elements[:n_elements], n_elements)
+        tsc.same(tsc.device_column(env.dev, a.d_buf, len(x.data), d_el.unsqueeze(0), 0, d_esel, col), col, (chain, "strings"))
+    assert col.rows() == [v.encode("utf-8") if isinstance(v, str) else None for v in items] and col.res.n_escaped > 10000
