@@ -4,6 +4,7 @@ Stage 1, then the spans, then the number call, all on the GPU through the C ABI.
 (json.loads, int(), float() with the definition's int64 and finite-range rules: tests/test_number_math.expected) and from
 the host twin of the same arithmetic (tests/number_math_host.cpp).  DERIVED like the token arrays: the definition is
 include/msj_stage1.h's, the reference's own parse_number cannot run here.
+The readers behind the arithmetic (the lane window, the wave steps) at every phase: tests/test_number_phases.py.
 """
 import ctypes
 import json
@@ -38,18 +39,23 @@ def twin():
     return tnm.load_twin()
 
 
-def _on_device(dev, data):
-    """stage 1 + spans on the device: (d_buf, d_idx, n, d_flags)."""
+def _on_device(dev, data, behind=b"", pairs=False):
+    """stage 1 + spans on the device: (d_buf, d_idx, n, d_flags).  behind: bytes that lie in the device tensor past the
+    buffer's end (every call gets len(data)); pairs: the spans of msj_stage2_prep_pairs_device instead of the span call's,
+    nothing waited for in between."""
     import torch
 
-    d_buf = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).to(dev.device)
+    d_buf = torch.from_numpy(np.frombuffer(data + behind, dtype=np.uint8).copy()).to(dev.device)[:len(data)]
     d_idx = torch.empty(len(data) + 3 + 4, dtype=torch.int32, device=dev.device)
     d_res = dev.new_carry()
     dev.index(d_buf, d_idx, d_res)
     r = dev.fetch(d_res)
     assert r.code == 0, r.code
     n = int(r.count)
-    _, d_flags = dev.token_spans(d_buf, len(data), d_idx, n)
+    if pairs:
+        d_flags = dev.stage2_prep_pairs(d_buf, len(data), d_idx, n, spans=True)[4][:n]
+    else:
+        _, d_flags = dev.token_spans(d_buf, len(data), d_idx, n)
     return d_buf, d_idx, n, d_flags
 
 
@@ -60,19 +66,22 @@ def _records(d_numbers, count):
     return bits, (hi & 0xFFFFFFFF).astype(np.uint32), (hi >> np.uint64(32)).astype(np.uint32)
 
 
-def _twin_values(twin, data, starts):
+def _twin_values(twin, data, starts, length=None):
+    """length: the buffer's len where `data` goes on behind it"""
     starts = np.ascontiguousarray(starts, dtype=np.uint64)
     bits = np.zeros(starts.size, dtype=np.uint64)
     kinds = np.zeros(starts.size, dtype=np.uint32)
     paths = np.zeros(3, dtype=np.uint64)
-    twin.nm_convert_batch(data, len(data), starts.ctypes.data, starts.size, bits.ctypes.data, kinds.ctypes.data, paths.ctypes.data)
+    twin.nm_convert_batch(data, len(data) if length is None else length, starts.ctypes.data, starts.size, bits.ctypes.data,
+                          kinds.ctypes.data, paths.ctypes.data)
     return bits, kinds, paths
 
 
-def _check_call(dev, twin, data, where, python_sample=None, seed=0):
-    """Every record against the twin, the counts against a host scan of the flags, (a sample of) the records against
-    Python.  -> (bits, tokens, kinds, result)."""
-    d_buf, d_idx, n, d_flags = _on_device(dev, data)
+def _check_call(dev, twin, data, where, python_sample=None, seed=0, behind=b"", pairs=False, seen=None):
+    """Every record against the twin, the counts against a host scan of the flags and the twin's paths, (a sample of) the
+    records against Python.  -> (bits, tokens, kinds, result).  behind, pairs: _on_device's; seen: a dict that receives
+    what the call saw (idx, flags, the number tokens, the buffer's address)."""
+    d_buf, d_idx, n, d_flags = _on_device(dev, data, behind, pairs)
     d_numbers, res = dev.number_values(d_buf, len(data), d_idx, n, d_flags)
     idx = d_idx[:n].cpu().numpy().view(np.uint32)
     flags = d_flags[:n].cpu().numpy()
@@ -80,12 +89,15 @@ def _check_call(dev, twin, data, where, python_sample=None, seed=0):
     assert res.n_numbers == num_tok.size, where
     bits, tokens, kinds = _records(d_numbers, num_tok.size)
     assert np.array_equal(tokens, num_tok.astype(np.uint32)), where
-    wb, wk, _ = _twin_values(twin, data, idx[num_tok])
+    if seen is not None:
+        seen.update(idx=idx, flags=flags, num_tok=num_tok, address=d_buf.data_ptr())
+    wb, wk, paths = _twin_values(twin, data + behind, idx[num_tok], len(data))
     bad = np.nonzero((wb != bits) | (wk != kinds))[0]
     assert bad.size == 0, (where, [(int(tokens[i]), data[idx[tokens[i]]:idx[tokens[i]] + 40]) for i in bad[:3]])
     err = np.isin(kinds, ERRORS)
     assert res.n_errors == int(err.sum()), where
     assert res.first_error == (int(tokens[np.argmax(err)]) if err.any() else UINT64_MAX), where
+    assert res.n_slow == int(paths[2]), where  # the exact path: the same numbers on the device as in the twin
     # flagged MSJ_SPAN_BAD: a syntax error
     assert (kinds[(flags[num_tok] & 32) != 0] == tnm.ERR_SYNTAX).all(), where
     pick = range(num_tok.size)
