@@ -1073,7 +1073,7 @@ uint64_t msj_string_column_workspace_bytes(uint64_t capacity);
  * against elements_capacity, and rows at or past D are not touched.  For a d_doc_first that is not what the split writes the
  * outputs are unspecified, still in bounds.
  * Out of scope: rows other than a select column's (so no list of lists in one step -- a nested array is an element record of
- * type '['), and any change to the pointer grammar.
+ * type '[', which msj_array_elements_device takes as a row), and any change to the pointer grammar.
  */
 typedef struct msj_array_column_result {   /* 48 bytes */
     int32_t  code;        /* 0; MSJ_CAPACITY (rows > capacity: nothing else written; or n_elements > elements_capacity: offsets /
@@ -1141,7 +1141,8 @@ uint64_t msj_array_column_workspace_bytes(uint64_t n, uint64_t capacity);
  * nothing is launched on either.  Asynchronous on `stream`, no host round trip, workspace in the context.  Safe on ANY arrays
  * and records: every index from a record, d_match or d_end is checked before it is used, the window is read only inside
  * [0, len), and rows at or past R are not touched.
- * Out of scope: a list of lists in one step, rows other than ascending element records, any change to the pointer grammar.
+ * Out of scope: a list of lists in one step (msj_array_elements_device opens a column of '[' records), rows other than
+ * ascending element records, any change to the pointer grammar.
  */
 int32_t msj_select_elements_device(msj_ctx *ctx, const msj_paths *paths,
         const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n,
@@ -1152,6 +1153,67 @@ int32_t msj_select_elements_device(msj_ctx *ctx, const msj_paths *paths,
 /* Device workspace of one msj_select_elements_device call (the context keeps it): two state words per (path, row) and 4 bytes
  * per row, for min(n, capacity) rows. */
 uint64_t msj_select_elements_workspace_bytes(uint64_t n, uint64_t capacity, uint32_t n_paths);
+
+/*
+ * ---- the arrays inside list rows as a list column (DERIVED) --------------------------------------
+ * msj_array_elements_device -- msj_array_column_device with ANY ascending msj_field records as the rows instead of one record
+ * per document: the arrays among the elements of a list column -- a list of lists, "coordinates":[[x,y],[x,y],...] -- or one
+ * path's records of msj_select_elements_device -- a list inside a list of structs, items[*].tags.  The output is again
+ * d_offsets[R + 1], a validity byte per row, the element records back to back and a msj_select_documents_result for them, so
+ * msj_string_column_device, msj_select_elements_device and this call itself run on it unchanged, to any depth.  All on the
+ * device, on the caller's stream, no host round trip.
+ * Inputs: the token arrays and the number records with their result, exactly those the call that wrote the rows ran over;
+ * d_rows / d_rows_select = an array-column call's (or this call's) d_elements / d_elements_select, or d_fields + p * capacity /
+ * d_result of a select-elements call.  R = d_rows_select->n_documents is read on the device.  There is no split and no d_docs:
+ * the window's n stands where a document's e_k stood.
+ *   d_rows_select->code != 0 (a clipped element list arrives this way): d_result is a zero result with that code and nothing
+ *                else is written
+ *   R > capacity: MSJ_CAPACITY with n_rows = R, nothing else written
+ *   order:       a select-elements column holds records with a code (20, 17), whose token is 0xFFFFFFFF.  The rows whose
+ *                record has code == 0 are the LIVE rows; their tokens must ascend strictly over r, compared as uint32
+ *                (array-column output does; so does select-elements output over true element rows: a found value lies inside
+ *                its own element).  Checked on the device, not believed: on a violation code = MSJ_ERR_BAD_ARGUMENT, n_rows = R,
+ *                every count 0, nothing else written -- neither d_valid nor d_offsets
+ * Row r (r < R) is an array, d_valid[r] = 1, iff all of the following hold, each re-checked on the arrays: its record has
+ * code == 0 and type == '['; v = token < n; d_type[v] == '['; m = d_match[v] lies in (v, n).  A row with a code and a row of
+ * any other kind are both invalid and have no elements.
+ * Which row a token belongs to: token i belongs to the LAST live row whose token lies below i, and to that row alone.  For
+ * true rows that is no restriction (siblings are disjoint and ascending); for any other records -- one row inside another,
+ * say -- it makes the output a function of the input: row r sees the tokens i <= the next live row's token only.
+ * The elements of row r are the tokens i that belong to r, in token order, with v < i < m, d_depth[i] == d_depth[v] + 1,
+ * d_type[i - 1] '[' or ',' and d_type[i] neither ']' nor '}': msj_array_column_device's element test.
+ *   d_offsets    d_offsets[r] = the number of elements of the rows in front of r, d_offsets[R] = n_elements; a row with a code,
+ *                or with token >= n, has the next row's offset.  uint64, capacity + 1 entries; those past R are not written
+ *   d_valid      capacity entries; those at or past R are not written
+ *   d_elements   as in msj_array_column_device: the record of the value at token i (MSJ_FIELD_NO_BITS and the number-record
+ *                search unchanged), clipped at elements_capacity -- then the offsets and d_valid are complete, the code is
+ *                MSJ_CAPACITY and n_elements is exact.  d_elements == NULL (with elements_capacity 0) is the layout-only form
+ *   d_elements_select  NULL, or written wherever d_result is: code = this call's code, n_documents = n_found = n_elements (0 on
+ *                a stop), n_paths = 1, n_no_bits as in d_result
+ * d_result: a msj_array_column_result -- code; n_rows = R; n_arrays the rows with d_valid = 1; n_elements; n_other the rows
+ * whose record has code 0 and that are no array; n_no_bits the element records written with MSJ_FIELD_NO_BITS.  R == 0 writes
+ * d_offsets[0] = 0 and a zero result; with n == 0 no row is valid.
+ * Arguments: d_idx, d_depth, d_match, d_end, d_numbers, d_rows, d_elements 16-byte aligned; d_type, d_flags, d_numbers_result,
+ * d_rows_select, d_offsets, d_result, d_elements_select 8-byte; d_valid any.  NULL ctx / d_result / d_rows_select, a NULL token
+ * array with n > 0, NULL d_rows / d_offsets / d_valid with capacity > 0, NULL d_elements with elements_capacity > 0, NULL
+ * d_numbers with numbers_capacity > 0, d_elements_select == d_rows_select, d_elements == d_rows, or an off-grid pointer:
+ * MSJ_ERR_BAD_ARGUMENT; n >= 2^31: MSJ_CAPACITY.  The checks come in msj_array_column_device's order -- missing arrays, the
+ * size, then outputs and alignment -- and nothing is launched on either.  Asynchronous on `stream`, no host round trip,
+ * workspace in the context.  Safe on ANY arrays and records: every index from a record or from d_match is checked before it is
+ * used, every store to d_elements is checked against elements_capacity, and rows at or past R are not touched.
+ * Out of scope: any change to the pointer grammar (no '*', no indices), an object's keys as rows, typed numeric columns.
+ */
+int32_t msj_array_elements_device(msj_ctx *ctx,
+        const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
+        const uint32_t *d_end, const uint8_t *d_flags,
+        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+        const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
+        uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+        msj_field *d_elements, uint64_t elements_capacity,
+        msj_array_column_result *d_result, msj_select_documents_result *d_elements_select, void *stream);
+/* Device workspace of one msj_array_elements_device call (the context keeps it): 8 bytes per row of capacity and 8 per 256 of
+ * them, 24 per row of min(n, capacity), 4 per 1 024 tokens. */
+uint64_t msj_array_elements_workspace_bytes(uint64_t n, uint64_t capacity);
 
 /*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors

@@ -314,6 +314,12 @@ def load():
                                  ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_select_elements_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_select_elements_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
+    lib.msj_array_elements_device.restype = ctypes.c_int32
+    lib.msj_array_elements_device.argtypes = [ctypes.c_void_p, u32p, ctypes.c_uint64] + [ctypes.c_void_p] * 6 + \
+        [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_array_elements_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_array_elements_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

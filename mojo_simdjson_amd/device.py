@@ -629,6 +629,61 @@ class Stage1Device:
             return d_result, d_fields
         return _lib.MsjSelectDocumentsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()), d_fields
 
+    def array_elements(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_rows, d_rows_select, d_numbers=None, numbers_capacity=0,
+                       d_numbers_result=None, d_offsets=None, d_valid=None, d_elements=None, capacity=None, elements_capacity=None,
+                       elements=True, d_result=None, d_elements_select=None, sync=True):
+        """The arrays inside list rows as a list column (``msj_array_elements_device``): ``array_column`` with element records
+        as the rows -- a list of lists, or a list inside a list of structs.  The token arrays and the number records with
+        their result: those the call that wrote the rows ran over; d_rows: ``array_column``'s (or this call's) d_elements, or
+        one path of ``select_elements``' d_fields, int64 of shape (rows, 2); d_rows_select: the device
+        ``msj_select_documents_result`` that goes with them, read on the device.  d_offsets: int64 tensor of capacity + 1
+        entries, d_valid: uint8 tensor of capacity entries (default: new ones, capacity = the rows of d_rows); d_elements:
+        int64 tensor of shape (elements_capacity, 2) (default: its rows).  Without a d_elements of the caller's, one of
+        ``elements_capacity`` records is made, and without that number either it is sized from a layout-only first call,
+        whose 48-byte result is waited for.  elements=False: the layout-only form alone (d_elements None).
+        d_elements_select: uint8[48] that receives the ``msj_select_documents_result`` of the element records (default: a
+        new one).  Returns (``MsjArrayColumnResult``, d_offsets, d_valid, d_elements, d_elements_select) -- blocking for the
+        48-byte result; with sync=False the device tensor that holds it, nothing waited for."""
+        if d_rows.stride(-1) != 1 or (d_rows.shape[0] > 1 and d_rows.stride(0) != 2):
+            raise ValueError("the records of the rows must be contiguous")
+        n, numbers_capacity = int(n), int(numbers_capacity)
+        if capacity is None:
+            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_rows.shape[0]
+        capacity = int(capacity)
+        if d_offsets is None:
+            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
+        if d_valid is None:
+            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
+        if d_result is None:
+            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        if d_elements_select is None:
+            d_elements_select = torch.zeros(48, dtype=torch.uint8, device=self.device)
+
+        def call(d_out, room):
+            rc = self.lib.msj_array_elements_device(
+                self.ctx, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
+                _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
+                _ptr(d_numbers_result) if d_numbers_result is not None else None, _ptr(d_rows), _ptr(d_rows_select), _ptr(d_offsets),
+                _ptr(d_valid), capacity, _ptr(d_out) if d_out is not None else None, int(room), _ptr(d_result), _ptr(d_elements_select),
+                self._stream())
+            if rc != 0:
+                raise RuntimeError(f"msj_array_elements_device failed: {rc}")
+
+        def read():
+            return _lib.MsjArrayColumnResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
+
+        if not elements:
+            d_elements, elements_capacity = None, 0
+        elif d_elements is None:
+            if elements_capacity is None:
+                call(None, 0)
+                elements_capacity = read().n_elements
+            d_elements = torch.empty((max(int(elements_capacity), 1), 2), dtype=torch.int64, device=self.device)
+        elif elements_capacity is None:
+            elements_capacity = d_elements.shape[0]
+        call(d_elements, elements_capacity)
+        return (read() if sync else d_result), d_offsets, d_valid, d_elements, d_elements_select
+
     def parse_document(self, d_buf, length, max_depth=100, exact_strings=False):
         """The whole chain for one document in a device buffer: stage 1, ``stage2_prep`` with partners, ``number_values``,
         ``validate`` and ``tape`` enqueued on one stream.  Returns stage 1's code if that is not 0, else

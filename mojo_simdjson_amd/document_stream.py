@@ -101,15 +101,42 @@ def _string_column(dev, d_window, length, d_fields, p, d_select, rows, bytes_cap
     return d_off, d_bytes[:int(res.total_bytes)], d_valid[:rows].view(torch.bool)
 
 
-class ListColumn:
-    """One path's arrays as a list column ON THE DEVICE (``Window.elements``).  offsets int64[D + 1]; fields int64[n_elements,
-    2], one ``msj_field`` per element back to back -- row k's elements are fields[offsets[k]:offsets[k + 1]]; valid bool[D],
-    False where the value is no array, the key is missing or the document has a verdict code (the row is empty then);
-    d_select uint8[48], the ``msj_select_documents_result`` of the element records.  Like every array a Window carries, the
-    window's own arrays are reused by the next window: use the column before the iterator advances."""
+def _array_elements(window, d_rows, d_rows_select, rows, elements_capacity, parent, what):
+    """``array_elements`` over `rows` records with an element buffer that starts from a guess and, when the call says it was
+    too small, is made as large as the call asks once -> ``ListColumn`` with `parent`"""
+    w = window
+    dvc = d_rows.device
+    if rows == 0:
+        d_rows = torch.zeros((1, 2), dtype=torch.int64, device=dvc)
+    d_off = torch.empty(rows + 1, dtype=torch.int64, device=dvc)
+    d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=dvc)
+    d_esel = torch.zeros(48, dtype=torch.uint8, device=dvc)
+    room = min(w.n_tokens, 4 * rows + 4096) if elements_capacity is None else int(elements_capacity)
+    for _ in range(2):
+        res, _, _, d_elements, _ = w.dev.array_elements(
+            w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_rows, d_rows_select, d_numbers=w.d_numbers,
+            numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, d_offsets=d_off, d_valid=d_valid, capacity=rows,
+            elements_capacity=room, d_elements_select=d_esel)
+        if res.code != errors.CAPACITY or res.n_rows > rows:
+            break
+        room = int(res.n_elements)
+    if res.code != 0:
+        raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be laid out")
+    return ListColumn(w, d_off, d_elements[:int(res.n_elements)], d_valid[:rows].view(torch.bool), d_esel, parent)
 
-    def __init__(self, window, offsets, fields, valid, d_select):
+
+class ListColumn:
+    """Arrays as a list column ON THE DEVICE (``Window.elements``, ``ListColumn.elements``, ``ElementFields.elements``).
+    offsets int64[rows + 1]; fields int64[n_elements, 2], one ``msj_field`` per element back to back -- row k's elements are
+    fields[offsets[k]:offsets[k + 1]]; valid bool[rows], False where the value is no array, the key is missing or the
+    document has a verdict code (the row is empty then); d_select uint8[48], the ``msj_select_documents_result`` of the
+    element records; parent, the ``ListColumn`` or ``ElementFields`` whose records are this column's rows -- None for
+    ``Window.elements``, whose rows are the documents.  Like every array a Window carries, the window's own arrays are reused
+    by the next window: use the column before the iterator advances."""
+
+    def __init__(self, window, offsets, fields, valid, d_select, parent=None):
         self.window, self.offsets, self.fields, self.valid, self.d_select = window, offsets, fields, valid, d_select
+        self.parent = parent
 
     @property
     def n_elements(self):
@@ -155,6 +182,14 @@ class ListColumn:
             raise DocumentStreamError(code, f"window at {w.base}: the fields of the elements could not be selected")
         return ElementFields(self, paths, d_fields[:, :self.n_elements], res)
 
+    def elements(self, elements_capacity=None):
+        """The arrays among this column's elements as a list column of their own -- a list of lists -- ON THE DEVICE
+        (``msj_array_elements_device``) -> ``ListColumn`` with one row per element of this column, aligned with this column's
+        offsets; an element that is no array is a row that is not valid.  The element buffer starts from a guess
+        (elements_capacity: the caller's) and is grown once, as in ``Window.elements``."""
+        return _array_elements(self.window, self.fields, self.d_select, self.n_elements, elements_capacity, self,
+                               "the arrays among the elements")
+
 
 class ElementFields:
     """Fields by path inside the elements of a ``ListColumn`` ON THE DEVICE (``ListColumn.select``).  fields int64[n_paths,
@@ -185,6 +220,15 @@ class ElementFields:
         d_fields = self.fields if self.n_elements else torch.zeros((self.fields.shape[0], 1, 2), dtype=torch.int64, device=self.fields.device)
         return _string_column(w.dev, w.d_window, w.length, d_fields, p, self.d_select, self.n_elements, bytes_capacity,
                               f"window at {w.base}: the strings of path {p} of the elements")
+
+    def elements(self, path_or_index, elements_capacity=None):
+        """The arrays of one path as a list column -- ``items[*].tags`` -- ON THE DEVICE (``msj_array_elements_device``) ->
+        ``ListColumn`` with one row per element of the list column the fields were selected in; a missing key and a value
+        that is no array are rows that are not valid.  The element buffer starts from a guess (elements_capacity: the
+        caller's) and is grown once, as in ``Window.elements``."""
+        p = self.paths.index(path_or_index)
+        return _array_elements(self.list_column.window, self.fields[p], self.d_select, self.n_elements, elements_capacity, self,
+                               f"the arrays of path {p} of the elements")
 
     def values(self, path_or_index):
         """The values of one path as a Python list, one per element: None where the record has a code, see ``field_value``."""
