@@ -1201,7 +1201,8 @@ uint64_t msj_select_elements_workspace_bytes(uint64_t n, uint64_t capacity, uint
  * size, then outputs and alignment -- and nothing is launched on either.  Asynchronous on `stream`, no host round trip,
  * workspace in the context.  Safe on ANY arrays and records: every index from a record or from d_match is checked before it is
  * used, every store to d_elements is checked against elements_capacity, and rows at or past R are not touched.
- * Out of scope: any change to the pointer grammar (no '*', no indices), an object's keys as rows, typed numeric columns.
+ * Out of scope: any change to the pointer grammar (no '*', no indices), typed numeric columns.  (An object's members as
+ * rows: msj_object_entries_device.)
  */
 int32_t msj_array_elements_device(msj_ctx *ctx,
         const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
@@ -1214,6 +1215,79 @@ int32_t msj_array_elements_device(msj_ctx *ctx,
 /* Device workspace of one msj_array_elements_device call (the context keeps it): 8 bytes per row of capacity and 8 per 256 of
  * them, 24 per row of min(n, capacity), 4 per 1 024 tokens. */
 uint64_t msj_array_elements_workspace_bytes(uint64_t n, uint64_t capacity);
+
+/*
+ * ---- an object's members as a map column (DERIVED) ------------------------------------------------
+ * msj_object_entries_device -- msj_array_elements_device with OBJECTS as the rows and two records per entry: an object whose
+ * keys are data, not schema -- "attrs":{"color":"red","size":"L"}, "counts":{"2024-01-01":3,...}, a map of maps -- as
+ * d_offsets[R + 1], a validity byte per row and, back to back, the key's record in d_keys and the value's in d_values at the
+ * same position.  Both record arrays come with a msj_select_documents_result, so msj_string_column_device runs on the keys
+ * and msj_array_elements_device, msj_select_elements_device and this call itself on the values, unchanged.  All on the
+ * device, on the caller's stream, no host round trip.
+ * Inputs: the token arrays and the number records with their result, exactly those the call that wrote the rows ran over;
+ * d_rows / d_rows_select = ANY msj_field records with their select result: one path's column of msj_select_documents_device
+ * (d_fields + p * capacity, its d_result: the rows are the documents), the d_elements / d_elements_select of an array call,
+ * one path of msj_select_elements_device, or this call's own d_values / d_values_select.  R = d_rows_select->n_documents is
+ * read on the device.  There is no split and no d_docs: the window's n stands where a document's e_k stood.
+ *   d_rows_select->code != 0: d_result is a zero result with that code and nothing else is written
+ *   R > capacity: MSJ_CAPACITY with n_rows = R, nothing else written
+ *   order:       the rows whose record has code == 0 are the LIVE rows; their tokens must ascend strictly over r, compared as
+ *                uint32.  Checked on the device, not believed: on a violation code = MSJ_ERR_BAD_ARGUMENT, n_rows = R, every
+ *                count 0, nothing else written -- neither d_valid nor d_offsets
+ *   on every stop only d_result and the two select results (when given) are written
+ * Row r (r < R) is an object, d_valid[r] = 1, iff all of the following hold, each re-checked on the arrays: its record has
+ * code == 0 and type == '{'; v = token < n; d_type[v] == '{'; m = d_match[v] lies in (v, n).  Every other row is invalid and
+ * has no entries.
+ * Which row a token belongs to: token i belongs to the LAST live row whose token lies below i, and to that row alone.
+ * The entries of row r are the tokens i that belong to r, in token order, with v < i, i + 2 < m, d_depth[i] == d_depth[v] + 1,
+ * d_type[i] == '"' and d_type[i + 1] == ':'.  For entry number e, counted over the window, d_keys[e] is the record of the value
+ * at token i -- a string record: the raw span, MSJ_SPAN_ESCAPED in flags -- and d_values[e] the record of the value at token
+ * i + 2, both as msj_select_documents_device writes a value (MSJ_FIELD_NO_BITS and the number-record search unchanged).
+ * Duplicate keys are all kept, in document order; {} is a valid row without entries.  Rows in a document with a verdict code
+ * and malformed members ({"a":}) give unspecified, in-bounds output.
+ *   d_offsets    d_offsets[r] = the number of entries in front of row r -- for a live row with token < n the entries whose key
+ *                token is at or below the row's token --, d_offsets[R] = n_entries; a row with a code, or with token >= n, has
+ *                the next row's offset.  uint64, capacity + 1 entries; those past R are not written
+ *   d_valid      capacity entries; those at or past R are not written
+ *   d_keys, d_values  records at or past min(n_entries, entries_capacity) are not written; with n_entries > entries_capacity the
+ *                offsets and d_valid are complete, the code is MSJ_CAPACITY and n_entries is exact.  Both NULL (with
+ *                entries_capacity 0) is the layout-only form
+ *   d_keys_select, d_values_select  each NULL, or written wherever d_result is: code = this call's code, n_documents = n_found =
+ *                n_entries (0 on a stop), n_paths = 1, n_no_bits 0 for the keys and d_result's for the values
+ * d_result: a msj_object_entries_result -- code; n_rows = R; n_objects the rows with d_valid = 1; n_entries; n_other the live
+ * rows that are no object; n_no_bits the value records written with MSJ_FIELD_NO_BITS.  R == 0 writes d_offsets[0] = 0 and a
+ * zero result; with n == 0 no row is valid.
+ * Arguments: d_idx, d_depth, d_match, d_end, d_numbers, d_rows, d_keys, d_values 16-byte aligned; d_type, d_flags,
+ * d_numbers_result, d_rows_select, d_offsets, d_result, d_keys_select, d_values_select 8-byte; d_valid any.  NULL ctx /
+ * d_result / d_rows_select, a NULL token array with n > 0, NULL d_rows / d_offsets / d_valid with capacity > 0, NULL d_keys with
+ * entries_capacity > 0, exactly one of d_keys / d_values NULL, NULL d_numbers with numbers_capacity > 0, d_keys, d_values or a
+ * select result that is the rows, their select result or each other, or an off-grid pointer: MSJ_ERR_BAD_ARGUMENT; n >= 2^31:
+ * MSJ_CAPACITY.  The checks come in msj_array_elements_device's order -- missing arrays, the size, then outputs and alignment
+ * -- and nothing is launched on either.  Asynchronous on `stream`, no host round trip, workspace in the context.  Safe on ANY
+ * arrays and records: every index from a record or from d_match is checked before it is used, tokens i + 1 and i + 2 are read
+ * only below n, every store to d_keys / d_values is checked against entries_capacity, and rows at or past R are not touched.
+ * Out of scope: any change to the pointer grammar, lookup of a run-time key, de-duplicating keys, typed numeric columns.
+ */
+typedef struct msj_object_entries_result {   /* 48 bytes; the layout of msj_array_column_result */
+    int32_t  code;          /* 0, MSJ_CAPACITY, MSJ_ERR_BAD_ARGUMENT (the order), or the code of d_rows_select */
+    uint32_t flags;         /* 0 */
+    uint64_t n_rows;        /* R */
+    uint64_t n_objects;     /* rows with d_valid = 1 */
+    uint64_t n_entries;     /* entries of all rows, exact also when they were clipped */
+    uint64_t n_other;       /* live rows that are no object */
+    uint64_t n_no_bits;     /* value records written with MSJ_FIELD_NO_BITS */
+} msj_object_entries_result;
+int32_t msj_object_entries_device(msj_ctx *ctx,
+        const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth, const uint32_t *d_match,
+        const uint32_t *d_end, const uint8_t *d_flags,
+        const msj_number *d_numbers, uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result,
+        const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
+        uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+        msj_field *d_keys, msj_field *d_values, uint64_t entries_capacity,
+        msj_object_entries_result *d_result,
+        msj_select_documents_result *d_keys_select, msj_select_documents_result *d_values_select, void *stream);
+/* Device workspace of one msj_object_entries_device call (the context keeps it): msj_array_elements_workspace_bytes' sizes. */
+uint64_t msj_object_entries_workspace_bytes(uint64_t n, uint64_t capacity);
 
 /*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors

@@ -6,3 +6,12 @@ indexer) rebuilt as hand-written HIP for gfx950 behind a C ABI
 """
 from . import errors  # noqa: F401
 from .dom_parser_implementation import DomParserImplementation  # noqa: F401
+
+
+def __getattr__(name):
+    # the columns of the document stream, without importing torch until one of them is asked for
+    if name in ("DocumentStream", "ListColumn", "ElementFields", "MapColumn"):
+        from . import document_stream
+
+        return getattr(document_stream, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

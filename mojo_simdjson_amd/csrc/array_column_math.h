@@ -37,13 +37,14 @@ struct Desc {
 MSJ_HD Desc no_array() { return Desc{0xFFFFFFFFu, 0u, 0, 0u}; }
 // One record of the column against the arrays; [f, e) is its document, bounds_ok what document_bounds said of it.  Every
 // clause is checked on the arrays, none believed from the record: the token lies in the document, is a '[' and has its
-// partner behind it inside the document.  other: the record has code 0 and the row is no array
+// partner behind it inside the document.  other: the record has code 0 and the row is no array.  row_of_kind: the same
+// test for a row that opens with `container` -- '[' here, '{' for msj_object_entries_device (object_entries_math.h)
 template <class Field>
-MSJ_HD Desc row_of(const Field &r, bool bounds_ok, uint64_t f, uint64_t e, const uint8_t *type, const int32_t *depth, const uint32_t *match,
-                   bool &other) {
+MSJ_HD Desc row_of_kind(const Field &r, uint32_t container, bool bounds_ok, uint64_t f, uint64_t e, const uint8_t *type, const int32_t *depth,
+                        const uint32_t *match, bool &other) {
     Desc d = no_array();
     const uint64_t v = r.token;
-    if (r.code == 0 && r.type == '[' && bounds_ok && v >= f && v < e && type[v] == '[') {  // (e <= T <= n: v indexes the arrays)
+    if (r.code == 0 && r.type == container && bounds_ok && v >= f && v < e && type[v] == container) {  // (e <= T <= n: v indexes the arrays)
         const uint32_t m = match[v];
         if (m != kNoPartner && (uint64_t)m > v && (uint64_t)m < e) {
             d.v = (uint32_t)v, d.m = m;
@@ -53,6 +54,11 @@ MSJ_HD Desc row_of(const Field &r, bool bounds_ok, uint64_t f, uint64_t e, const
     }
     other = r.code == 0 && !d.valid;
     return d;
+}
+template <class Field>
+MSJ_HD Desc row_of(const Field &r, bool bounds_ok, uint64_t f, uint64_t e, const uint8_t *type, const int32_t *depth, const uint32_t *match,
+                   bool &other) {
+    return row_of_kind(r, '[', bounds_ok, f, e, type, depth, match, other);
 }
 
 // ---- the element test -----------------------------------------------------------------------------------------------------

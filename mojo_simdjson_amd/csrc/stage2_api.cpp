@@ -1,7 +1,7 @@
 // stage2_api.cpp -- extern "C" entry points of everything that runs behind stage 1 (include/msj_stage1.h): tokens, spans,
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
 // window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
-// elements, the arrays inside list rows.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// elements, the arrays inside list rows, an object's members as a map column.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
 // see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
 #include <new>
 
@@ -462,6 +462,31 @@ int32_t msj_array_elements_device(msj_ctx *ctx, const uint32_t *d_idx, uint64_t 
     if (rc != MSJ_SUCCESS) return rc;
     return launched(msj_launch_array_elements(t, nv, d_rows, d_rows_select, d_offsets, d_valid, capacity, d_elements, elements_capacity, d_result,
                                               d_elements_select, ctx->aelem_ws.p, stream));
+}
+
+int32_t msj_object_entries_device(msj_ctx *ctx, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const int32_t *d_depth,
+                                  const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags, const msj_number *d_numbers,
+                                  uint64_t numbers_capacity, const msj_numbers_result *d_numbers_result, const msj_field *d_rows,
+                                  const msj_select_documents_result *d_rows_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+                                  msj_field *d_keys, msj_field *d_values, uint64_t entries_capacity, msj_object_entries_result *d_result,
+                                  msj_select_documents_result *d_keys_select, msj_select_documents_result *d_values_select, void *stream) {
+    const msj_token_view t{nullptr, 0, d_idx, n, d_type, d_depth, d_match, d_end, d_flags};  // (the call reads no byte of the window)
+    const msj_number_view nv{d_numbers, numbers_capacity, d_numbers_result};
+    if (!ctx || !d_result || !d_rows_select) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && !arrays_present(t)) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && (!d_rows || !d_offsets || !d_valid)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((entries_capacity > 0 && !d_keys) || (d_keys == nullptr) != (d_values == nullptr) || !records_present(nv)) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(t)) return MSJ_CAPACITY;
+    if (d_keys_select == d_rows_select || d_values_select == d_rows_select || (d_keys_select && d_keys_select == d_values_select))
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (d_keys && (d_keys == d_rows || d_values == d_rows || d_keys == d_values)) return MSJ_ERR_BAD_ARGUMENT;
+    if (!is_aligned(t) || !is_aligned(nv) || !all_aligned(16, d_rows, d_keys, d_values) ||
+        !all_aligned(8, d_rows_select, d_offsets, d_result, d_keys_select, d_values_select))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->oent_ws, msj_object_entries_workspace_bytes(n, capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_object_entries(t, nv, d_rows, d_rows_select, d_offsets, d_valid, capacity, d_keys, d_values, entries_capacity,
+                                              d_result, d_keys_select, d_values_select, ctx->oent_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

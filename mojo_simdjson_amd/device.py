@@ -684,6 +684,67 @@ class Stage1Device:
         call(d_elements, elements_capacity)
         return (read() if sync else d_result), d_offsets, d_valid, d_elements, d_elements_select
 
+    def object_entries(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_rows, d_rows_select, d_numbers=None, numbers_capacity=0,
+                       d_numbers_result=None, d_offsets=None, d_valid=None, d_keys=None, d_values=None, capacity=None, entries_capacity=None,
+                       entries=True, d_result=None, d_keys_select=None, d_values_select=None, sync=True):
+        """An object's members as a map column (``msj_object_entries_device``): ``array_elements`` with objects as the rows and
+        two records per entry.  The token arrays and the number records with their result: those the call that wrote the rows
+        ran over; d_rows: any ``msj_field`` records, int64 of shape (rows, 2) -- one path of ``select_documents``' d_fields (the
+        rows are the documents), the d_elements of an array call, one path of ``select_elements``' d_fields, or this call's own
+        d_values; d_rows_select: the device ``msj_select_documents_result`` that goes with them, read on the device.
+        d_offsets: int64 tensor of capacity + 1 entries, d_valid: uint8 tensor of capacity entries (default: new ones,
+        capacity = the rows of d_rows); d_keys, d_values: int64 tensors of shape (entries_capacity, 2), both or neither
+        (default: their rows).  Without record tensors of the caller's, two of ``entries_capacity`` records are made, and
+        without that number either they are sized from a layout-only first call, whose 48-byte result is waited for.
+        entries=False: the layout-only form alone (d_keys and d_values None).  d_keys_select, d_values_select: uint8[48] each,
+        the ``msj_select_documents_result`` of the key and of the value records (default: new ones).  Returns
+        (``MsjObjectEntriesResult``, d_offsets, d_valid, d_keys, d_values, d_keys_select, d_values_select) -- blocking for the
+        48-byte result; with sync=False the device tensor that holds it, nothing waited for."""
+        if d_rows.stride(-1) != 1 or (d_rows.shape[0] > 1 and d_rows.stride(0) != 2):
+            raise ValueError("the records of the rows must be contiguous")
+        if (d_keys is None) != (d_values is None):
+            raise ValueError("d_keys and d_values come together")
+        n, numbers_capacity = int(n), int(numbers_capacity)
+        if capacity is None:
+            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_rows.shape[0]
+        capacity = int(capacity)
+        if d_offsets is None:
+            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
+        if d_valid is None:
+            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
+        if d_result is None:
+            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        if d_keys_select is None:
+            d_keys_select = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        if d_values_select is None:
+            d_values_select = torch.zeros(48, dtype=torch.uint8, device=self.device)
+
+        def call(d_k, d_v, room):
+            rc = self.lib.msj_object_entries_device(
+                self.ctx, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
+                _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
+                _ptr(d_numbers_result) if d_numbers_result is not None else None, _ptr(d_rows), _ptr(d_rows_select), _ptr(d_offsets),
+                _ptr(d_valid), capacity, _ptr(d_k) if d_k is not None else None, _ptr(d_v) if d_v is not None else None, int(room),
+                _ptr(d_result), _ptr(d_keys_select), _ptr(d_values_select), self._stream())
+            if rc != 0:
+                raise RuntimeError(f"msj_object_entries_device failed: {rc}")
+
+        def read():
+            return _lib.MsjObjectEntriesResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
+
+        if not entries:
+            d_keys, d_values, entries_capacity = None, None, 0
+        elif d_keys is None:
+            if entries_capacity is None:
+                call(None, None, 0)
+                entries_capacity = read().n_entries
+            d_keys = torch.empty((max(int(entries_capacity), 1), 2), dtype=torch.int64, device=self.device)
+            d_values = torch.empty((max(int(entries_capacity), 1), 2), dtype=torch.int64, device=self.device)
+        elif entries_capacity is None:
+            entries_capacity = min(d_keys.shape[0], d_values.shape[0])
+        call(d_keys, d_values, entries_capacity)
+        return (read() if sync else d_result), d_offsets, d_valid, d_keys, d_values, d_keys_select, d_values_select
+
     def parse_document(self, d_buf, length, max_depth=100, exact_strings=False):
         """The whole chain for one document in a device buffer: stage 1, ``stage2_prep`` with partners, ``number_values``,
         ``validate`` and ``tape`` enqueued on one stream.  Returns stage 1's code if that is not 0, else

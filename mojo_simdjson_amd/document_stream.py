@@ -125,8 +125,78 @@ def _array_elements(window, d_rows, d_rows_select, rows, elements_capacity, pare
     return ListColumn(w, d_off, d_elements[:int(res.n_elements)], d_valid[:rows].view(torch.bool), d_esel, parent)
 
 
+def _object_entries(window, d_rows, d_rows_select, rows, entries_capacity, parent, what):
+    """``object_entries`` over `rows` records with key and value buffers that start from a guess and, when the call says they
+    were too small, are made as large as the call asks once -> ``MapColumn`` with `parent`"""
+    w = window
+    dvc = d_rows.device
+    if rows == 0:
+        d_rows = torch.zeros((1, 2), dtype=torch.int64, device=dvc)
+    d_off = torch.empty(rows + 1, dtype=torch.int64, device=dvc)
+    d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=dvc)
+    d_ksel, d_vsel = torch.zeros(48, dtype=torch.uint8, device=dvc), torch.zeros(48, dtype=torch.uint8, device=dvc)
+    room = min(w.n_tokens, 4 * rows + 4096) if entries_capacity is None else int(entries_capacity)
+    for _ in range(2):
+        res, _, _, d_keys, d_values, _, _ = w.dev.object_entries(
+            w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_rows, d_rows_select, d_numbers=w.d_numbers,
+            numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, d_offsets=d_off, d_valid=d_valid, capacity=rows,
+            entries_capacity=room, d_keys_select=d_ksel, d_values_select=d_vsel)
+        if res.code != errors.CAPACITY or res.n_rows > rows:
+            break
+        room = int(res.n_entries)
+    if res.code != 0:
+        raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be laid out")
+    n = int(res.n_entries)
+    return MapColumn(w, d_off, d_valid[:rows].view(torch.bool), d_keys[:n], d_values[:n], d_ksel, d_vsel, parent)
+
+
+class MapColumn:
+    """Objects as a map column ON THE DEVICE (``Window.entries``, ``ListColumn.entries``, ``ElementFields.entries``): the
+    members of objects whose keys are data.  offsets int64[rows + 1]; key_fields and value_fields int64[n_entries, 2], one
+    ``msj_field`` per entry back to back at the same position -- row k's entries are [offsets[k]:offsets[k + 1]], duplicate
+    keys all kept in document order; valid bool[rows], False where the value is no object, the key is missing or the document
+    has a verdict code (the row is empty then); d_keys_select / d_values_select uint8[48], the
+    ``msj_select_documents_result`` of the key and of the value records; parent, the column whose records are this column's
+    rows -- None for ``Window.entries``, whose rows are the documents.  Like every array a Window carries, the window's own
+    arrays are reused by the next window: use the column before the iterator advances."""
+
+    def __init__(self, window, offsets, valid, key_fields, value_fields, d_keys_select, d_values_select, parent=None):
+        self.window, self.offsets, self.valid, self.parent = window, offsets, valid, parent
+        self.key_fields, self.value_fields = key_fields, value_fields
+        self.d_keys_select, self.d_values_select = d_keys_select, d_values_select
+
+    @property
+    def n_entries(self):
+        return self.key_fields.shape[0]
+
+    def keys(self, bytes_capacity=None):
+        """The keys, unescaped, as a string column on the device (``msj_string_column_device`` over the key records):
+        (offsets int64[n_entries + 1], bytes uint8[total], valid bool[n_entries])."""
+        w = self.window
+        d_fields = self.key_fields if self.n_entries else torch.zeros((1, 2), dtype=torch.int64, device=self.key_fields.device)
+        return _string_column(w.dev, w.d_window, w.length, d_fields.unsqueeze(0), 0, self.d_keys_select, self.n_entries, bytes_capacity,
+                              f"window at {w.base}: the keys of the entries")
+
+    def values(self):
+        """The values as a ``ListColumn`` that shares this column's offsets and validity: ``.numbers()``, ``.strings()``,
+        ``.select()``, ``.elements()`` and ``.entries()`` (a map of maps) run on them."""
+        return ListColumn(self.window, self.offsets, self.value_fields, self.valid, self.d_values_select, self)
+
+    def to_python(self):
+        """A dict per row, None where the row is no object; the first of duplicate keys wins, as in a selected container.
+        The records come to the host, and the window's bytes, d_idx and d_end once per window."""
+        w = self.window
+        off, ok = self.offsets.cpu().tolist(), self.valid.cpu().tolist()
+        host = w._host_arrays()
+        as_records = lambda t: np.ascontiguousarray(t.cpu().numpy()).view(FIELD_DTYPE).reshape(-1)
+        keys, values = as_records(self.key_fields), as_records(self.value_fields)
+        pairs = lambda k: ((field_value(keys[j], *host), field_value(values[j], *host)) for j in range(off[k], off[k + 1]))
+        return [_first_wins(pairs(k)) if ok[k] else None for k in range(len(ok))]
+
+
 class ListColumn:
-    """Arrays as a list column ON THE DEVICE (``Window.elements``, ``ListColumn.elements``, ``ElementFields.elements``).
+    """Arrays as a list column ON THE DEVICE (``Window.elements``, ``ListColumn.elements``, ``ElementFields.elements``,
+    ``MapColumn.values``).
     offsets int64[rows + 1]; fields int64[n_elements, 2], one ``msj_field`` per element back to back -- row k's elements are
     fields[offsets[k]:offsets[k + 1]]; valid bool[rows], False where the value is no array, the key is missing or the
     document has a verdict code (the row is empty then); d_select uint8[48], the ``msj_select_documents_result`` of the
@@ -190,6 +260,14 @@ class ListColumn:
         return _array_elements(self.window, self.fields, self.d_select, self.n_elements, elements_capacity, self,
                                "the arrays among the elements")
 
+    def entries(self, entries_capacity=None):
+        """The objects among this column's elements as a map column -- a list of maps, or the values of a ``MapColumn`` (a map
+        of maps) -- ON THE DEVICE (``msj_object_entries_device``) -> ``MapColumn`` with one row per element of this column; an
+        element that is no object is a row that is not valid.  The buffers start from a guess (entries_capacity: the
+        caller's) and are grown once, as in ``Window.elements``."""
+        return _object_entries(self.window, self.fields, self.d_select, self.n_elements, entries_capacity, self,
+                               "the objects among the elements")
+
 
 class ElementFields:
     """Fields by path inside the elements of a ``ListColumn`` ON THE DEVICE (``ListColumn.select``).  fields int64[n_paths,
@@ -229,6 +307,14 @@ class ElementFields:
         p = self.paths.index(path_or_index)
         return _array_elements(self.list_column.window, self.fields[p], self.d_select, self.n_elements, elements_capacity, self,
                                f"the arrays of path {p} of the elements")
+
+    def entries(self, path_or_index, entries_capacity=None):
+        """The objects of one path as a map column -- ``items[*].dims`` -- ON THE DEVICE (``msj_object_entries_device``) ->
+        ``MapColumn`` with one row per element of the list column the fields were selected in; a missing key and a value that
+        is no object are rows that are not valid."""
+        p = self.paths.index(path_or_index)
+        return _object_entries(self.list_column.window, self.fields[p], self.d_select, self.n_elements, entries_capacity, self,
+                               f"the objects of path {p} of the elements")
 
     def values(self, path_or_index):
         """The values of one path as a Python list, one per element: None where the record has a code, see ``field_value``."""
@@ -356,6 +442,17 @@ class Window:
         if res.code != 0:
             raise DocumentStreamError(int(res.code), f"window at {self.base}: the arrays of path {p} could not be laid out")
         return ListColumn(self, d_off, d_elements[:int(res.n_elements)], d_valid[:nd].view(torch.bool), d_esel)
+
+    def entries(self, path_or_index, entries_capacity=None):
+        """The objects of one path as a map column ON THE DEVICE (``msj_object_entries_device``) -> ``MapColumn``: offsets
+        int64[D + 1], a key and a value ``msj_field`` per entry back to back, valid bool[D] -- "attrs":{"color":"red",...}
+        with the keys as data.  The rows are the documents: the path's records of the window's select call.  The call runs
+        on the window's arrays and records where they lie; only its 48-byte result comes to the host.  The buffers start
+        from a guess (entries_capacity: the caller's) and are grown once, as in ``Window.elements``."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        p = self.paths.index(path_or_index)
+        return _object_entries(self, self.d_fields[p], self.d_select, self.n_documents, entries_capacity, None, f"the objects of path {p}")
 
     def number_column(self, path_or_index, dtype=torch.float64):
         """The numbers of one path as a column ON THE DEVICE, from the records alone (torch operations, no call): (values
