@@ -1290,6 +1290,77 @@ int32_t msj_object_entries_device(msj_ctx *ctx,
 uint64_t msj_object_entries_workspace_bytes(uint64_t n, uint64_t capacity);
 
 /*
+ * ---- a selected value's JSON text as a column (DERIVED) ---------------------------------------------
+ * msj_raw_column_device -- simdjson's raw_json(), get_json_object of the dataframe engines: the value ITSELF, as JSON text,
+ * for every row of any msj_field records, in the standard variable-length layout: d_offsets[R + 1], the bytes back to back
+ * in d_bytes, a validity byte per row in d_valid.  It is the column for a field whose shape differs from line to line, for a
+ * subtree that is handed on unparsed, and for re-emitting a window as minified NDJSON.  All on the device, on the caller's
+ * stream, no host round trip.
+ * Inputs: d_buf / len and the token arrays of the window the records were written over (d_depth is not among them; d_match
+ * may be NULL: it is not read, a container's closing token is its record's bits); d_rows / d_rows_select = ANY msj_field
+ * records with their select result: a path of msj_select_documents_device (d_fields + p * capacity, its d_result), the
+ * d_elements / d_elements_select of an array call, a path of msj_select_elements_device, the d_keys or d_values of
+ * msj_object_entries_device with their select result.  The rows need NOT ascend: every row is treated on its own, and two
+ * rows may name the same value.  R = d_rows_select->n_documents is read on the device.
+ *   d_rows_select->code != 0: d_result is a zero result with that code (flags kept) and nothing else is written
+ *   R > capacity, or R >= 2^31: MSJ_CAPACITY with n_rows = R, nothing else written
+ * Token text: lim(i) = d_idx[i + 1] for i + 1 < n, else len, and never more than len.  te(i) =
+ *   d_end[i] + 1                                  d_flags[i] has MSJ_SPAN_STRING
+ *   d_end[i]                                      MSJ_SPAN_NUMBER without MSJ_SPAN_LONG
+ *   lim(i) minus the blanks (space \t \n \r) directly in front of it    MSJ_SPAN_NUMBER with MSJ_SPAN_LONG
+ *   d_idx[i] + 4 / + 5 / + 1                      d_type[i] 't' or 'n' / 'f' / anything else
+ * clipped to lim(i), and tl(i) = te(i) - d_idx[i], 0 when that is negative.  On any arrays the text of a token then lies in
+ * [0, len) and ends at or in front of lim(i).
+ * Row k (k < R) is a value, d_valid[k] = 1, iff its record has code == 0 and token < n and, for type '{' or '[', last = bits
+ * satisfies token < last < n; for every other type last = token.  A record with code 0 that fails the test is counted in
+ * n_other, has d_valid[k] = 0 and length 0 and is never dereferenced; a record with a code has d_valid[k] = 0 and length 0
+ * and is in neither count.
+ *   flags 0, verbatim:   row k's bytes are d_buf[d_idx[token] .. te(last)) -- the source's text, blanks and escapes included;
+ *                        no byte when the arrays put te(last) in front of d_idx[token].  No pass over the tokens runs
+ *   MSJ_RAW_COMPACT:     row k's bytes are the texts of the tokens token .. last back to back: the blanks BETWEEN tokens are
+ *                        dropped, those inside a string stay.  The length is P[last + 1] - P[token], P the exclusive sum of
+ *                        tl over the window's tokens (one pass and a scan, 64-bit throughout).  A pretty-printed window gives
+ *                        the bytes of its minified twin
+ *   d_offsets    d_offsets[0] = 0, d_offsets[k + 1] = d_offsets[k] + the length of row k; uint64; capacity + 1 entries,
+ *                those past R are not written
+ *   d_valid      capacity entries; those at or past R are not written
+ *   d_bytes      bytes at or past min(total_bytes, bytes_capacity) are not written: with total_bytes > bytes_capacity the
+ *                offsets and d_valid are complete, the bytes clipped, the code MSJ_CAPACITY and total_bytes exact.
+ *                d_bytes == NULL (with bytes_capacity 0) is the layout-only form: code 0
+ * d_result: code; flags, the call's; n_rows = R; n_values the rows with d_valid = 1; n_containers those of them of type '{'
+ * or '['; total_bytes = d_offsets[R]; n_other.  R == 0 writes d_offsets[0] = 0 and a zero result (flags kept).
+ * Arguments, checked in this order: NULL ctx / d_result / d_rows_select / d_buf; NULL d_idx / d_type / d_end / d_flags with
+ * n > 0; NULL d_rows / d_offsets / d_valid with capacity > 0; NULL d_bytes with bytes_capacity > 0 or a flag other than
+ * MSJ_RAW_COMPACT: MSJ_ERR_BAD_ARGUMENT.  len > MSJ_MAX_SEGMENT_BYTES or n >= 2^31: MSJ_CAPACITY.  Then alignment: d_rows
+ * 16-byte; d_offsets, d_rows_select, d_result 8-byte; d_idx, d_match, d_end 4-byte; the others any: MSJ_ERR_BAD_ARGUMENT.
+ * Nothing is launched on any of them.  Asynchronous on `stream`, no host round trip, workspace in the context.  Safe on ANY
+ * arrays and records: a token from a record is used only below n, every read of the window lies in [0, len), every store
+ * to d_bytes is below min(total_bytes, bytes_capacity), and rows at or past R are not touched.
+ * Out of scope: array indices in pointers, re-serialising numbers or strings, pretty-printing.
+ */
+#define MSJ_RAW_COMPACT 1u   /* msj_raw_column_device flags: the tokens' texts back to back, blanks between tokens dropped */
+typedef struct msj_raw_column_result {   /* 48 bytes */
+    int32_t  code;          /* 0; MSJ_CAPACITY (rows > capacity: nothing else written; or total_bytes > bytes_capacity:
+                               offsets / valid complete, bytes clipped); or d_rows_select->code when that is not 0 */
+    uint32_t flags;         /* the call's flags */
+    uint64_t n_rows;        /* R */
+    uint64_t n_values;      /* rows with valid = 1 */
+    uint64_t n_containers;  /* ... of which are of type '{' or '[' */
+    uint64_t total_bytes;   /* offsets[R], exact also when clipped and when d_bytes == NULL */
+    uint64_t n_other;       /* rows with code 0 that fail the row test */
+} msj_raw_column_result;
+int32_t msj_raw_column_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len,
+        const uint32_t *d_idx, uint64_t n, const uint8_t *d_type, const uint32_t *d_match,
+        const uint32_t *d_end, const uint8_t *d_flags,
+        const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
+        uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+        uint8_t *d_bytes, uint64_t bytes_capacity, uint32_t flags,
+        msj_raw_column_result *d_result, void *stream);
+/* Device workspace of one msj_raw_column_device call (the context keeps it): 8 bytes per row of capacity, 8 per 256 rows, a
+ * list of 1 024 long rows; with MSJ_RAW_COMPACT also 8 bytes per token and 8 per 1 024 tokens. */
+uint64_t msj_raw_column_workspace_bytes(uint64_t n, uint64_t capacity, uint32_t flags);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

@@ -144,6 +144,14 @@ class MsjObjectEntriesResult(ctypes.Structure):
                 ("n_entries", ctypes.c_uint64), ("n_other", ctypes.c_uint64), ("n_no_bits", ctypes.c_uint64)]
 
 
+class MsjRawColumnResult(ctypes.Structure):
+    """``msj_raw_column_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_values", ctypes.c_uint64),
+                ("n_containers", ctypes.c_uint64), ("total_bytes", ctypes.c_uint64), ("n_other", ctypes.c_uint64)]
+
+
+RAW_COMPACT = 1   # MSJ_RAW_COMPACT
 FIELD_NO_BITS = 64
 NO_SUCH_FIELD, INCORRECT_TYPE, INVALID_JSON_POINTER = 20, 17, 22
 MAX_PATHS, MAX_PATH_SEGMENTS, MAX_SEGMENT_BYTES = 16, 8, 255
@@ -168,7 +176,7 @@ assert ctypes.sizeof(MsjDocumentVerdict) == 16 and ctypes.sizeof(MsjValidateDocu
 assert ctypes.sizeof(MsjDocumentTape) == 32 and ctypes.sizeof(MsjTapeDocumentsResult) == 64
 assert ctypes.sizeof(MsjField) == 16 and ctypes.sizeof(MsjSelectDocumentsResult) == 48
 assert ctypes.sizeof(MsjStringColumnResult) == 48 and ctypes.sizeof(MsjArrayColumnResult) == 48
-assert ctypes.sizeof(MsjObjectEntriesResult) == 48
+assert ctypes.sizeof(MsjObjectEntriesResult) == 48 and ctypes.sizeof(MsjRawColumnResult) == 48
 
 _lib = None
 
@@ -334,6 +342,11 @@ def load():
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_object_entries_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_object_entries_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    lib.msj_raw_column_device.restype = ctypes.c_int32
+    lib.msj_raw_column_device.argtypes = [ctypes.c_void_p, u8p, ctypes.c_uint64, u32p, ctypes.c_uint64] + [ctypes.c_void_p] * 8 + \
+        [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_raw_column_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_raw_column_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

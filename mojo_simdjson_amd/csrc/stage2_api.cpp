@@ -1,7 +1,7 @@
 // stage2_api.cpp -- extern "C" entry points of everything that runs behind stage 1 (include/msj_stage1.h): tokens, spans,
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
 // window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
-// elements, the arrays inside list rows, an object's members as a map column.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// elements, the arrays inside list rows, an object's members as a map column, a selected value's JSON text as a column.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
 // see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
 #include <new>
 
@@ -487,6 +487,24 @@ int32_t msj_object_entries_device(msj_ctx *ctx, const uint32_t *d_idx, uint64_t 
     if (rc != MSJ_SUCCESS) return rc;
     return launched(msj_launch_object_entries(t, nv, d_rows, d_rows_select, d_offsets, d_valid, capacity, d_keys, d_values, entries_capacity,
                                               d_result, d_keys_select, d_values_select, ctx->oent_ws.p, stream));
+}
+
+int32_t msj_raw_column_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_type,
+                              const uint32_t *d_match, const uint32_t *d_end, const uint8_t *d_flags, const msj_field *d_rows,
+                              const msj_select_documents_result *d_rows_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
+                              uint8_t *d_bytes, uint64_t bytes_capacity, uint32_t flags, msj_raw_column_result *d_result, void *stream) {
+    const msj_token_view t{d_buf, len, d_idx, n, d_type, nullptr, d_match, d_end, d_flags};  // (d_match is not read: the record's bits name the partner)
+    if (!ctx || !d_result || !d_rows_select || !d_buf) return MSJ_ERR_BAD_ARGUMENT;
+    if (n > 0 && (!d_idx || !d_type || !d_end || !d_flags)) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && (!d_rows || !d_offsets || !d_valid)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((bytes_capacity > 0 && !d_bytes) || (flags & ~MSJ_RAW_COMPACT) != 0) return MSJ_ERR_BAD_ARGUMENT;
+    if (too_big(t)) return MSJ_CAPACITY;
+    if (!aligned(d_rows, 16) || !all_aligned(8, d_offsets, d_rows_select, d_result) || !all_aligned(4, d_idx, d_match, d_end))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->rcol_ws, msj_raw_column_workspace_bytes(n, capacity, flags));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_raw_column(t, d_rows, d_rows_select, d_offsets, d_valid, capacity, d_bytes, bytes_capacity, flags, d_result,
+                                          ctx->rcol_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

@@ -542,6 +542,54 @@ class Stage1Device:
         call(d_bytes, bytes_capacity)
         return (read() if sync else d_result), d_offsets, d_valid, d_bytes
 
+    def raw_column(self, d_buf, length, d_idx, n, d_type, d_match, d_end, d_flags, d_rows, d_rows_select, d_offsets=None, d_valid=None,
+                   d_bytes=None, capacity=None, bytes_capacity=None, compact=False, text=True, d_result=None, sync=True):
+        """The JSON text of the values that records name, as a column (``msj_raw_column_device``): offsets, the text back to
+        back and a validity byte per row, all on the device.  d_buf / length and the token arrays: the window the records
+        were written over; d_rows: int64 of shape (rows, 2), any ``msj_field`` records in any order -- a path of
+        ``select_documents`` or ``select_elements``, the elements of a list column, the keys or values of a map column;
+        d_rows_select: the device ``msj_select_documents_result`` that counts them, read on the device.  compact=False: the
+        window's bytes from the value's first to its last; compact=True (MSJ_RAW_COMPACT): the blanks between tokens
+        dropped.  d_offsets, d_valid, d_bytes, capacity, bytes_capacity and the layout-only first call when no size is given
+        are ``string_column``'s; text=False: the layout-only form alone (d_bytes None).  Returns (``MsjRawColumnResult``,
+        d_offsets, d_valid, d_bytes) -- blocking for the 48-byte result; with sync=False the device tensor that holds it,
+        nothing waited for."""
+        if d_rows.stride(-1) != 1 or (d_rows.shape[0] > 1 and d_rows.stride(0) != 2):
+            raise ValueError("the records must be contiguous")
+        if capacity is None:
+            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_rows.shape[0]
+        capacity = int(capacity)
+        if d_offsets is None:
+            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
+        if d_valid is None:
+            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
+        if d_result is None:
+            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        flags = _lib.RAW_COMPACT if compact else 0
+
+        def call(d_out, room):
+            rc = self.lib.msj_raw_column_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), int(n), _ptr(d_type),
+                                                _ptr(d_match) if d_match is not None else None, _ptr(d_end), _ptr(d_flags), _ptr(d_rows),
+                                                _ptr(d_rows_select), _ptr(d_offsets), _ptr(d_valid), capacity,
+                                                _ptr(d_out) if d_out is not None else None, int(room), flags, _ptr(d_result), self._stream())
+            if rc != 0:
+                raise RuntimeError(f"msj_raw_column_device failed: {rc}")
+
+        def read():
+            return _lib.MsjRawColumnResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
+
+        if not text:
+            d_bytes, bytes_capacity = None, 0
+        elif d_bytes is None:
+            if bytes_capacity is None:
+                call(None, 0)
+                bytes_capacity = read().total_bytes
+            d_bytes = torch.empty(max(int(bytes_capacity), 1), dtype=torch.uint8, device=self.device)
+        elif bytes_capacity is None:
+            bytes_capacity = d_bytes.numel()
+        call(d_bytes, bytes_capacity)
+        return (read() if sync else d_result), d_offsets, d_valid, d_bytes
+
     def array_column(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_fields, p, d_select_result,
                      d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_offsets=None, d_valid=None, d_elements=None,
                      capacity=None, elements_capacity=None, elements=True, d_result=None, d_elements_select=None, sync=True):

@@ -101,6 +101,28 @@ def _string_column(dev, d_window, length, d_fields, p, d_select, rows, bytes_cap
     return d_off, d_bytes[:int(res.total_bytes)], d_valid[:rows].view(torch.bool)
 
 
+def _raw_column(window, d_rows, d_rows_select, rows, compact, bytes_capacity, what):
+    """``raw_column`` over `rows` records with a byte buffer that starts from a guess and, when the call says it was too
+    small, is made as large as the call asks once -> (offsets int64[rows + 1], bytes uint8[total], valid bool[rows])"""
+    w = window
+    dvc = d_rows.device
+    if rows == 0:
+        d_rows = torch.zeros((1, 2), dtype=torch.int64, device=dvc)
+    d_off = torch.empty(rows + 1, dtype=torch.int64, device=dvc)
+    d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=dvc)
+    room = min(w.length, 64 * rows + 4096) if bytes_capacity is None else int(bytes_capacity)
+    for _ in range(2):
+        res, _, _, d_bytes = w.dev.raw_column(w.d_window, w.length, w.d_idx, w.n_tokens, w.d_type, w.d_match, w.d_end, w.d_flags, d_rows,
+                                              d_rows_select, d_offsets=d_off, d_valid=d_valid, capacity=rows, bytes_capacity=room,
+                                              compact=compact)
+        if res.code != errors.CAPACITY or res.n_rows > rows:
+            break
+        room = int(res.total_bytes)
+    if res.code != 0:
+        raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be laid out")
+    return d_off, d_bytes[:int(res.total_bytes)], d_valid[:rows].view(torch.bool)
+
+
 def _array_elements(window, d_rows, d_rows_select, rows, elements_capacity, parent, what):
     """``array_elements`` over `rows` records with an element buffer that starts from a guess and, when the call says it was
     too small, is made as large as the call asks once -> ``ListColumn`` with `parent`"""
@@ -225,6 +247,12 @@ class ListColumn:
         return _string_column(w.dev, w.d_window, w.length, d_fields.unsqueeze(0), 0, self.d_select, self.n_elements, bytes_capacity,
                               f"window at {w.base}: the strings of the elements")
 
+    def raw(self, compact=False, bytes_capacity=None):
+        """The JSON text of every element as a column on the device (``msj_raw_column_device`` over the element records):
+        (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements]) -- a container's text too, without the
+        window on the host.  compact: the blanks between tokens dropped."""
+        return _raw_column(self.window, self.fields, self.d_select, self.n_elements, compact, bytes_capacity, "the text of the elements")
+
     def to_python(self):
         """A list per row, None where the row is no array; the elements as ``field_value`` gives them.  The element records
         come to the host, and the window's bytes, d_idx and d_end once per window."""
@@ -298,6 +326,14 @@ class ElementFields:
         d_fields = self.fields if self.n_elements else torch.zeros((self.fields.shape[0], 1, 2), dtype=torch.int64, device=self.fields.device)
         return _string_column(w.dev, w.d_window, w.length, d_fields, p, self.d_select, self.n_elements, bytes_capacity,
                               f"window at {w.base}: the strings of path {p} of the elements")
+
+    def raw(self, path_or_index, compact=False, bytes_capacity=None):
+        """The JSON text of one path's values as a column on the device (``msj_raw_column_device`` over the path's records):
+        (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements]); a missing key is a row that is not
+        valid.  compact: the blanks between tokens dropped."""
+        p = self.paths.index(path_or_index)
+        return _raw_column(self.list_column.window, self.fields[p], self.d_select, self.n_elements, compact, bytes_capacity,
+                           f"the text of path {p} of the elements")
 
     def elements(self, path_or_index, elements_capacity=None):
         """The arrays of one path as a list column -- ``items[*].tags`` -- ON THE DEVICE (``msj_array_elements_device``) ->
@@ -414,6 +450,18 @@ class Window:
         p = self.paths.index(path_or_index)
         return _string_column(self.dev, self.d_window, self.length, self.d_fields, p, self.d_select, self.n_documents, bytes_capacity,
                               f"window at {self.base}: the strings of path {p}")
+
+    def raw(self, path_or_index, compact=False, bytes_capacity=None):
+        """The JSON text of one path's values as a column ON THE DEVICE (``msj_raw_column_device``): (offsets int64[D + 1],
+        bytes uint8[total], valid bool[D]) -- row k's text is bytes[offsets[k]:offsets[k + 1]], the source's own bytes from the
+        value's first to its last, whatever the value is: the way to a container's text without the window on the host.  ""
+        is the whole document.  Empty where valid[k] is False (the key is missing, the document has a verdict code).
+        compact: the blanks between tokens dropped, so that a pretty-printed window gives the bytes of its minified twin.
+        The byte buffer starts from a guess (bytes_capacity: the caller's) and is grown once, as in ``strings``."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        p = self.paths.index(path_or_index)
+        return _raw_column(self, self.d_fields[p], self.d_select, self.n_documents, compact, bytes_capacity, f"the text of path {p}")
 
     def elements(self, path_or_index, elements_capacity=None):
         """The arrays of one path as a list column ON THE DEVICE (``msj_array_column_device``) -> ``ListColumn``: offsets
