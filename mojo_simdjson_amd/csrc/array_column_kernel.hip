@@ -29,12 +29,12 @@
 
 #include "../../include/msj_stage1.h"
 #include "array_column_math.h"
-#include "docs_block.h"
 #include "launch.h"
+#include "list_block.h"
 
 namespace msj_acol {
 
-using namespace msj_tdocs;
+using namespace msj_list;
 using namespace msj::acol;
 
 static_assert(sizeof(msj_field) == 16 && sizeof(msj_array_column_result) == 48 && sizeof(Desc) == 16, "ABI");
@@ -50,7 +50,6 @@ struct ColWork {
 };
 
 __host__ __device__ inline uint64_t most_rows(uint64_t n, uint64_t capacity) { return n < capacity ? n : capacity; }
-__host__ __device__ inline uint64_t token_blocks(uint64_t tokens) { return (tokens + kBlock - 1) / kBlock; }
 static inline ColWork col_layout(void *ws, uint64_t n, uint64_t capacity) {
     uint8_t *p = static_cast<uint8_t *>(ws);
     ColWork w;
@@ -99,30 +98,10 @@ __global__ __launch_bounds__(kThreads) void ac_rows(uint64_t n, const uint8_t *_
     (void)block_counter_add(n_other, s_other, &w.st->n_other);
 }
 
-// A lane's four tokens of the block at `base`: types, depths and the candidates among them (bit k: token mine + k)
-struct Lane {
-    TokenQuad t;
-    uint32_t cand;
-};
-// s_type: kThreads words of LDS that nothing else uses (a lane reads its neighbour's word behind the barrier)
+// a lane's tokens and its candidates (list_block.h): tokens at or past T read as nothing, they belong to the cut document
 __device__ __forceinline__ Lane load_lane(const Window &win, uint64_t base, const uint8_t *__restrict__ type, const int32_t *__restrict__ depth,
                                           uint32_t *s_type) {
-    Lane l;
-    const uint64_t mine = base + (uint64_t)threadIdx.x * kPer;
-    l.t = load_token_quad(type, depth, mine, win.T);  // tokens at or past T read as nothing: they belong to the cut document
-    s_type[threadIdx.x] = l.t.tw;
-    __syncthreads();
-    // the token in front of this lane's first: the lane before's last, or the halo, one token in front of the block
-    uint32_t prev = threadIdx.x > 0 ? s_type[threadIdx.x - 1] >> 24 : (base > 0 ? (uint32_t)type[base - 1] : 0u);  // (base - 1 < T)
-    l.cand = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; k++) {
-        const uint64_t i = mine + k;
-        const uint32_t t = (l.t.tw >> (8 * k)) & 0xFFu;
-        if (in_documents(win, i) && is_candidate(prev, t)) l.cand |= 1u << k;
-        prev = t;
-    }
-    return l;
+    return load_lane_front(win.T, base, type, depth, s_type, [&win](uint64_t i) { return in_documents(win, i); });
 }
 // the candidates that are elements of their document's row: one 16-byte gather each
 __device__ __forceinline__ uint32_t elements_of(const Lane &l, const BlockDocs &bd, const Window &win, uint64_t base, const Desc *__restrict__ desc) {
@@ -179,15 +158,7 @@ __global__ __launch_bounds__(1024) void ac_scan(uint64_t n, const uint32_t *__re
     r.n_no_bits = 0;  // (ac_emit's)
     *result = r;
     if (!h.stop && offsets) offsets[h.win.D] = run;  // (NULL only with capacity 0: D is 0 then)
-    if (elements_select) {
-        msj_select_documents_result e;
-        e.code = r.code;
-        e.flags = 0;
-        e.n_documents = e.n_found = run;
-        e.n_paths = 1;
-        e.n_no_bits = e.reserved = 0;
-        *elements_select = e;
-    }
+    if (elements_select) *elements_select = items_select(r.code, run);
 }
 
 __global__ __launch_bounds__(kThreads) void ac_emit(const uint32_t *__restrict__ idx, uint64_t n, const uint8_t *__restrict__ type,

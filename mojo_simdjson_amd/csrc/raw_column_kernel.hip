@@ -36,7 +36,7 @@
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
-#include "docs_block.h"
+#include "bytes_block.h"
 #include "launch.h"
 #include "raw_column_math.h"
 
@@ -44,11 +44,10 @@ namespace msj_rcol {
 
 using namespace msj::rcol;
 using namespace msj::wave;
+using namespace msj_bytes;
 using msj_tape::block_scan, msj_tape::kThreads, msj_tape::kWaves, msj_tape::up16;
 using msj_tdocs::load_field;
 
-constexpr uint32_t kRows = kThreads;      // rows per block: one per lane
-constexpr uint32_t kGridBlocks = 4096;    // most blocks of the kernels over the rows (they loop over what R needs)
 constexpr uint32_t kTokPer = 4;           // tokens per lane of rc_tokens
 constexpr uint32_t kTokBlock = kThreads * kTokPer;  // tokens per block of rc_tokens: 1 024
 constexpr uint32_t kTokShift = 10;
@@ -81,7 +80,6 @@ struct PSum {
     __device__ __forceinline__ uint64_t operator()(uint64_t i) const { return base[i >> kTokShift] + loc[i]; }
 };
 
-__host__ __device__ inline uint64_t most_rows(uint64_t capacity) { return capacity < msj::scol::kMaxRows ? capacity : msj::scol::kMaxRows; }
 __host__ __device__ inline uint64_t token_blocks(uint64_t n) { return n / kTokBlock + 1; }  // tokens 0 .. n: P has n + 1 entries
 static inline uint64_t workspace_bytes(uint64_t n, uint64_t capacity, bool compact) {
     const uint64_t rows = most_rows(capacity);
@@ -100,23 +98,6 @@ static inline Work layout(void *ws, uint64_t n, uint64_t capacity) {
     w.tbase = reinterpret_cast<uint64_t *>(p), p += up16(8 * token_blocks(n));
     w.tloc = reinterpret_cast<uint64_t *>(p);
     return w;
-}
-
-// what every kernel reads of d_rows_select.  stop: nothing but the result is written
-struct Head {
-    uint64_t R, blocks;
-    int32_t code;
-    bool skip, over, stop;
-};
-__device__ __forceinline__ Head load_head(const msj_select_documents_result *__restrict__ sel, uint64_t capacity) {
-    Head h;
-    h.code = sel->code;
-    h.R = sel->n_documents;
-    h.skip = h.code != 0;
-    h.over = !h.skip && rows_over(h.R, capacity);
-    h.stop = h.skip || h.over;
-    h.blocks = h.stop ? 0 : (h.R + kRows - 1) / kRows;
-    return h;
 }
 
 __global__ __launch_bounds__(kThreads) void rc_tokens(const Tokens t, const msj_select_documents_result *__restrict__ sel, uint64_t capacity,
@@ -170,21 +151,7 @@ __global__ __launch_bounds__(kThreads) void rc_lengths(const Tokens t, const msj
             valid[k] = y.valid;
             w.lens[k] = ul | (listed ? kListed : 0);
         }
-        // values, containers and other rows of the block: at most 256 each, 10 bits each
-        const uint32_t cnt = wave_sum((uint32_t)y.valid | ((uint32_t)y.container << 10) | ((uint32_t)y.other << 20));
-        const uint64_t sum = wave_sum64(ul);
-        __syncthreads();  // (the last round's words have been read)
-        if (lane == 0) s_sum[wave] = sum, s_cnt[wave] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t all = 0;
-            uint32_t c = 0;
-            for (int x = 0; x < kWaves; x++) all += s_sum[x], c += s_cnt[x];
-            w.bsum[v] = all;
-            if (c & 0x3FFu) atomicAdd(&w.st->n_values, (unsigned long long)(c & 0x3FFu));
-            if ((c >> 10) & 0x3FFu) atomicAdd(&w.st->n_containers, (unsigned long long)((c >> 10) & 0x3FFu));
-            if (c >> 20) atomicAdd(&w.st->n_other, (unsigned long long)(c >> 20));
-        }
+        block_sums_out(lane, wave, ul, y.valid, y.container, y.other, s_sum, s_cnt, &w.bsum[v], &w.st->n_values, &w.st->n_containers, &w.st->n_other);
     }
 }
 

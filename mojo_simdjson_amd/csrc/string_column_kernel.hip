@@ -28,7 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
-#include "docs_block.h"
+#include "bytes_block.h"
 #include "launch.h"
 #include "string_column_math.h"
 
@@ -36,12 +36,10 @@ namespace msj_scol {
 
 using namespace msj::scol;
 using namespace msj::wave;
+using namespace msj_bytes;
 using msj::val::ByteReader;
 using msj_tape::block_scan, msj_tape::BufWriter, msj_tape::kLaneBody, msj_tape::kThreads, msj_tape::kWaves, msj_tape::up16, msj_tape::wave_unescape;
 using msj_tdocs::load_field;
-
-constexpr uint32_t kRows = kThreads;   // rows per block: one per lane
-constexpr uint32_t kGridBlocks = 4096; // most blocks of the kernels over the rows (they loop over what D needs)
 
 static_assert(sizeof(msj_string_column_result) == 48 && sizeof(msj_field) == 16, "ABI");
 
@@ -55,7 +53,6 @@ struct Work {
     uint32_t *lens;  // per row: its length in the output
 };
 
-__host__ __device__ inline uint64_t most_rows(uint64_t capacity) { return capacity < kMaxRows ? capacity : kMaxRows; }
 static inline Work layout(void *ws, uint64_t capacity) {
     const uint64_t rows = most_rows(capacity), nb = rows / kRows + 1;
     uint8_t *p = static_cast<uint8_t *>(ws);
@@ -64,23 +61,6 @@ static inline Work layout(void *ws, uint64_t capacity) {
     w.bsum = reinterpret_cast<uint64_t *>(p + sizeof(State));
     w.lens = reinterpret_cast<uint32_t *>(p + sizeof(State) + up16(8 * nb));
     return w;
-}
-
-// what every kernel reads of d_select.  stop: nothing but the result is written
-struct Head {
-    uint64_t D, blocks;
-    int32_t code;
-    bool skip, over, stop;
-};
-__device__ __forceinline__ Head load_head(const msj_select_documents_result *__restrict__ sel, uint64_t capacity) {
-    Head h;
-    h.code = sel->code;
-    h.D = sel->n_documents;
-    h.skip = h.code != 0;
-    h.over = !h.skip && rows_over(h.D, capacity);
-    h.stop = h.skip || h.over;
-    h.blocks = h.stop ? 0 : (h.D + kRows - 1) / kRows;
-    return h;
 }
 
 __global__ __launch_bounds__(kThreads) void sc_lengths(const uint8_t *__restrict__ buf, uint64_t len, const msj_field *__restrict__ column,
@@ -94,7 +74,7 @@ __global__ __launch_bounds__(kThreads) void sc_lengths(const uint8_t *__restrict
     for (uint64_t v = blockIdx.x; v < h.blocks; v += gridDim.x) {
         const uint64_t k = v * kRows + threadIdx.x;
         Row y = row_of(msj_field{0, 0, 0, 0, 1}, len);  // (a row past D: a record with a code)
-        if (k < h.D) y = row_of(load_field(column, k), len);
+        if (k < h.R) y = row_of(load_field(column, k), len);
         const bool far = is_long(y, kLaneBody);
         uint64_t ul = far ? 0 : ulen(rd, y);
         for (uint64_t m = __ballot(far); m; m &= m - 1) {  // (the same in every lane of the wave)
@@ -103,25 +83,11 @@ __global__ __launch_bounds__(kThreads) void sc_lengths(const uint8_t *__restrict
             const uint64_t u = wave_unescape(rd, BufWriter{nullptr, 0, 0}, b, b + r, true);
             if ((int)lane == src) ul = u;
         }
-        if (k < h.D) {
+        if (k < h.R) {
             valid[k] = y.valid;
             w.lens[k] = (uint32_t)ul;  // (<= r < 2^32)
         }
-        // strings, escaped and other rows of the block: at most 256 each, 10 bits each
-        const uint32_t cnt = wave_sum((uint32_t)y.valid | ((uint32_t)y.escaped << 10) | ((uint32_t)y.other << 20));
-        const uint64_t sum = wave_sum64(ul);
-        __syncthreads();  // (the last round's words have been read)
-        if (lane == 0) s_sum[wave] = sum, s_cnt[wave] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t all = 0;
-            uint32_t c = 0;
-            for (int x = 0; x < kWaves; x++) all += s_sum[x], c += s_cnt[x];
-            w.bsum[v] = all;
-            if (c & 0x3FFu) atomicAdd(&w.st->n_strings, (unsigned long long)(c & 0x3FFu));
-            if ((c >> 10) & 0x3FFu) atomicAdd(&w.st->n_escaped, (unsigned long long)((c >> 10) & 0x3FFu));
-            if (c >> 20) atomicAdd(&w.st->n_other, (unsigned long long)(c >> 20));
-        }
+        block_sums_out(lane, wave, ul, y.valid, y.escaped, y.other, s_sum, s_cnt, &w.bsum[v], &w.st->n_strings, &w.st->n_escaped, &w.st->n_other);
     }
 }
 
@@ -135,7 +101,7 @@ __global__ __launch_bounds__(1024) void sc_scan(const msj_select_documents_resul
     msj_string_column_result r;
     r.code = h.skip ? h.code : h.over ? MSJ_CAPACITY : bytes_code(run, have_bytes, bytes_capacity);
     r.flags = 0;
-    r.n_rows = h.skip ? 0 : h.D;
+    r.n_rows = h.skip ? 0 : h.R;
     r.n_strings = h.stop ? 0 : w.st->n_strings;
     r.n_escaped = h.stop ? 0 : w.st->n_escaped;
     r.total_bytes = run;
@@ -157,10 +123,10 @@ __global__ __launch_bounds__(kThreads) void sc_copy(const uint8_t *__restrict__ 
         const uint64_t k = v * kRows + threadIdx.x;
         Row y = row_of(msj_field{0, 0, 0, 0, 1}, len);
         uint64_t ul = 0;
-        if (k < h.D) y = row_of(load_field(column, k), len), ul = w.lens[k];
+        if (k < h.R) y = row_of(load_field(column, k), len), ul = w.lens[k];
         uint64_t total;
         const uint64_t base = w.bsum[v], off = base + block_scan(ul, s_w, total);
-        if (k < h.D) offsets[k + 1] = off + ul;  // (k + 1 <= D <= capacity)
+        if (k < h.R) offsets[k + 1] = off + ul;  // (k + 1 <= D <= capacity)
         if (!bytes || total == 0) continue;      // (the whole block: the layout-only form, or rows without a byte)
         __syncthreads();                         // (the last round's mapping has been read)
         s_off[threadIdx.x] = off, s_src[threadIdx.x] = (uint32_t)y.b, s_esc[threadIdx.x] = y.escaped;

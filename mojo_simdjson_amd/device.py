@@ -18,6 +18,17 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _opt(t):
+    """``_ptr`` of a tensor the call can do without: None, a NULL pointer, for None"""
+    return None if t is None else _ptr(t)
+
+
+def _check_records(d_rows, what):
+    """``msj_field`` records as int64 of shape (rows, 2) lie back to back"""
+    if d_rows.stride(-1) != 1 or (d_rows.shape[0] > 1 and d_rows.stride(0) != 2):
+        raise ValueError(f"{what} must be contiguous")
+
+
 class Paths:
     """Compiled JSON pointers (``msj_paths``), from ``Stage1Device.compile_paths``."""
 
@@ -72,6 +83,45 @@ class Stage1Device:
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _result(self, d_result=None):
+        """The caller's 48-byte result tensor, or a new one"""
+        return d_result if d_result is not None else torch.zeros(48, dtype=torch.uint8, device=self.device)
+
+    def _column_rows(self, d_rows, d_offsets, d_valid, capacity):
+        """What the column calls default to: capacity = the room of the caller's d_offsets, else the rows of `d_rows`;
+        d_offsets: int64[capacity + 1], d_valid: uint8[capacity] (never empty) -> (capacity, d_offsets, d_valid)"""
+        if capacity is None:
+            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_rows.shape[0]
+        capacity = int(capacity)
+        if d_offsets is None:
+            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
+        if d_valid is None:
+            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
+        return capacity, d_offsets, d_valid
+
+    def _sized_call(self, call, result_type, d_result, total, wanted, d_outs, room, width, sync):
+        """The column calls' way to an output of the right size.  call(room, *d_outs) enqueues the C call with these output
+        tensors (None each: layout only) of `room` items; `total` names the field of `result_type` that carries the items the
+        call needs; width: 1 for bytes (uint8[room]), 2 for records (int64[room, 2]).  wanted False: the layout-only form
+        alone.  Else, without tensors of the caller's (d_outs: a tuple, all given or all None), new ones of `room` items are
+        made, and without that number either (None) they are sized from a layout-only first call whose result is waited
+        for; with the caller's tensors and no number, what they hold.  -> (the result, or d_result with sync False; d_outs)"""
+        def read():
+            return result_type.from_buffer_copy(d_result.cpu().numpy().tobytes())
+
+        if not wanted:
+            d_outs, room = (None,) * len(d_outs), 0
+        elif d_outs[0] is None:
+            if room is None:
+                call(0, *d_outs)
+                room = getattr(read(), total)
+            shape, dtype = ((max(int(room), 1),), torch.uint8) if width == 1 else ((max(int(room), 1), 2), torch.int64)
+            d_outs = tuple(torch.empty(shape, dtype=dtype, device=self.device) for _ in d_outs)
+        elif room is None:
+            room = min(t.numel() // width for t in d_outs)
+        call(int(room), *d_outs)
+        return (read() if sync else d_result), d_outs
+
     def new_carry(self):
         return torch.zeros(CARRY_BYTES, dtype=torch.uint8, device=self.device)
 
@@ -116,7 +166,7 @@ class Stage1Device:
         d_depth = torch.empty(max(n, 4), dtype=torch.int32, device=dv)
         d_pairs = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dv)
         d_res = d_result if d_result is not None else torch.zeros(24, dtype=torch.uint8, device=dv)
-        prev = _ptr(d_prev) if d_prev is not None else None
+        prev = _opt(d_prev)
         if spans:
             d_end = torch.empty(max(n, 2), dtype=torch.int32, device=dv)
             d_flags = torch.empty(max(n, 2), dtype=torch.uint8, device=dv)
@@ -139,8 +189,8 @@ class Stage1Device:
         if match and d_match is None:
             d_match = torch.empty(max(n, 4), dtype=torch.int32, device=self.device)
         d_res = d_result if d_result is not None else torch.zeros(24, dtype=torch.uint8, device=self.device)
-        rc = self.lib.msj_depth_from_types_device(self.ctx, _ptr(d_type), n, _ptr(d_depth), _ptr(d_match) if d_match is not None else None,
-                                                  _ptr(d_res), _ptr(d_prev) if d_prev is not None else None, self._stream())
+        rc = self.lib.msj_depth_from_types_device(self.ctx, _ptr(d_type), n, _ptr(d_depth), _opt(d_match),
+                                                  _ptr(d_res), _opt(d_prev), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_depth_from_types_device failed: {rc}")
         return d_depth, d_match, d_res
@@ -150,10 +200,10 @@ class Stage1Device:
         nseg = ctypes.c_uint32(0)
         rc = self.lib.msj_stage1_shard_device(
             self.ctx, _ptr(d_buf), int(length),
-            _ptr(d_idx) if d_idx is not None else None,
+            _opt(d_idx),
             d_idx.numel() if d_idx is not None else 0,
             _ptr(carry_in), _ptr(carry_out),
-            _ptr(segments) if segments is not None else None,
+            _opt(segments),
             (segments.numel() // SEGMENT_BYTES) if segments is not None else 0,
             ctypes.byref(nseg), int(has_prefix), int(is_final), int(no_emit), int(trailer_len),
             self._stream(), flags)
@@ -177,8 +227,8 @@ class Stage1Device:
         d_res = d_result if d_result is not None else torch.zeros(24, dtype=torch.uint8, device=self.device)
         # d_prev: the device msj_tokens_result of the call for the tokens in front (``msj_tokens_chain_device``)
         rc = self.lib.msj_tokens_chain_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), n, _ptr(d_type),
-                                              _ptr(d_depth), _ptr(d_match) if d_match is not None else None,
-                                              _ptr(d_res), _ptr(d_prev) if d_prev is not None else None, self._stream())
+                                              _ptr(d_depth), _opt(d_match),
+                                              _ptr(d_res), _opt(d_prev), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_tokens_device failed: {rc}")
         # sync=False: nothing is waited for; the third element is the device tensor holding the msj_tokens_result
@@ -220,7 +270,7 @@ class Stage1Device:
         d_res = d_result if d_result is not None else torch.zeros(24, dtype=torch.uint8, device=dv)
         rc = self.lib.msj_stage2_prep_chain_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth),
                                                    _ptr(d_match) if match else None, _ptr(d_end), _ptr(d_flags), _ptr(d_res),
-                                                   _ptr(d_prev) if d_prev is not None else None, self._stream())
+                                                   _opt(d_prev), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_stage2_prep_device failed: {rc}")
         res = _lib.MsjTokensResult.from_buffer_copy(d_res.cpu().numpy().tobytes()) if sync else d_res
@@ -246,7 +296,7 @@ class Stage1Device:
         offs = (ctypes.c_uint64 * nseg)()
         rc = self.lib.msj_stage2_prep_segments(self.ctx, _ptr(d_buf), ctypes.byref(table), nseg, _ptr(d_idx), _ptr(d_type), _ptr(d_depth),
                                                _ptr(d_match) if match else None, _ptr(d_end), _ptr(d_flags), _ptr(d_res),
-                                               _ptr(d_prev) if d_prev is not None else None, offs, self._stream())
+                                               _opt(d_prev), offs, self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_stage2_prep_segments failed: {rc}")
         raw = d_res.cpu().numpy().tobytes()
@@ -269,7 +319,7 @@ class Stage1Device:
             d_result = torch.zeros(32, dtype=torch.uint8, device=self.device)
         rc = self.lib.msj_documents_device(self.ctx, _ptr(d_buf), int(length), int(bool(is_final)) | (2 if after_tokens else 0), _ptr(d_idx), n,
                                            _ptr(d_type),
-                                           _ptr(d_depth), _ptr(d_carry) if d_carry is not None else None, _ptr(d_doc_first),
+                                           _ptr(d_depth), _opt(d_carry), _ptr(d_doc_first),
                                            d_doc_first.numel(), _ptr(d_result), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_documents_device failed: {rc}")
@@ -309,7 +359,7 @@ class Stage1Device:
             d_result = torch.zeros(32, dtype=torch.uint8, device=self.device)
         rc = self.lib.msj_validate_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), int(n), _ptr(d_type), _ptr(d_depth),
                                           _ptr(d_match), _ptr(d_end), _ptr(d_flags),
-                                          _ptr(d_numbers_result) if d_numbers_result is not None else None, int(max_depth),
+                                          _opt(d_numbers_result), int(max_depth),
                                           _ptr(d_result), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_validate_device failed: {rc}")
@@ -339,8 +389,8 @@ class Stage1Device:
             d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
         rc = self.lib.msj_validate_documents_device(
             self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
-            _ptr(d_doc_first), _ptr(d_docs), _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, int(numbers_capacity),
-            _ptr(d_numbers_result) if d_numbers_result is not None else None, int(max_depth), _ptr(d_verdicts), int(capacity),
+            _ptr(d_doc_first), _ptr(d_docs), _opt(d_numbers if numbers_capacity else None), int(numbers_capacity),
+            _opt(d_numbers_result), int(max_depth), _ptr(d_verdicts), int(capacity),
             _ptr(d_result), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_validate_documents_device failed: {rc}")
@@ -389,9 +439,9 @@ class Stage1Device:
         if d_result is None:
             d_result = torch.zeros(32, dtype=torch.uint8, device=self.device)
         rc = self.lib.msj_tape_device(self.ctx, _ptr(d_buf), length, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match),
-                                      _ptr(d_end), _ptr(d_flags), _ptr(d_numbers) if d_numbers is not None else None,
-                                      numbers_capacity, None, _ptr(d_verdict) if d_verdict is not None else None, _ptr(d_tape),
-                                      int(tape_capacity), _ptr(d_string_buf) if d_string_buf is not None else None,
+                                      _ptr(d_end), _ptr(d_flags), _opt(d_numbers),
+                                      numbers_capacity, None, _opt(d_verdict), _ptr(d_tape),
+                                      int(tape_capacity), _opt(d_string_buf),
                                       int(string_capacity), _ptr(d_result), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_tape_device failed: {rc}")
@@ -434,9 +484,9 @@ class Stage1Device:
             d_result = torch.zeros(64, dtype=torch.uint8, device=self.device)
         rc = self.lib.msj_tape_documents_device(
             self.ctx, _ptr(d_buf), length, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
-            _ptr(d_doc_first), _ptr(d_docs), _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
-            None, _ptr(d_verdicts) if d_verdicts is not None else None, _ptr(d_tape), int(tape_capacity),
-            _ptr(d_string_buf) if d_string_buf is not None else None, int(string_capacity), _ptr(d_doc_tapes), int(capacity),
+            _ptr(d_doc_first), _ptr(d_docs), _opt(d_numbers if numbers_capacity else None), numbers_capacity,
+            None, _opt(d_verdicts), _ptr(d_tape), int(tape_capacity),
+            _opt(d_string_buf), int(string_capacity), _ptr(d_doc_tapes), int(capacity),
             _ptr(d_result), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_tape_documents_device failed: {rc}")
@@ -486,8 +536,8 @@ class Stage1Device:
             d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
         rc = self.lib.msj_select_documents_device(
             self.ctx, paths.handle, _ptr(d_buf), length, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
-            _ptr(d_doc_first), _ptr(d_docs), _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
-            _ptr(d_numbers_result) if d_numbers_result is not None else None, _ptr(d_verdicts) if d_verdicts is not None else None,
+            _ptr(d_doc_first), _ptr(d_docs), _opt(d_numbers if numbers_capacity else None), numbers_capacity,
+            _opt(d_numbers_result), _opt(d_verdicts),
             _ptr(d_fields), int(capacity), _ptr(d_result), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_select_documents_device failed: {rc}")
@@ -508,39 +558,18 @@ class Stage1Device:
         (``MsjStringColumnResult``, d_offsets, d_valid, d_bytes) -- blocking for the 48-byte result; with sync=False the
         device tensor that holds it, nothing waited for."""
         d_col = d_fields[p]
-        if d_col.stride(-1) != 1 or (d_col.shape[0] > 1 and d_col.stride(0) != 2):
-            raise ValueError("the records of a path must be contiguous")
-        if capacity is None:
-            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_col.shape[0]
-        capacity = int(capacity)
-        if d_offsets is None:
-            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
-        if d_valid is None:
-            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
-        if d_result is None:
-            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        _check_records(d_col, "the records of a path")
+        capacity, d_offsets, d_valid = self._column_rows(d_col, d_offsets, d_valid, capacity)
+        d_result = self._result(d_result)
 
-        def call(d_out, room):
+        def call(room, d_out):
             rc = self.lib.msj_string_column_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_col), _ptr(d_select_result), _ptr(d_offsets),
-                                                   _ptr(d_valid), capacity, _ptr(d_out) if d_out is not None else None, int(room),
-                                                   _ptr(d_result), self._stream())
+                                                   _ptr(d_valid), capacity, _opt(d_out), room, _ptr(d_result), self._stream())
             if rc != 0:
                 raise RuntimeError(f"msj_string_column_device failed: {rc}")
 
-        def read():
-            return _lib.MsjStringColumnResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
-
-        if not strings:
-            d_bytes, bytes_capacity = None, 0
-        elif d_bytes is None:
-            if bytes_capacity is None:
-                call(None, 0)
-                bytes_capacity = read().total_bytes
-            d_bytes = torch.empty(max(int(bytes_capacity), 1), dtype=torch.uint8, device=self.device)
-        elif bytes_capacity is None:
-            bytes_capacity = d_bytes.numel()
-        call(d_bytes, bytes_capacity)
-        return (read() if sync else d_result), d_offsets, d_valid, d_bytes
+        res, (d_bytes,) = self._sized_call(call, _lib.MsjStringColumnResult, d_result, "total_bytes", strings, (d_bytes,), bytes_capacity, 1, sync)
+        return res, d_offsets, d_valid, d_bytes
 
     def raw_column(self, d_buf, length, d_idx, n, d_type, d_match, d_end, d_flags, d_rows, d_rows_select, d_offsets=None, d_valid=None,
                    d_bytes=None, capacity=None, bytes_capacity=None, compact=False, text=True, d_result=None, sync=True):
@@ -554,41 +583,20 @@ class Stage1Device:
         are ``string_column``'s; text=False: the layout-only form alone (d_bytes None).  Returns (``MsjRawColumnResult``,
         d_offsets, d_valid, d_bytes) -- blocking for the 48-byte result; with sync=False the device tensor that holds it,
         nothing waited for."""
-        if d_rows.stride(-1) != 1 or (d_rows.shape[0] > 1 and d_rows.stride(0) != 2):
-            raise ValueError("the records must be contiguous")
-        if capacity is None:
-            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_rows.shape[0]
-        capacity = int(capacity)
-        if d_offsets is None:
-            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
-        if d_valid is None:
-            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
-        if d_result is None:
-            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        _check_records(d_rows, "the records")
+        capacity, d_offsets, d_valid = self._column_rows(d_rows, d_offsets, d_valid, capacity)
+        d_result = self._result(d_result)
         flags = _lib.RAW_COMPACT if compact else 0
 
-        def call(d_out, room):
-            rc = self.lib.msj_raw_column_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), int(n), _ptr(d_type),
-                                                _ptr(d_match) if d_match is not None else None, _ptr(d_end), _ptr(d_flags), _ptr(d_rows),
-                                                _ptr(d_rows_select), _ptr(d_offsets), _ptr(d_valid), capacity,
-                                                _ptr(d_out) if d_out is not None else None, int(room), flags, _ptr(d_result), self._stream())
+        def call(room, d_out):
+            rc = self.lib.msj_raw_column_device(self.ctx, _ptr(d_buf), int(length), _ptr(d_idx), int(n), _ptr(d_type), _opt(d_match), _ptr(d_end),
+                                                _ptr(d_flags), _ptr(d_rows), _ptr(d_rows_select), _ptr(d_offsets), _ptr(d_valid), capacity,
+                                                _opt(d_out), room, flags, _ptr(d_result), self._stream())
             if rc != 0:
                 raise RuntimeError(f"msj_raw_column_device failed: {rc}")
 
-        def read():
-            return _lib.MsjRawColumnResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
-
-        if not text:
-            d_bytes, bytes_capacity = None, 0
-        elif d_bytes is None:
-            if bytes_capacity is None:
-                call(None, 0)
-                bytes_capacity = read().total_bytes
-            d_bytes = torch.empty(max(int(bytes_capacity), 1), dtype=torch.uint8, device=self.device)
-        elif bytes_capacity is None:
-            bytes_capacity = d_bytes.numel()
-        call(d_bytes, bytes_capacity)
-        return (read() if sync else d_result), d_offsets, d_valid, d_bytes
+        res, (d_bytes,) = self._sized_call(call, _lib.MsjRawColumnResult, d_result, "total_bytes", text, (d_bytes,), bytes_capacity, 1, sync)
+        return res, d_offsets, d_valid, d_bytes
 
     def array_column(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_fields, p, d_select_result,
                      d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_offsets=None, d_valid=None, d_elements=None,
@@ -606,45 +614,23 @@ class Stage1Device:
         d_elements_select) -- blocking for the 48-byte result; with sync=False the device tensor that holds it, nothing
         waited for."""
         d_col = d_fields[p]
-        if d_col.stride(-1) != 1 or (d_col.shape[0] > 1 and d_col.stride(0) != 2):
-            raise ValueError("the records of a path must be contiguous")
+        _check_records(d_col, "the records of a path")
         n, numbers_capacity = int(n), int(numbers_capacity)
-        if capacity is None:
-            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_col.shape[0]
-        capacity = int(capacity)
-        if d_offsets is None:
-            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
-        if d_valid is None:
-            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
-        if d_result is None:
-            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
-        if d_elements_select is None:
-            d_elements_select = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        capacity, d_offsets, d_valid = self._column_rows(d_col, d_offsets, d_valid, capacity)
+        d_result, d_elements_select = self._result(d_result), self._result(d_elements_select)
 
-        def call(d_out, room):
+        def call(room, d_out):
             rc = self.lib.msj_array_column_device(
                 self.ctx, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags), _ptr(d_doc_first),
-                _ptr(d_docs), _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
-                _ptr(d_numbers_result) if d_numbers_result is not None else None, _ptr(d_col), _ptr(d_select_result), _ptr(d_offsets),
-                _ptr(d_valid), capacity, _ptr(d_out) if d_out is not None else None, int(room), _ptr(d_result), _ptr(d_elements_select),
+                _ptr(d_docs), _opt(d_numbers if numbers_capacity else None), numbers_capacity, _opt(d_numbers_result), _ptr(d_col),
+                _ptr(d_select_result), _ptr(d_offsets), _ptr(d_valid), capacity, _opt(d_out), room, _ptr(d_result), _ptr(d_elements_select),
                 self._stream())
             if rc != 0:
                 raise RuntimeError(f"msj_array_column_device failed: {rc}")
 
-        def read():
-            return _lib.MsjArrayColumnResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
-
-        if not elements:
-            d_elements, elements_capacity = None, 0
-        elif d_elements is None:
-            if elements_capacity is None:
-                call(None, 0)
-                elements_capacity = read().n_elements
-            d_elements = torch.empty((max(int(elements_capacity), 1), 2), dtype=torch.int64, device=self.device)
-        elif elements_capacity is None:
-            elements_capacity = d_elements.shape[0]
-        call(d_elements, elements_capacity)
-        return (read() if sync else d_result), d_offsets, d_valid, d_elements, d_elements_select
+        res, (d_elements,) = self._sized_call(call, _lib.MsjArrayColumnResult, d_result, "n_elements", elements, (d_elements,),
+                                              elements_capacity, 2, sync)
+        return res, d_offsets, d_valid, d_elements, d_elements_select
 
     def select_elements(self, paths, d_buf, length, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_rows, d_rows_select,
                         d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_fields=None, capacity=None, d_result=None,
@@ -656,8 +642,7 @@ class Stage1Device:
         (n_paths, capacity, 2) as for ``select_documents`` -- default one row per record of d_rows.  Returns
         (``MsjSelectDocumentsResult``, d_fields) -- blocking for the 48-byte result; with sync=False the device tensor that
         holds it, nothing waited for.  That tensor is what ``string_column`` takes as d_select_result for any of the columns."""
-        if d_rows.stride(-1) != 1 or (d_rows.shape[0] > 1 and d_rows.stride(0) != 2):
-            raise ValueError("the element records must be contiguous")
+        _check_records(d_rows, "the element records")
         n, length, numbers_capacity = int(n), int(length), int(numbers_capacity)
         if d_fields is None:
             capacity = d_rows.shape[0] if capacity is None else int(capacity)
@@ -668,8 +653,8 @@ class Stage1Device:
             d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
         rc = self.lib.msj_select_elements_device(
             self.ctx, paths.handle, _ptr(d_buf), length, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
-            _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
-            _ptr(d_numbers_result) if d_numbers_result is not None else None, _ptr(d_rows), _ptr(d_rows_select), _ptr(d_fields),
+            _opt(d_numbers if numbers_capacity else None), numbers_capacity,
+            _opt(d_numbers_result), _ptr(d_rows), _ptr(d_rows_select), _ptr(d_fields),
             int(capacity), _ptr(d_result), self._stream())
         if rc != 0:
             raise RuntimeError(f"msj_select_elements_device failed: {rc}")
@@ -692,45 +677,22 @@ class Stage1Device:
         d_elements_select: uint8[48] that receives the ``msj_select_documents_result`` of the element records (default: a
         new one).  Returns (``MsjArrayColumnResult``, d_offsets, d_valid, d_elements, d_elements_select) -- blocking for the
         48-byte result; with sync=False the device tensor that holds it, nothing waited for."""
-        if d_rows.stride(-1) != 1 or (d_rows.shape[0] > 1 and d_rows.stride(0) != 2):
-            raise ValueError("the records of the rows must be contiguous")
+        _check_records(d_rows, "the records of the rows")
         n, numbers_capacity = int(n), int(numbers_capacity)
-        if capacity is None:
-            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_rows.shape[0]
-        capacity = int(capacity)
-        if d_offsets is None:
-            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
-        if d_valid is None:
-            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
-        if d_result is None:
-            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
-        if d_elements_select is None:
-            d_elements_select = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        capacity, d_offsets, d_valid = self._column_rows(d_rows, d_offsets, d_valid, capacity)
+        d_result, d_elements_select = self._result(d_result), self._result(d_elements_select)
 
-        def call(d_out, room):
+        def call(room, d_out):
             rc = self.lib.msj_array_elements_device(
                 self.ctx, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
-                _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
-                _ptr(d_numbers_result) if d_numbers_result is not None else None, _ptr(d_rows), _ptr(d_rows_select), _ptr(d_offsets),
-                _ptr(d_valid), capacity, _ptr(d_out) if d_out is not None else None, int(room), _ptr(d_result), _ptr(d_elements_select),
-                self._stream())
+                _opt(d_numbers if numbers_capacity else None), numbers_capacity, _opt(d_numbers_result), _ptr(d_rows), _ptr(d_rows_select),
+                _ptr(d_offsets), _ptr(d_valid), capacity, _opt(d_out), room, _ptr(d_result), _ptr(d_elements_select), self._stream())
             if rc != 0:
                 raise RuntimeError(f"msj_array_elements_device failed: {rc}")
 
-        def read():
-            return _lib.MsjArrayColumnResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
-
-        if not elements:
-            d_elements, elements_capacity = None, 0
-        elif d_elements is None:
-            if elements_capacity is None:
-                call(None, 0)
-                elements_capacity = read().n_elements
-            d_elements = torch.empty((max(int(elements_capacity), 1), 2), dtype=torch.int64, device=self.device)
-        elif elements_capacity is None:
-            elements_capacity = d_elements.shape[0]
-        call(d_elements, elements_capacity)
-        return (read() if sync else d_result), d_offsets, d_valid, d_elements, d_elements_select
+        res, (d_elements,) = self._sized_call(call, _lib.MsjArrayColumnResult, d_result, "n_elements", elements, (d_elements,),
+                                              elements_capacity, 2, sync)
+        return res, d_offsets, d_valid, d_elements, d_elements_select
 
     def object_entries(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_rows, d_rows_select, d_numbers=None, numbers_capacity=0,
                        d_numbers_result=None, d_offsets=None, d_valid=None, d_keys=None, d_values=None, capacity=None, entries_capacity=None,
@@ -748,50 +710,25 @@ class Stage1Device:
         the ``msj_select_documents_result`` of the key and of the value records (default: new ones).  Returns
         (``MsjObjectEntriesResult``, d_offsets, d_valid, d_keys, d_values, d_keys_select, d_values_select) -- blocking for the
         48-byte result; with sync=False the device tensor that holds it, nothing waited for."""
-        if d_rows.stride(-1) != 1 or (d_rows.shape[0] > 1 and d_rows.stride(0) != 2):
-            raise ValueError("the records of the rows must be contiguous")
+        _check_records(d_rows, "the records of the rows")
         if (d_keys is None) != (d_values is None):
             raise ValueError("d_keys and d_values come together")
         n, numbers_capacity = int(n), int(numbers_capacity)
-        if capacity is None:
-            capacity = d_offsets.numel() - 1 if d_offsets is not None else d_rows.shape[0]
-        capacity = int(capacity)
-        if d_offsets is None:
-            d_offsets = torch.empty(capacity + 1, dtype=torch.int64, device=self.device)
-        if d_valid is None:
-            d_valid = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
-        if d_result is None:
-            d_result = torch.zeros(48, dtype=torch.uint8, device=self.device)
-        if d_keys_select is None:
-            d_keys_select = torch.zeros(48, dtype=torch.uint8, device=self.device)
-        if d_values_select is None:
-            d_values_select = torch.zeros(48, dtype=torch.uint8, device=self.device)
+        capacity, d_offsets, d_valid = self._column_rows(d_rows, d_offsets, d_valid, capacity)
+        d_result, d_keys_select, d_values_select = self._result(d_result), self._result(d_keys_select), self._result(d_values_select)
 
-        def call(d_k, d_v, room):
+        def call(room, d_k, d_v):
             rc = self.lib.msj_object_entries_device(
                 self.ctx, _ptr(d_idx), n, _ptr(d_type), _ptr(d_depth), _ptr(d_match), _ptr(d_end), _ptr(d_flags),
-                _ptr(d_numbers) if d_numbers is not None and numbers_capacity else None, numbers_capacity,
-                _ptr(d_numbers_result) if d_numbers_result is not None else None, _ptr(d_rows), _ptr(d_rows_select), _ptr(d_offsets),
-                _ptr(d_valid), capacity, _ptr(d_k) if d_k is not None else None, _ptr(d_v) if d_v is not None else None, int(room),
-                _ptr(d_result), _ptr(d_keys_select), _ptr(d_values_select), self._stream())
+                _opt(d_numbers if numbers_capacity else None), numbers_capacity, _opt(d_numbers_result), _ptr(d_rows), _ptr(d_rows_select),
+                _ptr(d_offsets), _ptr(d_valid), capacity, _opt(d_k), _opt(d_v), room, _ptr(d_result), _ptr(d_keys_select),
+                _ptr(d_values_select), self._stream())
             if rc != 0:
                 raise RuntimeError(f"msj_object_entries_device failed: {rc}")
 
-        def read():
-            return _lib.MsjObjectEntriesResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
-
-        if not entries:
-            d_keys, d_values, entries_capacity = None, None, 0
-        elif d_keys is None:
-            if entries_capacity is None:
-                call(None, None, 0)
-                entries_capacity = read().n_entries
-            d_keys = torch.empty((max(int(entries_capacity), 1), 2), dtype=torch.int64, device=self.device)
-            d_values = torch.empty((max(int(entries_capacity), 1), 2), dtype=torch.int64, device=self.device)
-        elif entries_capacity is None:
-            entries_capacity = min(d_keys.shape[0], d_values.shape[0])
-        call(d_keys, d_values, entries_capacity)
-        return (read() if sync else d_result), d_offsets, d_valid, d_keys, d_values, d_keys_select, d_values_select
+        res, (d_keys, d_values) = self._sized_call(call, _lib.MsjObjectEntriesResult, d_result, "n_entries", entries, (d_keys, d_values),
+                                                   entries_capacity, 2, sync)
+        return res, d_offsets, d_valid, d_keys, d_values, d_keys_select, d_values_select
 
     def parse_document(self, d_buf, length, max_depth=100, exact_strings=False):
         """The whole chain for one document in a device buffer: stage 1, ``stage2_prep`` with partners, ``number_values``,

@@ -84,92 +84,73 @@ def number_column(col, dtype=torch.float64):
     return torch.where(valid, values, torch.zeros_like(values)), valid
 
 
-def _string_column(dev, d_window, length, d_fields, p, d_select, rows, bytes_capacity, what):
-    """``string_column`` over `rows` records with a byte buffer that starts from a guess and, when the call says it was too
-    small, is made as large as the call asks once -> (offsets int64[rows + 1], bytes uint8[total], valid bool[rows])"""
-    d_off = torch.empty(rows + 1, dtype=torch.int64, device=d_fields.device)
-    d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=d_fields.device)
-    room = min(length, 32 * rows + 4096) if bytes_capacity is None else int(bytes_capacity)
+def _grow_once(call, d_rows, rows, room, total, what):
+    """A column call over `rows` records whose output buffer starts from a guess of `room` items and, when the call says it
+    was too small, is made as large as the call asks (the result field `total`) once.  call(d_rows, room, **outputs) is the
+    ``Stage1Device`` method with everything else bound; outputs: d_offsets int64[rows + 1], d_valid uint8[rows] and the
+    capacity, made here; d_rows: the records, or the d_fields whose path holds them -- one blank record per path stands in for
+    none.  -> (result, what the call returned behind d_valid, offsets, valid bool[rows]); DocumentStreamError for a code"""
+    dvc = d_rows.device
+    if rows == 0:
+        d_rows = torch.zeros(d_rows.shape[:-2] + (1, 2), dtype=torch.int64, device=dvc)
+    d_off = torch.empty(rows + 1, dtype=torch.int64, device=dvc)
+    d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=dvc)
     for _ in range(2):
-        res, _, _, d_bytes = dev.string_column(d_window, length, d_fields, p, d_select, d_offsets=d_off, d_valid=d_valid, capacity=rows,
-                                               bytes_capacity=room)
+        res, _, _, *out = call(d_rows, room, d_offsets=d_off, d_valid=d_valid, capacity=rows)
         if res.code != errors.CAPACITY or res.n_rows > rows:
             break
-        room = int(res.total_bytes)
+        room = int(getattr(res, total))
     if res.code != 0:
         raise DocumentStreamError(int(res.code), f"{what} could not be laid out")
-    return d_off, d_bytes[:int(res.total_bytes)], d_valid[:rows].view(torch.bool)
+    return res, out, d_off, d_valid[:rows].view(torch.bool)
+
+
+def _string_column(dev, d_window, length, d_fields, p, d_select, rows, bytes_capacity, what):
+    """``string_column`` over `rows` records of path p of d_fields, its byte buffer grown once (``_grow_once``)
+    -> (offsets int64[rows + 1], bytes uint8[total], valid bool[rows])"""
+    room = min(length, 32 * rows + 4096) if bytes_capacity is None else int(bytes_capacity)
+    res, (d_bytes,), d_off, valid = _grow_once(
+        lambda d_f, room, **out: dev.string_column(d_window, length, d_f, p, d_select, bytes_capacity=room, **out),
+        d_fields, rows, room, "total_bytes", what)
+    return d_off, d_bytes[:int(res.total_bytes)], valid
 
 
 def _raw_column(window, d_rows, d_rows_select, rows, compact, bytes_capacity, what):
-    """``raw_column`` over `rows` records with a byte buffer that starts from a guess and, when the call says it was too
-    small, is made as large as the call asks once -> (offsets int64[rows + 1], bytes uint8[total], valid bool[rows])"""
+    """``raw_column`` over `rows` records, its byte buffer grown once (``_grow_once``)
+    -> (offsets int64[rows + 1], bytes uint8[total], valid bool[rows])"""
     w = window
-    dvc = d_rows.device
-    if rows == 0:
-        d_rows = torch.zeros((1, 2), dtype=torch.int64, device=dvc)
-    d_off = torch.empty(rows + 1, dtype=torch.int64, device=dvc)
-    d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=dvc)
     room = min(w.length, 64 * rows + 4096) if bytes_capacity is None else int(bytes_capacity)
-    for _ in range(2):
-        res, _, _, d_bytes = w.dev.raw_column(w.d_window, w.length, w.d_idx, w.n_tokens, w.d_type, w.d_match, w.d_end, w.d_flags, d_rows,
-                                              d_rows_select, d_offsets=d_off, d_valid=d_valid, capacity=rows, bytes_capacity=room,
-                                              compact=compact)
-        if res.code != errors.CAPACITY or res.n_rows > rows:
-            break
-        room = int(res.total_bytes)
-    if res.code != 0:
-        raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be laid out")
-    return d_off, d_bytes[:int(res.total_bytes)], d_valid[:rows].view(torch.bool)
+    res, (d_bytes,), d_off, valid = _grow_once(
+        lambda d_r, room, **out: w.dev.raw_column(w.d_window, w.length, w.d_idx, w.n_tokens, w.d_type, w.d_match, w.d_end, w.d_flags, d_r,
+                                                  d_rows_select, bytes_capacity=room, compact=compact, **out),
+        d_rows, rows, room, "total_bytes", f"window at {w.base}: {what}")
+    return d_off, d_bytes[:int(res.total_bytes)], valid
 
 
 def _array_elements(window, d_rows, d_rows_select, rows, elements_capacity, parent, what):
-    """``array_elements`` over `rows` records with an element buffer that starts from a guess and, when the call says it was
-    too small, is made as large as the call asks once -> ``ListColumn`` with `parent`"""
+    """``array_elements`` over `rows` records, its element buffer grown once (``_grow_once``) -> ``ListColumn`` with `parent`"""
     w = window
-    dvc = d_rows.device
-    if rows == 0:
-        d_rows = torch.zeros((1, 2), dtype=torch.int64, device=dvc)
-    d_off = torch.empty(rows + 1, dtype=torch.int64, device=dvc)
-    d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=dvc)
-    d_esel = torch.zeros(48, dtype=torch.uint8, device=dvc)
     room = min(w.n_tokens, 4 * rows + 4096) if elements_capacity is None else int(elements_capacity)
-    for _ in range(2):
-        res, _, _, d_elements, _ = w.dev.array_elements(
-            w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_rows, d_rows_select, d_numbers=w.d_numbers,
-            numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, d_offsets=d_off, d_valid=d_valid, capacity=rows,
-            elements_capacity=room, d_elements_select=d_esel)
-        if res.code != errors.CAPACITY or res.n_rows > rows:
-            break
-        room = int(res.n_elements)
-    if res.code != 0:
-        raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be laid out")
-    return ListColumn(w, d_off, d_elements[:int(res.n_elements)], d_valid[:rows].view(torch.bool), d_esel, parent)
+    res, (d_elements, d_esel), d_off, valid = _grow_once(
+        lambda d_r, room, **out: w.dev.array_elements(
+            w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_r, d_rows_select, d_numbers=w.d_numbers,
+            numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, elements_capacity=room, **out),
+        d_rows, rows, room, "n_elements", f"window at {w.base}: {what}")
+    return ListColumn(w, d_off, d_elements[:int(res.n_elements)], valid, d_esel, parent)
 
 
 def _object_entries(window, d_rows, d_rows_select, rows, entries_capacity, parent, what):
-    """``object_entries`` over `rows` records with key and value buffers that start from a guess and, when the call says they
-    were too small, are made as large as the call asks once -> ``MapColumn`` with `parent`"""
+    """``object_entries`` over `rows` records, its key and value buffers grown once (``_grow_once``) -> ``MapColumn`` with
+    `parent`"""
     w = window
-    dvc = d_rows.device
-    if rows == 0:
-        d_rows = torch.zeros((1, 2), dtype=torch.int64, device=dvc)
-    d_off = torch.empty(rows + 1, dtype=torch.int64, device=dvc)
-    d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=dvc)
-    d_ksel, d_vsel = torch.zeros(48, dtype=torch.uint8, device=dvc), torch.zeros(48, dtype=torch.uint8, device=dvc)
     room = min(w.n_tokens, 4 * rows + 4096) if entries_capacity is None else int(entries_capacity)
-    for _ in range(2):
-        res, _, _, d_keys, d_values, _, _ = w.dev.object_entries(
-            w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_rows, d_rows_select, d_numbers=w.d_numbers,
-            numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, d_offsets=d_off, d_valid=d_valid, capacity=rows,
-            entries_capacity=room, d_keys_select=d_ksel, d_values_select=d_vsel)
-        if res.code != errors.CAPACITY or res.n_rows > rows:
-            break
-        room = int(res.n_entries)
-    if res.code != 0:
-        raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be laid out")
+    res, (d_keys, d_values, d_ksel, d_vsel), d_off, valid = _grow_once(
+        lambda d_r, room, **out: w.dev.object_entries(
+            w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_r, d_rows_select, d_numbers=w.d_numbers,
+            numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, entries_capacity=room, **out),
+        d_rows, rows, room, "n_entries", f"window at {w.base}: {what}")
     n = int(res.n_entries)
-    return MapColumn(w, d_off, d_valid[:rows].view(torch.bool), d_keys[:n], d_values[:n], d_ksel, d_vsel, parent)
+    return MapColumn(w, d_off, valid, d_keys[:n], d_values[:n], d_ksel, d_vsel, parent)
 
 
 class MapColumn:
@@ -195,8 +176,7 @@ class MapColumn:
         """The keys, unescaped, as a string column on the device (``msj_string_column_device`` over the key records):
         (offsets int64[n_entries + 1], bytes uint8[total], valid bool[n_entries])."""
         w = self.window
-        d_fields = self.key_fields if self.n_entries else torch.zeros((1, 2), dtype=torch.int64, device=self.key_fields.device)
-        return _string_column(w.dev, w.d_window, w.length, d_fields.unsqueeze(0), 0, self.d_keys_select, self.n_entries, bytes_capacity,
+        return _string_column(w.dev, w.d_window, w.length, self.key_fields.unsqueeze(0), 0, self.d_keys_select, self.n_entries, bytes_capacity,
                               f"window at {w.base}: the keys of the entries")
 
     def values(self):
@@ -243,8 +223,7 @@ class ListColumn:
         """The elements that are strings as a column on the device (``msj_string_column_device`` over the element records):
         (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements])."""
         w = self.window
-        d_fields = self.fields if self.n_elements else torch.zeros((1, 2), dtype=torch.int64, device=self.fields.device)
-        return _string_column(w.dev, w.d_window, w.length, d_fields.unsqueeze(0), 0, self.d_select, self.n_elements, bytes_capacity,
+        return _string_column(w.dev, w.d_window, w.length, self.fields.unsqueeze(0), 0, self.d_select, self.n_elements, bytes_capacity,
                               f"window at {w.base}: the strings of the elements")
 
     def raw(self, compact=False, bytes_capacity=None):
@@ -323,8 +302,7 @@ class ElementFields:
         """The strings of one path as a column on the device (``msj_string_column_device`` over the path's records):
         (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements])."""
         w, p = self.list_column.window, self.paths.index(path_or_index)
-        d_fields = self.fields if self.n_elements else torch.zeros((self.fields.shape[0], 1, 2), dtype=torch.int64, device=self.fields.device)
-        return _string_column(w.dev, w.d_window, w.length, d_fields, p, self.d_select, self.n_elements, bytes_capacity,
+        return _string_column(w.dev, w.d_window, w.length, self.fields, p, self.d_select, self.n_elements, bytes_capacity,
                               f"window at {w.base}: the strings of path {p} of the elements")
 
     def raw(self, path_or_index, compact=False, bytes_capacity=None):
@@ -473,23 +451,14 @@ class Window:
             raise ValueError("no fields: the stream was not created with select=[...]")
         p = self.paths.index(path_or_index)
         nd, nt = self.n_documents, self.n_tokens
-        dvc = self.d_fields.device
-        d_off = torch.empty(nd + 1, dtype=torch.int64, device=dvc)
-        d_valid = torch.empty(max(nd, 1), dtype=torch.uint8, device=dvc)
-        d_esel = torch.zeros(48, dtype=torch.uint8, device=dvc)
         room = min(nt, 4 * nd + 4096) if elements_capacity is None else int(elements_capacity)
-        for _ in range(2):
-            res, _, _, d_elements, _ = self.dev.array_column(
-                self.d_idx, nt, self.d_type, self.d_depth, self.d_match, self.d_end, self.d_flags, self.d_doc_first, self.d_docs,
-                self.d_fields, p, self.d_select, d_numbers=self.d_numbers, numbers_capacity=self.d_numbers.shape[0],
-                d_numbers_result=self.d_numbers_result, d_offsets=d_off, d_valid=d_valid, capacity=nd, elements_capacity=room,
-                d_elements_select=d_esel)
-            if res.code != errors.CAPACITY or res.n_rows > nd:
-                break
-            room = int(res.n_elements)
-        if res.code != 0:
-            raise DocumentStreamError(int(res.code), f"window at {self.base}: the arrays of path {p} could not be laid out")
-        return ListColumn(self, d_off, d_elements[:int(res.n_elements)], d_valid[:nd].view(torch.bool), d_esel)
+        res, (d_elements, d_esel), d_off, valid = _grow_once(
+            lambda d_f, room, **out: self.dev.array_column(
+                self.d_idx, nt, self.d_type, self.d_depth, self.d_match, self.d_end, self.d_flags, self.d_doc_first, self.d_docs, d_f, p,
+                self.d_select, d_numbers=self.d_numbers, numbers_capacity=self.d_numbers.shape[0], d_numbers_result=self.d_numbers_result,
+                elements_capacity=room, **out),
+            self.d_fields, nd, room, "n_elements", f"window at {self.base}: the arrays of path {p}")
+        return ListColumn(self, d_off, d_elements[:int(res.n_elements)], valid, d_esel)
 
     def entries(self, path_or_index, entries_capacity=None):
         """The objects of one path as a map column ON THE DEVICE (``msj_object_entries_device``) -> ``MapColumn``: offsets

@@ -7,9 +7,9 @@ bytes of canary behind its capacity, so a store the twin does not make shows).  
 and the twins' records, uploaded, and the real chain (shard, stage2_prep, documents, number_values, validate_documents,
 select_documents, array_column, select_elements), whose device results the call reads.
 
-The kernel constants the shapes lean on: a block of ae_count / ae_emit is 1 024 tokens (csrc/tape_block.h: kBlock); a block
-of rows of ae_live / ae_place is 256 rows, and the kernels over rows sweep 1 024 of them per trip; ae_ranks takes 1 024 block
-sums of rows per chunk and ae_scan 1 024 block counts of tokens.
+The kernel constants the shapes lean on: a block of items_count / items_emit (csrc/rows_block.h) is 1 024 tokens
+(csrc/tape_block.h: kBlock); a block of rows of rows_live / rows_place is 256 rows, and the kernels over rows sweep 1 024 of
+them per trip; rows_ranks takes 1 024 block sums of rows per chunk and items_scan 1 024 block counts of tokens.
 """
 import json
 
@@ -31,10 +31,10 @@ from tests import test_validate_documents_math as tdm
 
 pytestmark = pytest.mark.gpu
 
-BLOCK = 1024                # tokens per workgroup of ae_count / ae_emit
-ROW_BLOCK = 256             # rows per block of rows of ae_live / ae_place
-SWEEP = 1024 * ROW_BLOCK    # rows one trip of the kernels over rows covers, and one chunk of ae_ranks
-SCAN_CHUNK = 1024 * BLOCK   # tokens whose block counts ae_scan takes in one round
+BLOCK = 1024                # tokens per workgroup of items_count / items_emit
+ROW_BLOCK = 256             # rows per block of rows of rows_live / rows_place
+SWEEP = 1024 * ROW_BLOCK    # rows one trip of the kernels over rows covers, and one chunk of rows_ranks
+SCAN_CHUNK = 1024 * BLOCK   # tokens whose block counts items_scan takes in one round
 MSJ_CAPACITY, BAD_ARGUMENT = 1, -1
 
 
@@ -275,8 +275,8 @@ def test_coded_runs_across_blocks_of_rows(env):
 
 
 def test_more_rows_than_one_sweep_and_a_second_scan_chunk(env):
-    """262 500 rows of [j] and [] -- the kernels over rows take their second trip and ae_ranks its second chunk of block sums --
-    in a window of more than 1 048 577 tokens, which gives ae_scan its second chunk."""
+    """262 500 rows of [j] and [] -- the kernels over rows take their second trip and rows_ranks its second chunk of block
+    sums -- in a window of more than 1 048 577 tokens, which gives items_scan its second chunk."""
     per_line, lines = 100, 2625
     line = lambda k: b'{"c":[' + b",".join(b"[%d]" % ((k + j) % 7) if (k + j) % 25 else b"[]" for j in range(per_line)) + b"]}"
     data = b"\n".join(line(k) for k in range(lines)) + b"\n"

@@ -7,9 +7,9 @@ with 64 bytes of canary behind its capacity, so a store the twin does not make s
 arrays and the twins' records, uploaded, and the real chain (shard, stage2_prep, documents, number_values,
 validate_documents, select_documents, array_column, select_elements), whose device results the call reads.
 
-The kernel constants the shapes lean on: a block of oe_count / oe_emit is 1 024 tokens (csrc/tape_block.h: kBlock), its halo
-the ONE token behind it; a block of rows of the kernels over rows (csrc/rows_block.h) is 256 rows, and they sweep 1 024 of them
-per trip; rows_ranks takes 1 024 block sums of rows per chunk and oe_scan 1 024 block counts of tokens.
+The kernel constants the shapes lean on: a block of items_count / items_emit is 1 024 tokens (csrc/tape_block.h: kBlock), its
+halo the ONE token behind it; a block of rows of the kernels over rows (csrc/rows_block.h) is 256 rows, and they sweep 1 024
+of them per trip; rows_ranks takes 1 024 block sums of rows per chunk and items_scan 1 024 block counts of tokens.
 """
 import json
 
@@ -33,10 +33,10 @@ from tests import test_validate_documents_math as tdm
 
 pytestmark = pytest.mark.gpu
 
-BLOCK = 1024                # tokens per workgroup of oe_count / oe_emit
+BLOCK = 1024                # tokens per workgroup of items_count / items_emit
 ROW_BLOCK = 256             # rows per block of rows
 SWEEP = 1024 * ROW_BLOCK    # rows one trip of the kernels over rows covers, and one chunk of rows_ranks
-SCAN_CHUNK = 1024 * BLOCK   # tokens whose block counts oe_scan takes in one round
+SCAN_CHUNK = 1024 * BLOCK   # tokens whose block counts items_scan takes in one round
 MSJ_CAPACITY, BAD_ARGUMENT = 1, -1
 
 
@@ -247,7 +247,7 @@ def test_rows_across_a_block_of_rows(env):
 
 def test_more_rows_than_one_sweep_and_a_second_scan_chunk(env):
     """263 000 elements {"k":j} and {} in one array -- the kernels over rows take their second trip and rows_ranks its second
-    chunk of block sums -- in a window of more than 1 048 576 tokens, which gives oe_scan its second chunk."""
+    chunk of block sums -- in a window of more than 1 048 576 tokens, which gives items_scan its second chunk."""
     R = 263000
     data = b"[" + b",".join(b'{"k":%d}' % (j % 7) if j % 25 else b"{}" for j in range(R)) + b"]\n"
     c = Case(env, data, ("list", ""), chain=True)
