@@ -1266,7 +1266,8 @@ uint64_t msj_array_elements_workspace_bytes(uint64_t n, uint64_t capacity);
  * -- and nothing is launched on either.  Asynchronous on `stream`, no host round trip, workspace in the context.  Safe on ANY
  * arrays and records: every index from a record or from d_match is checked before it is used, tokens i + 1 and i + 2 are read
  * only below n, every store to d_keys / d_values is checked against entries_capacity, and rows at or past R are not touched.
- * Out of scope: any change to the pointer grammar, lookup of a run-time key, de-duplicating keys, typed numeric columns.
+ * Out of scope: any change to the pointer grammar, lookup of a run-time key, de-duplicating keys (the distinct keys of a map
+ * column are msj_dictionary_device over msj_string_column_device over d_keys), typed numeric columns.
  */
 typedef struct msj_object_entries_result {   /* 48 bytes; the layout of msj_array_column_result */
     int32_t  code;          /* 0, MSJ_CAPACITY, MSJ_ERR_BAD_ARGUMENT (the order), or the code of d_rows_select */
@@ -1359,6 +1360,72 @@ int32_t msj_raw_column_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len,
 /* Device workspace of one msj_raw_column_device call (the context keeps it): 8 bytes per row of capacity, 8 per 256 rows, a
  * list of 1 024 long rows; with MSJ_RAW_COMPACT also 8 bytes per token and 8 per 1 024 tokens. */
 uint64_t msj_raw_column_workspace_bytes(uint64_t n, uint64_t capacity, uint32_t flags);
+
+/*
+ * ---- a byte column as codes plus distinct values (DERIVED) ------------------------------------------
+ * msj_dictionary_device -- the dictionary layout of a variable-length byte column: an int32 code per row and the distinct
+ * values back to back.  It answers, without moving a byte to the host: which distinct values does the column have, which
+ * rows are equal, and -- over the keys of a map column of the root objects -- which fields do the documents have at all.
+ * All on the device, on the caller's stream, no host round trip.
+ * Inputs: the (d_offsets, d_bytes, d_valid) layout that msj_string_column_device and msj_raw_column_device write -- a path's
+ * strings, a list's strings, a map's keys, raw JSON texts (on a compact raw column: whole sub-objects) -- or any arrays of
+ * that shape: d_offsets[rows + 1], d_valid[rows], d_bytes[bytes_len].  R, the number of rows, is `rows` when d_n_rows == NULL,
+ * else *d_n_rows read on the device (for example &string_result->n_rows: the call follows a column call without a
+ * synchronisation).  R > rows, or R >= 2^31: MSJ_CAPACITY with n_rows = R and nothing else written.
+ * Row k (k < R) has a value iff d_valid[k] != 0 and d_offsets[k] <= d_offsets[k + 1] <= bytes_len -- checked on the arrays,
+ * never believed; the value is the bytes [d_offsets[k], d_offsets[k + 1]), the empty string is a value.  Any other row is
+ * null.  Two rows are equal iff their values are byte for byte equal: no normalisation (the string column has unescaped
+ * already, so an A written as the escape u0041 and a plain "A" arrive equal).
+ *   d_codes      rows entries, those at or past R not written.  -1 for a null row; else the number of distinct values whose
+ *                first occurrence lies in a row in front of the first occurrence of row k's value: the order of first
+ *                appearance, what dict.setdefault(v, len(d)) gives over the rows in order
+ *   d_dict_first    dict_capacity entries: d_dict_first[c] is the row of code c's first occurrence
+ *   d_dict_offsets  dict_capacity + 1 entries: d_dict_offsets[0] = 0, d_dict_offsets[c + 1] - d_dict_offsets[c] the length of
+ *                   code c's value
+ *   d_dict_bytes    the distinct values back to back in code order, no prefix, no terminator
+ * Entries at or past min(n_distinct, dict_capacity) (offsets: one further) and bytes at or past min(d_dict_offsets[that],
+ * dict_bytes_capacity) are not written: with n_distinct > dict_capacity or dict_bytes > dict_bytes_capacity the codes are
+ * complete, n_distinct and dict_bytes exact, what does not fit is not written, and the code is MSJ_CAPACITY.  All three
+ * dictionary arrays NULL with both capacities 0 is the layout-only form: codes and counts, code 0.  (One of them NULL with
+ * its capacity 0 writes the others, clipped as above.)
+ * Every output but max_probe is a pure function of the input, bit-identical from run to run whatever the scheduling;
+ * max_probe is a diagnostic of the hash table's state, which depends on which row reached a slot first.
+ * d_result: code; flags, the call's; n_rows = R; n_values the rows that are not null; n_distinct; dict_bytes the total bytes
+ * of the distinct values; max_probe the longest probe sequence any row walked.  R == 0 writes d_dict_offsets[0] = 0 and a zero
+ * result (flags kept).
+ * MSJ_DICTIONARY_WEAK_HASH is a TEST AID, like the forced span kernels: the hash of every row becomes 2^64 - 1 - (length mod
+ * 4), so that every chain starts in the table's last four slots and wraps through slot 0, and every slot is decided by the
+ * byte compare.  The result is by definition the same as without it.
+ * Arguments, checked in this order: NULL ctx / d_result; NULL d_offsets / d_valid / d_codes with rows > 0; NULL d_bytes with
+ * bytes_len > 0; NULL d_dict_offsets / d_dict_first with dict_capacity > 0; NULL d_dict_bytes with dict_bytes_capacity > 0; a
+ * flag other than MSJ_DICTIONARY_WEAK_HASH: MSJ_ERR_BAD_ARGUMENT.  Then alignment: d_offsets, d_n_rows, d_dict_offsets,
+ * d_result 8-byte; d_codes, d_dict_first 4-byte; d_bytes, d_valid, d_dict_bytes any: MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of them.  Asynchronous on `stream`, no host round trip, workspace in the
+ * context.  Safe on ANY arrays: d_bytes is read only inside [0, bytes_len), every store to the dictionary arrays is checked
+ * against its capacity, nothing at or past R is touched.
+ * Out of scope: counts per value (bincount of the codes; the Python layer does that), a dictionary shared across windows,
+ * ordering the dictionary by value, case or Unicode folding.
+ */
+#define MSJ_DICTIONARY_WEAK_HASH 1u   /* msj_dictionary_device flags: TEST AID, every chain in the table's last four slots */
+typedef struct msj_dictionary_result {   /* 48 bytes */
+    int32_t  code;        /* 0; MSJ_CAPACITY (R > rows or R >= 2^31: nothing else written; or the dictionary clipped: codes
+                             complete, counts exact); MSJ_UNEXPECTED_ERROR: a row walked the whole table (never) */
+    uint32_t flags;       /* the call's flags */
+    uint64_t n_rows;      /* R */
+    uint64_t n_values;    /* rows that are not null */
+    uint64_t n_distinct;  /* distinct values */
+    uint64_t dict_bytes;  /* total bytes of the distinct values, exact also when clipped and in the layout-only form */
+    uint64_t max_probe;   /* the longest probe sequence any row walked (a diagnostic; not a function of the input alone) */
+} msj_dictionary_result;
+int32_t msj_dictionary_device(msj_ctx *ctx,
+        const uint64_t *d_offsets, const uint8_t *d_valid, uint64_t rows, const uint64_t *d_n_rows,
+        const uint8_t *d_bytes, uint64_t bytes_len,
+        int32_t *d_codes,
+        uint64_t *d_dict_offsets, uint32_t *d_dict_first, uint64_t dict_capacity,
+        uint8_t *d_dict_bytes, uint64_t dict_bytes_capacity,
+        uint32_t flags, msj_dictionary_result *d_result, void *stream);
+/* Device workspace of one msj_dictionary_device call (the context keeps it): 8 + 4 bytes per row (hash, slot), 4 bytes per
+ * table slot (the power of two >= 2 * rows, at least 1 024), 16 per 256 rows (block sums), a list of 1 024 long rows. */
+uint64_t msj_dictionary_workspace_bytes(uint64_t rows);
 
 /*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors

@@ -151,7 +151,15 @@ class MsjRawColumnResult(ctypes.Structure):
                 ("n_containers", ctypes.c_uint64), ("total_bytes", ctypes.c_uint64), ("n_other", ctypes.c_uint64)]
 
 
+class MsjDictionaryResult(ctypes.Structure):
+    """``msj_dictionary_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_values", ctypes.c_uint64),
+                ("n_distinct", ctypes.c_uint64), ("dict_bytes", ctypes.c_uint64), ("max_probe", ctypes.c_uint64)]
+
+
 RAW_COMPACT = 1   # MSJ_RAW_COMPACT
+DICTIONARY_WEAK_HASH = 1   # MSJ_DICTIONARY_WEAK_HASH (a test aid)
 FIELD_NO_BITS = 64
 NO_SUCH_FIELD, INCORRECT_TYPE, INVALID_JSON_POINTER = 20, 17, 22
 MAX_PATHS, MAX_PATH_SEGMENTS, MAX_SEGMENT_BYTES = 16, 8, 255
@@ -177,6 +185,7 @@ assert ctypes.sizeof(MsjDocumentTape) == 32 and ctypes.sizeof(MsjTapeDocumentsRe
 assert ctypes.sizeof(MsjField) == 16 and ctypes.sizeof(MsjSelectDocumentsResult) == 48
 assert ctypes.sizeof(MsjStringColumnResult) == 48 and ctypes.sizeof(MsjArrayColumnResult) == 48
 assert ctypes.sizeof(MsjObjectEntriesResult) == 48 and ctypes.sizeof(MsjRawColumnResult) == 48
+assert ctypes.sizeof(MsjDictionaryResult) == 48
 
 _lib = None
 
@@ -347,6 +356,12 @@ def load():
         [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_raw_column_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_raw_column_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
+    lib.msj_dictionary_device.restype = ctypes.c_int32
+    lib.msj_dictionary_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                          ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_dictionary_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_dictionary_workspace_bytes.argtypes = [ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

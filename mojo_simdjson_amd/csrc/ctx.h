@@ -115,6 +115,7 @@ struct msj_ctx {
     DeviceBuffer aelem_ws;        // msj_array_elements_device: the state, a word and a start token per row, a descriptor and an offset per dense row, the block counts
     DeviceBuffer oent_ws;         // msj_object_entries_device: the same state and arrays (rows_block.h)
     DeviceBuffer rcol_ws;         // msj_raw_column_device: lengths per row, the list of long rows, P per token (compact)
+    DeviceBuffer dict_ws;         // msj_dictionary_device: a hash and a slot per row, the table of rows, the block sums, the list of long rows
 };
 
 // ---- api.cpp ----

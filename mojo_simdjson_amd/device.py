@@ -598,6 +598,61 @@ class Stage1Device:
         res, (d_bytes,) = self._sized_call(call, _lib.MsjRawColumnResult, d_result, "total_bytes", text, (d_bytes,), bytes_capacity, 1, sync)
         return res, d_offsets, d_valid, d_bytes
 
+    def dictionary(self, d_offsets, d_bytes, d_valid, rows=None, d_n_rows=None, bytes_len=None, d_codes=None, d_dict_offsets=None,
+                   d_dict_first=None, d_dict_bytes=None, dict_capacity=None, dict_bytes_capacity=None, values=True, weak_hash=False,
+                   d_result=None, sync=True):
+        """A byte column as codes plus distinct values (``msj_dictionary_device``), all on the device.  d_offsets (int64,
+        rows + 1 entries), d_bytes (uint8) and d_valid (uint8, one per row): what ``string_column`` or ``raw_column`` wrote, or
+        any arrays of that shape; rows: default the room of d_offsets; d_n_rows: an int64 device tensor whose first word is
+        the number of rows, read on the device (for example the ``n_rows`` of a column call's result tensor: ``d_res[8:16]
+        .view(torch.int64)``); bytes_len: default the size of d_bytes.  d_codes: int32 tensor of `rows` entries (default: a
+        new one).  d_dict_offsets (int64, dict_capacity + 1), d_dict_first (int32, dict_capacity), d_dict_bytes (uint8,
+        dict_bytes_capacity): the caller's, all three or none; without them new ones of the named capacities are made, and
+        without those numbers either they are sized from a layout-only first call, whose 48-byte result is waited for.
+        values=False: the layout-only form alone (codes and counts; the three are None).  weak_hash: the test aid
+        MSJ_DICTIONARY_WEAK_HASH.  Returns (``MsjDictionaryResult``, d_codes, d_dict_offsets, d_dict_first, d_dict_bytes) --
+        blocking for the 48-byte result; with sync=False the device tensor that holds it, nothing waited for."""
+        rows = d_offsets.numel() - 1 if rows is None else int(rows)
+        bytes_len = d_bytes.numel() if bytes_len is None else int(bytes_len)
+        if d_codes is None:
+            d_codes = torch.empty(max(rows, 1), dtype=torch.int32, device=self.device)
+        d_result = self._result(d_result)
+        flags = _lib.DICTIONARY_WEAK_HASH if weak_hash else 0
+
+        def call(capacity, room, d_off, d_first, d_out):
+            rc = self.lib.msj_dictionary_device(self.ctx, _ptr(d_offsets), _ptr(d_valid), rows, _opt(d_n_rows), _ptr(d_bytes), bytes_len,
+                                                _ptr(d_codes), _opt(d_off), _opt(d_first), int(capacity), _opt(d_out), int(room), flags,
+                                                _ptr(d_result), self._stream())
+            if rc != 0:
+                raise RuntimeError(f"msj_dictionary_device failed: {rc}")
+
+        def read():
+            return _lib.MsjDictionaryResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
+
+        mine = (d_dict_offsets, d_dict_first, d_dict_bytes)
+        if any(t is None for t in mine) != all(t is None for t in mine):
+            raise ValueError("d_dict_offsets, d_dict_first and d_dict_bytes: all three or none")
+        if not values:
+            d_dict_offsets = d_dict_first = d_dict_bytes = None
+            dict_capacity = dict_bytes_capacity = 0
+        elif d_dict_offsets is None:
+            if dict_capacity is None or dict_bytes_capacity is None:
+                call(0, 0, None, None, None)
+                first = read()
+                dict_capacity = first.n_distinct if dict_capacity is None else dict_capacity
+                dict_bytes_capacity = first.dict_bytes if dict_bytes_capacity is None else dict_bytes_capacity
+            dict_capacity, dict_bytes_capacity = int(dict_capacity), int(dict_bytes_capacity)
+            d_dict_offsets = torch.empty(dict_capacity + 1, dtype=torch.int64, device=self.device)
+            d_dict_first = torch.empty(max(dict_capacity, 1), dtype=torch.int32, device=self.device)
+            d_dict_bytes = torch.empty(max(dict_bytes_capacity, 1), dtype=torch.uint8, device=self.device)
+        else:
+            if dict_capacity is None:
+                dict_capacity = min(d_dict_offsets.numel() - 1, d_dict_first.numel())
+            if dict_bytes_capacity is None:
+                dict_bytes_capacity = d_dict_bytes.numel()
+        call(dict_capacity, dict_bytes_capacity, d_dict_offsets, d_dict_first, d_dict_bytes)
+        return (read() if sync else d_result), d_codes, d_dict_offsets, d_dict_first, d_dict_bytes
+
     def array_column(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_fields, p, d_select_result,
                      d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_offsets=None, d_valid=None, d_elements=None,
                      capacity=None, elements_capacity=None, elements=True, d_result=None, d_elements_select=None, sync=True):

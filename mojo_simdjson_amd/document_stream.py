@@ -153,6 +153,51 @@ def _object_entries(window, d_rows, d_rows_select, rows, entries_capacity, paren
     return MapColumn(w, d_off, valid, d_keys[:n], d_values[:n], d_ksel, d_vsel, parent)
 
 
+_TAGS = '{["ldtfn'  # the value tags of an msj_field
+
+
+class DictionaryColumn:
+    """A byte column in the dictionary layout ON THE DEVICE (``msj_dictionary_device``; ``Window.categories``,
+    ``ListColumn.categories``, ``ElementFields.categories``, ``MapColumn.key_categories``).  codes int32[rows]: -1 for a row
+    without a value, else the value's number in the order of first appearance; offsets int64[n_distinct + 1] and bytes
+    uint8[total]: value c is bytes[offsets[c]:offsets[c + 1]]; first int32[n_distinct]: the row value c first appears in;
+    valid bool[rows], the column's own validity."""
+
+    def __init__(self, codes, offsets, data, first, valid):
+        self.codes, self.offsets, self.bytes, self.first, self.valid = codes, offsets, data, first, valid
+
+    @property
+    def n_distinct(self):
+        return self.first.shape[0]
+
+    def counts(self):
+        """Rows per value, int64[n_distinct], on the device (``torch.bincount`` of the codes that are not -1)."""
+        codes = self.codes[self.codes >= 0].to(torch.int64)
+        return torch.bincount(codes, minlength=self.n_distinct)
+
+    def values(self):
+        """The distinct values as str in the order of first appearance: the dictionary comes to the host, the codes do not."""
+        off, data = self.offsets.cpu().tolist(), self.bytes.cpu().numpy().tobytes()
+        return [data[off[c]:off[c + 1]].decode("utf-8", "surrogateescape") for c in range(self.n_distinct)]
+
+    def to_python(self):
+        """(the distinct values as ``values`` gives them, the codes as a list)."""
+        return self.values(), self.codes.cpu().tolist()
+
+
+def _dictionary(dev, column, what):
+    """``dictionary`` over a column (offsets int64[rows + 1], bytes uint8[total], valid bool[rows]) as the column calls
+    return it, sized from the call's own layout-only pass -> ``DictionaryColumn``"""
+    offsets, data, valid = column
+    rows = valid.shape[0]
+    d_valid = valid.view(torch.uint8) if rows else torch.zeros(1, dtype=torch.uint8, device=offsets.device)
+    res, codes, d_off, d_first, d_bytes = dev.dictionary(offsets, data, d_valid, rows=rows)
+    if res.code != 0:
+        raise DocumentStreamError(int(res.code), f"{what} could not be dictionary-encoded")
+    n = int(res.n_distinct)
+    return DictionaryColumn(codes[:rows], d_off[:n + 1], d_bytes[:int(res.dict_bytes)], d_first[:n], valid)
+
+
 class MapColumn:
     """Objects as a map column ON THE DEVICE (``Window.entries``, ``ListColumn.entries``, ``ElementFields.entries``): the
     members of objects whose keys are data.  offsets int64[rows + 1]; key_fields and value_fields int64[n_entries, 2], one
@@ -178,6 +223,33 @@ class MapColumn:
         w = self.window
         return _string_column(w.dev, w.d_window, w.length, self.key_fields.unsqueeze(0), 0, self.d_keys_select, self.n_entries, bytes_capacity,
                               f"window at {w.base}: the keys of the entries")
+
+    def key_categories(self, bytes_capacity=None):
+        """The keys in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over ``keys()``) ->
+        ``DictionaryColumn`` with one code per entry: the same few names repeated millions of times become one int32 each
+        and the names once."""
+        return _dictionary(self.window.dev, self.keys(bytes_capacity), f"window at {self.window.base}: the keys of the entries")
+
+    def schema(self):
+        """Which keys these objects have: for each distinct key in the order of first appearance (the key, how many entries
+        carry it, the set of value tags -- ``{ [ " l d t f n`` -- seen under it).  Computed on the device: the key codes
+        of ``key_categories``, the type byte of ``value_fields`` and ``torch.bincount``; only the distinct keys and one
+        small table come to the host.  ``Window.entries("").schema()`` is therefore "which fields do these documents have
+        at all" -- what a user has to know before writing ``select=[...]``."""
+        cats = self.key_categories()
+        keys, n = cats.values(), cats.n_distinct
+        if n == 0:
+            return []
+        meta = self.value_fields[:, 1]
+        tag, code = (meta >> 32) & 0xFF, (meta >> 48) & 0xFFFF
+        kind = torch.full((256,), len(_TAGS), dtype=torch.int64, device=meta.device)
+        kind[torch.tensor([ord(c) for c in _TAGS], device=meta.device)] = torch.arange(len(_TAGS), device=meta.device)
+        width = len(_TAGS) + 1  # (the last column: a value record with a code, or a tag that is none)
+        column = torch.where(code == 0, kind[tag], torch.full_like(tag, len(_TAGS)))
+        codes = cats.codes.to(torch.int64)
+        has = codes >= 0
+        table = torch.bincount(codes[has] * width + column[has], minlength=n * width).view(n, width).cpu().tolist()
+        return [(keys[c], sum(table[c]), {t for t, seen in zip(_TAGS, table[c]) if seen}) for c in range(n)]
 
     def values(self):
         """The values as a ``ListColumn`` that shares this column's offsets and validity: ``.numbers()``, ``.strings()``,
@@ -225,6 +297,11 @@ class ListColumn:
         w = self.window
         return _string_column(w.dev, w.d_window, w.length, self.fields.unsqueeze(0), 0, self.d_select, self.n_elements, bytes_capacity,
                               f"window at {w.base}: the strings of the elements")
+
+    def categories(self, bytes_capacity=None):
+        """The elements that are strings in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over
+        ``strings()``) -> ``DictionaryColumn`` with one code per element, -1 where the element is no string."""
+        return _dictionary(self.window.dev, self.strings(bytes_capacity), f"window at {self.window.base}: the strings of the elements")
 
     def raw(self, compact=False, bytes_capacity=None):
         """The JSON text of every element as a column on the device (``msj_raw_column_device`` over the element records):
@@ -304,6 +381,12 @@ class ElementFields:
         w, p = self.list_column.window, self.paths.index(path_or_index)
         return _string_column(w.dev, w.d_window, w.length, self.fields, p, self.d_select, self.n_elements, bytes_capacity,
                               f"window at {w.base}: the strings of path {p} of the elements")
+
+    def categories(self, path_or_index, bytes_capacity=None):
+        """The strings of one path in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over ``strings(path)``)
+        -> ``DictionaryColumn`` with one code per element, -1 where the value is no string or the key is missing."""
+        w = self.list_column.window
+        return _dictionary(w.dev, self.strings(path_or_index, bytes_capacity), f"window at {w.base}: the strings of a path of the elements")
 
     def raw(self, path_or_index, compact=False, bytes_capacity=None):
         """The JSON text of one path's values as a column on the device (``msj_raw_column_device`` over the path's records):
@@ -428,6 +511,13 @@ class Window:
         p = self.paths.index(path_or_index)
         return _string_column(self.dev, self.d_window, self.length, self.d_fields, p, self.d_select, self.n_documents, bytes_capacity,
                               f"window at {self.base}: the strings of path {p}")
+
+    def categories(self, path_or_index, bytes_capacity=None):
+        """The string values of one path in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over
+        ``strings(path)``) -> ``DictionaryColumn``: codes int32[D], -1 where the row has no string, else the value's number
+        in the order of first appearance, and the distinct values once.  A low-cardinality column -- a status, a country, a
+        device id -- is grouped, compared and counted (``counts()``) without moving a byte to the host."""
+        return _dictionary(self.dev, self.strings(path_or_index, bytes_capacity), f"window at {self.base}: the strings of a path")
 
     def raw(self, path_or_index, compact=False, bytes_capacity=None):
         """The JSON text of one path's values as a column ON THE DEVICE (``msj_raw_column_device``): (offsets int64[D + 1],
