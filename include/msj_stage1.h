@@ -129,8 +129,17 @@ int32_t msj_device_count(void);
 const char *msj_version(void);
 
 /* Context: owns the per-device workspace (tile descriptors, carry structs,
- * staging buffers).  Not re-entrant: one in-flight call per context, matching
- * the reference (one parser = one synchronous call). */
+ * staging buffers).  Not re-entrant on the host: one thread per context at a
+ * time, matching the reference (one parser = one synchronous call).  On the
+ * device (tests/test_stream_order.py):
+ *  - any number of calls of one context may be in flight on ONE stream: a
+ *    call's workspace is reused by the next call in stream order, and no call
+ *    waits for the one in front of it;
+ *  - calls of one context on DIFFERENT streams share those workspaces: the
+ *    caller orders them (an event, or a synchronisation in between);
+ *  - a call that has to grow a workspace synchronises the device first, once
+ *    per size (nothing of the context may still be using the old block): a
+ *    chain that has run once over its largest window never waits again. */
 int32_t msj_ctx_create(int32_t device, msj_ctx **out);
 void msj_ctx_destroy(msj_ctx *ctx);
 int32_t msj_ctx_device(const msj_ctx *ctx); /* the HIP device the context was created on (-1: NULL) */
