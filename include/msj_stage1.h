@@ -1437,6 +1437,153 @@ int32_t msj_dictionary_device(msj_ctx *ctx,
 uint64_t msj_dictionary_workspace_bytes(uint64_t rows);
 
 /*
+ * ---- rows by predicate (DERIVED) --------------------------------------------------------------------
+ * msj_filter_rows_device chooses rows, msj_take_rows_device gathers them: "keep the lines where /status == "error" and
+ * /latency_ms > 250" without a copy to the host, without a host wait for the count, without building the string column
+ * first and without casting an int64 to a double.  Both write msj_field records WITH a msj_select_documents_result, which
+ * is all that msj_string_column_device, msj_raw_column_device, msj_array_elements_device, msj_object_entries_device,
+ * msj_select_elements_device and (behind a column call) msj_dictionary_device ask of their rows: the whole chain runs on
+ * filtered rows unchanged.  A filtered window as minified NDJSON is filter -> take -> msj_raw_column_device(MSJ_RAW_COMPACT)
+ * over the "" path; a take by msj_dictionary_device's d_dict_first is one row per distinct value.
+ *
+ * Predicates: msj_predicates_create compiles 1 to 16 msj_predicate, synchronously, into device memory the object owns -- the
+ * twin of msj_paths_create: immutable, usable by any number of later calls on any stream of its context's device;
+ * msj_predicates_destroy(NULL) does nothing.  A predicate names a column c (0..15), an op, flags and an operand, and looks at
+ * ONE record f, that of its column in the row:
+ *   MSJ_PRED_FOUND        f.code == 0
+ *   MSJ_PRED_TYPE         f.code == 0 and f.type is in operand_bits, an 8-bit mask over the tape's tags in the order
+ *                         { [ " l d t f n (MSJ_TYPE_*); a mask of 0 or with other bits set: MSJ_ERR_BAD_ARGUMENT
+ *   MSJ_PRED_NUM_EQ / _LT / _LE / _GT / _GE
+ *                         f.code == 0, f.type is 'l' or 'd', MSJ_FIELD_NO_BITS is not set, and value OP operand holds between
+ *                         the two AS REAL NUMBERS, EXACTLY.  operand_bits is an int64, or with MSJ_PRED_DOUBLE the pattern of
+ *                         a finite binary64 (not finite: MSJ_ERR_BAD_ARGUMENT).  Neither side is cast to the other's type:
+ *                         an int64 i against a double d is decided by the sign when d >= 2^63 or d < -2^63 (-2^63 itself is
+ *                         an int64), else by i against trunc(d) as int64 and on equality by 0 against d - trunc(d), which
+ *                         is exact.  So 9007199254740993 > 9007199254740992.0 holds, and -0.0 == 0.  A record whose double
+ *                         is a NaN (no number call writes one) fails all five.  A number without bits fails all five and
+ *                         its row is counted in n_no_bits
+ *   MSJ_PRED_STR_EQ / MSJ_PRED_STR_PREFIX
+ *                         the operand is operand_len (0..255) bytes at operand_bytes, NUL allowed.  The string value of a
+ *                         row is BY DEFINITION the bytes msj_string_column_device would write for the record, and the row's
+ *                         validity is that call's too: code == 0, type == '"', the span inside the window; the value
+ *                         unescaped as the tape does it when MSJ_SPAN_ESCAPED is set.  STR_EQ: the value equals the
+ *                         operand.  STR_PREFIX: the value starts with it; an empty operand holds for every string row.  A
+ *                         row that is no string fails both.  At most 6 * 255 raw bytes are read per row
+ * MSJ_PRED_NOT inverts the predicate's truth value, INCLUDING for rows that have no value: a record with a code fails
+ * NUM_GT, so it passes NOT NUM_GT.  This is two-valued logic, not SQL's three-valued logic; ask for MSJ_PRED_FOUND as well
+ * where that matters.  MSJ_PREDICATES_ANY on the object: a row is kept when any predicate holds; default: when all hold.
+ * Every predicate is evaluated on every row, whatever the others said: the counts do not depend on an order.
+ * msj_predicates_create returns MSJ_ERR_BAD_ARGUMENT on NULL, a count outside 1..16, a column above 15, an operand over 255
+ * bytes (or without its pointer), an unknown op, an unknown flag (MSJ_PRED_DOUBLE on an op that is not numeric is one).
+ *
+ * msj_filter_rows_device.  Column c is d_fields + c * stride -- the path-major layout the two select calls write; a single
+ * column is n_columns = 1.  R = d_rows_select->n_documents is read on the device.  d_rows_select->code != 0: a zero result
+ * with that code, d_kept_select likewise, nothing else written.  R > capacity or R >= 2^31: MSJ_CAPACITY with n_rows = R,
+ * nothing else written.  A predicate naming a column at or past n_columns: MSJ_ERR_BAD_ARGUMENT on the host.
+ *   d_keep          capacity bytes: d_keep[k] = 1 iff row k is kept, else 0, for k < R
+ *   d_kept          capacity uint32: the kept row numbers ascending, n_kept of them -- the selection vector.  NULL: the
+ *                   mask-only form
+ *   d_kept_select   NULL, or a msj_select_documents_result: code = this call's, n_documents = n_found = n_kept, n_paths = 1,
+ *                   n_no_bits = 0: a later call reads the count on the device
+ *   d_list_offsets / d_list_offsets_out   both NULL, or the offsets of a list column WHOSE ELEMENTS ARE THESE ROWS and their
+ *                   re-based form: P + 1 uint64 each, P = list_rows, or *d_list_n_rows read on the device when that is not
+ *                   NULL.  d_list_offsets_out[r] = the number of kept rows k < min(d_list_offsets[r], R), for r <= P: a
+ *                   gather in the exclusive rank, so defined on any input array; items[*] stays a list column behind
+ *                   items[*].qty > 1.  P > list_rows or P >= 2^31: MSJ_CAPACITY, d_list_offsets_out not written, the rest
+ *                   complete
+ * d_result: code; flags, the object's; n_rows = R; n_kept; n_no_bits, the rows where at least one numeric predicate met a
+ * number without bits; n_missing, the rows where at least one predicate met a record with a code.  R == 0 writes a zero
+ * result (flags kept) and d_list_offsets_out all 0.  Every output is a pure function of the input.
+ * Arguments, checked in this order: NULL ctx / predicates (or predicates of another device) / d_result / d_rows_select /
+ * d_buf; NULL d_fields / d_keep with capacity > 0; one of d_list_offsets / d_list_offsets_out without the other; n_columns
+ * outside 1..16, a predicate's column at or past n_columns, stride < capacity with n_columns > 1: MSJ_ERR_BAD_ARGUMENT.
+ * len > MSJ_MAX_SEGMENT_BYTES: MSJ_CAPACITY.  Then d_result == a select result, d_kept_select == d_rows_select, and alignment
+ * -- d_fields 16-byte; d_kept 4-byte; the offsets, d_list_n_rows, the results and select results 8-byte:
+ * MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of them.  Asynchronous on `stream`, no host round trip, workspace in the
+ * context.  Safe on ANY records: the window is read only inside [0, len), nothing at or past R or capacity is touched.
+ *
+ * msj_take_rows_device gathers records by a selection vector: d_out[c * out_stride + j] = d_fields[c * stride + d_take[j]]
+ * for j < K and c < n_columns, K = d_take_select->n_documents read on the device.  d_take: any uint32 row numbers -- d_kept,
+ * d_dict_first -- in any order, with repeats; K is known on the device only, so the array holds min(K, out_capacity) entries
+ * at least.  `stride` is also the room of a column: R = d_rows_select->n_documents > stride
+ * is MSJ_CAPACITY.  An index at or past R writes the record of a missing value -- code 20, token 0xFFFFFFFF, everything else 0
+ * -- and is counted in n_out_of_range.  K > out_capacity (or K >= 2^31): MSJ_CAPACITY with n_rows = K, nothing else written.
+ * A code in d_take_select (it wins) or d_rows_select: a zero result with that code.  d_out_select: NULL, or a
+ * msj_select_documents_result with code = this call's, n_documents = K, n_paths = n_columns, n_found and n_no_bits RECOUNTED
+ * over what was written, so that any downstream call runs on d_out as on a select call's output.  Rows taken in ascending
+ * order stay ascending, which msj_array_elements_device, msj_object_entries_device and msj_select_elements_device ask for;
+ * their on-device order check catches any other vector.
+ * Arguments, in this order: NULL ctx / d_result / d_take_select / d_rows_select; NULL d_take / d_out with out_capacity > 0,
+ * NULL d_fields with stride > 0; n_columns outside 1..16, out_stride < out_capacity with n_columns > 1: MSJ_ERR_BAD_ARGUMENT;
+ * a stride or capacity of 2^40 records or more: MSJ_CAPACITY; d_out overlapping
+ * d_fields, d_result == a select result, d_out_select == d_take_select or d_rows_select; alignment (d_fields, d_out 16-byte,
+ * d_take 4-byte, the results 8-byte): MSJ_ERR_BAD_ARGUMENT.  Asynchronous on `stream`, safe on ANY arrays.
+ * Out of scope: contains / suffix / regex, predicates on dictionary codes, nested boolean expressions (a second call over
+ * the taken rows is AND), sorting.
+ */
+#define MSJ_PRED_FOUND 0u
+#define MSJ_PRED_TYPE 1u
+#define MSJ_PRED_NUM_EQ 2u
+#define MSJ_PRED_NUM_LT 3u
+#define MSJ_PRED_NUM_LE 4u
+#define MSJ_PRED_NUM_GT 5u
+#define MSJ_PRED_NUM_GE 6u
+#define MSJ_PRED_STR_EQ 7u
+#define MSJ_PRED_STR_PREFIX 8u
+#define MSJ_PRED_NOT 1u        /* msj_predicate.flags: the truth value inverted, also for a row without a value */
+#define MSJ_PRED_DOUBLE 2u     /* msj_predicate.flags, numeric ops: operand_bits is a binary64 pattern, not an int64 */
+#define MSJ_PREDICATES_ANY 1u  /* msj_predicates_create flags: any predicate keeps a row; default: all must hold */
+#define MSJ_TYPE_OBJECT 1u     /* MSJ_PRED_TYPE's mask: { [ " l d t f n */
+#define MSJ_TYPE_ARRAY 2u
+#define MSJ_TYPE_STRING 4u
+#define MSJ_TYPE_INT64 8u
+#define MSJ_TYPE_DOUBLE 16u
+#define MSJ_TYPE_TRUE 32u
+#define MSJ_TYPE_FALSE 64u
+#define MSJ_TYPE_NULL 128u
+typedef struct msj_predicates msj_predicates;
+typedef struct msj_predicate {   /* 32 bytes */
+    uint32_t column;         /* 0..15 */
+    uint32_t op;             /* MSJ_PRED_* */
+    uint32_t flags;          /* MSJ_PRED_NOT, MSJ_PRED_DOUBLE */
+    uint32_t operand_len;    /* string ops: 0..255 */
+    uint64_t operand_bits;   /* numeric ops: the int64, or the binary64 pattern; MSJ_PRED_TYPE: the mask */
+    const uint8_t *operand_bytes;  /* string ops; read during the create call only */
+} msj_predicate;
+typedef struct msj_filter_rows_result {   /* 48 bytes */
+    int32_t  code;       /* 0; MSJ_CAPACITY; or the code of d_rows_select */
+    uint32_t flags;      /* the predicates object's flags */
+    uint64_t n_rows;     /* R */
+    uint64_t n_kept;
+    uint64_t n_no_bits;  /* rows where a numeric predicate met a number with MSJ_FIELD_NO_BITS */
+    uint64_t n_missing;  /* rows where at least one predicate met a record with a code */
+    uint64_t reserved;
+} msj_filter_rows_result;
+typedef struct msj_take_rows_result {   /* 48 bytes */
+    int32_t  code;            /* 0; MSJ_CAPACITY; or the code of d_take_select / d_rows_select */
+    uint32_t flags;           /* 0 */
+    uint64_t n_rows;          /* K */
+    uint64_t n_out_of_range;  /* indices at or past R */
+    uint64_t n_found;         /* records written with code 0, over all columns */
+    uint64_t n_no_bits;       /* records written with MSJ_FIELD_NO_BITS */
+    uint64_t reserved;
+} msj_take_rows_result;
+int32_t msj_predicates_create(msj_ctx *ctx, const msj_predicate *predicates, uint32_t n_predicates, uint32_t flags, msj_predicates **out);
+void msj_predicates_destroy(msj_predicates *predicates);
+int32_t msj_filter_rows_device(msj_ctx *ctx, const msj_predicates *predicates, const uint8_t *d_buf, uint64_t len,
+        const msj_field *d_fields, uint64_t stride, uint32_t n_columns, const msj_select_documents_result *d_rows_select,
+        uint8_t *d_keep, uint32_t *d_kept, uint64_t capacity,
+        const uint64_t *d_list_offsets, uint64_t list_rows, const uint64_t *d_list_n_rows, uint64_t *d_list_offsets_out,
+        msj_filter_rows_result *d_result, msj_select_documents_result *d_kept_select, void *stream);
+int32_t msj_take_rows_device(msj_ctx *ctx, const uint32_t *d_take, const msj_select_documents_result *d_take_select,
+        const msj_field *d_fields, uint64_t stride, uint32_t n_columns, const msj_select_documents_result *d_rows_select,
+        msj_field *d_out, uint64_t out_stride, uint64_t out_capacity,
+        msj_take_rows_result *d_result, msj_select_documents_result *d_out_select, void *stream);
+/* Device workspace of one msj_filter_rows_device call (the context keeps it): 4 bytes per row (the rank), 8 per 256 rows
+ * (block counts).  msj_take_rows_device needs the counters alone. */
+uint64_t msj_filter_rows_workspace_bytes(uint64_t capacity);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

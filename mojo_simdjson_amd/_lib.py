@@ -158,6 +158,33 @@ class MsjDictionaryResult(ctypes.Structure):
                 ("n_distinct", ctypes.c_uint64), ("dict_bytes", ctypes.c_uint64), ("max_probe", ctypes.c_uint64)]
 
 
+class MsjPredicate(ctypes.Structure):
+    """``msj_predicate`` (include/msj_stage1.h)."""
+
+    _fields_ = [("column", ctypes.c_uint32), ("op", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("operand_len", ctypes.c_uint32),
+                ("operand_bits", ctypes.c_uint64), ("operand_bytes", ctypes.c_void_p)]
+
+
+class MsjFilterRowsResult(ctypes.Structure):
+    """``msj_filter_rows_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_kept", ctypes.c_uint64),
+                ("n_no_bits", ctypes.c_uint64), ("n_missing", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+class MsjTakeRowsResult(ctypes.Structure):
+    """``msj_take_rows_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_out_of_range", ctypes.c_uint64),
+                ("n_found", ctypes.c_uint64), ("n_no_bits", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+# msj_predicate.op, .flags, msj_predicates_create's flags, MSJ_PRED_TYPE's mask bits by tape tag
+PRED_FOUND, PRED_TYPE, PRED_NUM_EQ, PRED_NUM_LT, PRED_NUM_LE, PRED_NUM_GT, PRED_NUM_GE, PRED_STR_EQ, PRED_STR_PREFIX = range(9)
+PRED_NOT, PRED_DOUBLE, PREDICATES_ANY = 1, 2, 1
+TYPE_BITS = {"{": 1, "[": 2, '"': 4, "l": 8, "d": 16, "t": 32, "f": 64, "n": 128}
+MAX_PREDICATES, MAX_COLUMNS, MAX_OPERAND_BYTES = 16, 16, 255
+
 RAW_COMPACT = 1   # MSJ_RAW_COMPACT
 DICTIONARY_WEAK_HASH = 1   # MSJ_DICTIONARY_WEAK_HASH (a test aid)
 FIELD_NO_BITS = 64
@@ -362,6 +389,21 @@ def load():
                                           ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_dictionary_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_dictionary_workspace_bytes.argtypes = [ctypes.c_uint64]
+    lib.msj_predicates_create.restype = ctypes.c_int32
+    lib.msj_predicates_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
+    lib.msj_predicates_destroy.restype = None
+    lib.msj_predicates_destroy.argtypes = [ctypes.c_void_p]
+    lib.msj_filter_rows_device.restype = ctypes.c_int32
+    lib.msj_filter_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u8p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_take_rows_device.restype = ctypes.c_int32
+    lib.msj_take_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]
+    lib.msj_filter_rows_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_filter_rows_workspace_bytes.argtypes = [ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

@@ -1,7 +1,7 @@
 // launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 /
 // f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
 // validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
-// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip.  Every launcher and every internal workspace size is declared
+// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, filter_rows_kernel.hip.  Every launcher and every internal workspace size is declared
 // here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
 // compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
 // (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.
@@ -172,3 +172,18 @@ extern "C" int msj_launch_dictionary(const uint64_t *d_offsets, const uint8_t *d
                                      const uint8_t *d_bytes, uint64_t bytes_len, int32_t *d_codes, uint64_t *d_dict_offsets,
                                      uint32_t *d_dict_first, uint64_t dict_capacity, uint8_t *d_dict_bytes, uint64_t dict_bytes_capacity,
                                      uint32_t flags, msj_dictionary_result *d_result, void *d_ws, void *stream);
+
+// ---- filter_rows_kernel.hip ----
+// d_predicates: the compiled predicates (filter_rows_math.h: Predicates) in device memory; d_fields: column c at c * stride;
+// d_kept null: the mask-only form; the two list arrays: both or neither; d_list_n_rows: the list rows on the device, or null
+// for `list_rows`
+extern "C" int msj_launch_filter_rows(const void *d_predicates, const uint8_t *d_buf, uint64_t len, const msj_field *d_fields, uint64_t stride,
+                                      const msj_select_documents_result *d_rows_select, uint8_t *d_keep, uint32_t *d_kept, uint64_t capacity,
+                                      const uint64_t *d_list_offsets, uint64_t list_rows, const uint64_t *d_list_n_rows,
+                                      uint64_t *d_list_offsets_out, msj_filter_rows_result *d_result,
+                                      msj_select_documents_result *d_kept_select, void *d_ws, void *stream);
+// d_take / d_take_select: any row numbers with the select result that counts them; `stride` is also the room of a column
+extern "C" int msj_launch_take_rows(const uint32_t *d_take, const msj_select_documents_result *d_take_select, const msj_field *d_fields,
+                                    uint64_t stride, uint32_t n_columns, const msj_select_documents_result *d_rows_select, msj_field *d_out,
+                                    uint64_t out_stride, uint64_t out_capacity, msj_take_rows_result *d_result,
+                                    msj_select_documents_result *d_out_select, void *d_ws, void *stream);

@@ -2,17 +2,26 @@
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
 // window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
 // elements, the arrays inside list rows, an object's members as a map column, a selected value's JSON text as a column, a byte column as codes plus distinct
-// values.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// values, rows by predicate.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
 // see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
 #include <new>
 
 #include "ctx.h"
+#include "filter_rows_math.h"
 #include "select_math.h"
 
 // msj_paths_create's object: the compiled paths (select_math.h: Paths) in device memory, and what the host needs of them
 struct msj_paths {
     int device = 0;
     uint32_t n_paths = 0, max_levels = 0;
+    DeviceBuffer blob;
+};
+
+// msj_predicates_create's object: the compiled predicates (filter_rows_math.h: Predicates) in device memory, and what the
+// host needs of them
+struct msj_predicates {
+    int device = 0;
+    uint32_t max_column = 0;
     DeviceBuffer blob;
 };
 
@@ -522,6 +531,81 @@ int32_t msj_dictionary_device(msj_ctx *ctx, const uint64_t *d_offsets, const uin
     if (rc != MSJ_SUCCESS) return rc;
     return launched(msj_launch_dictionary(d_offsets, d_valid, rows, d_n_rows, d_bytes, bytes_len, d_codes, d_dict_offsets, d_dict_first,
                                           dict_capacity, d_dict_bytes, dict_bytes_capacity, flags, d_result, ctx->dict_ws.p, stream));
+}
+
+int32_t msj_predicates_create(msj_ctx *ctx, const msj_predicate *predicates, uint32_t n_predicates, uint32_t flags, msj_predicates **out) {
+    using namespace msj::frows;
+    if (!ctx || !out) return MSJ_ERR_BAD_ARGUMENT;
+    std::vector<Predicates> host(1);  // (4 KiB: not on the stack)
+    Predicates &h = host[0];
+    if (compile_predicates(predicates, n_predicates, flags, h) != 0) return MSJ_ERR_BAD_ARGUMENT;
+    if (!hip_ok(hipSetDevice(ctx->device))) return MSJ_ERR_HIP;
+    msj_predicates *obj = new (std::nothrow) msj_predicates;
+    if (!obj) return MSJ_MEMALLOC;
+    obj->device = ctx->device, obj->max_column = h.max_column;
+    if (!obj->blob.reserve(sizeof h, false)) {
+        delete obj;
+        return MSJ_MEMALLOC;
+    }
+    if (!hip_ok(hipMemcpy(obj->blob.p, &h, sizeof h, hipMemcpyHostToDevice))) {  // synchronous: usable on any stream from here on
+        delete obj;
+        return MSJ_ERR_HIP;
+    }
+    *out = obj;
+    return MSJ_SUCCESS;
+}
+
+void msj_predicates_destroy(msj_predicates *predicates) {
+    if (!predicates) return;
+    (void)hipSetDevice(predicates->device);
+    delete predicates;
+}
+
+int32_t msj_filter_rows_device(msj_ctx *ctx, const msj_predicates *predicates, const uint8_t *d_buf, uint64_t len, const msj_field *d_fields,
+                               uint64_t stride, uint32_t n_columns, const msj_select_documents_result *d_rows_select, uint8_t *d_keep,
+                               uint32_t *d_kept, uint64_t capacity, const uint64_t *d_list_offsets, uint64_t list_rows,
+                               const uint64_t *d_list_n_rows, uint64_t *d_list_offsets_out, msj_filter_rows_result *d_result,
+                               msj_select_documents_result *d_kept_select, void *stream) {
+    if (!ctx || !predicates || predicates->device != ctx->device || !d_result || !d_rows_select || !d_buf) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && (!d_fields || !d_keep)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((d_list_offsets == nullptr) != (d_list_offsets_out == nullptr)) return MSJ_ERR_BAD_ARGUMENT;
+    if (n_columns == 0 || n_columns > msj::frows::kMaxColumns || predicates->max_column >= n_columns || (n_columns > 1 && stride < capacity))
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (len > MSJ_MAX_SEGMENT_BYTES) return MSJ_CAPACITY;
+    if ((const void *)d_result == (const void *)d_rows_select || (const void *)d_result == (const void *)d_kept_select ||
+        d_kept_select == d_rows_select)
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (!aligned(d_fields, 16) || !aligned(d_kept, 4) ||
+        !all_aligned(8, d_list_offsets, d_list_n_rows, d_list_offsets_out, d_rows_select, d_result, d_kept_select))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->frow_ws, msj_filter_rows_workspace_bytes(capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_filter_rows(predicates->blob.p, d_buf, len, d_fields, stride, d_rows_select, d_keep, d_kept, capacity, d_list_offsets,
+                                           list_rows, d_list_n_rows, d_list_offsets_out, d_result, d_kept_select, ctx->frow_ws.p, stream));
+}
+
+int32_t msj_take_rows_device(msj_ctx *ctx, const uint32_t *d_take, const msj_select_documents_result *d_take_select, const msj_field *d_fields,
+                             uint64_t stride, uint32_t n_columns, const msj_select_documents_result *d_rows_select, msj_field *d_out,
+                             uint64_t out_stride, uint64_t out_capacity, msj_take_rows_result *d_result,
+                             msj_select_documents_result *d_out_select, void *stream) {
+    if (!ctx || !d_result || !d_take_select || !d_rows_select) return MSJ_ERR_BAD_ARGUMENT;
+    if ((out_capacity > 0 && (!d_take || !d_out)) || (stride > 0 && !d_fields)) return MSJ_ERR_BAD_ARGUMENT;
+    if (n_columns == 0 || n_columns > msj::frows::kMaxColumns || (n_columns > 1 && out_stride < out_capacity)) return MSJ_ERR_BAD_ARGUMENT;
+    if (stride >= (1ull << 40) || out_stride >= (1ull << 40) || out_capacity >= (1ull << 40)) return MSJ_CAPACITY;  // (the extents below: no overflow)
+    if (d_out && d_fields) {  // the two sets of records may not share a byte
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_fields), b = reinterpret_cast<uintptr_t>(d_out);
+        const uint64_t a_bytes = 16 * (uint64_t)n_columns * stride, b_bytes = 16 * ((uint64_t)(n_columns - 1) * out_stride + out_capacity);
+        if (a < b + b_bytes && b < a + a_bytes) return MSJ_ERR_BAD_ARGUMENT;
+    }
+    if ((const void *)d_result == (const void *)d_take_select || (const void *)d_result == (const void *)d_rows_select ||
+        (const void *)d_result == (const void *)d_out_select || d_out_select == d_take_select || d_out_select == d_rows_select)
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (!all_aligned(16, d_fields, d_out) || !aligned(d_take, 4) || !all_aligned(8, d_take_select, d_rows_select, d_result, d_out_select))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->take_ws, msj_filter_rows_workspace_bytes(0));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_take_rows(d_take, d_take_select, d_fields, stride, n_columns, d_rows_select, d_out, out_stride, out_capacity, d_result,
+                                         d_out_select, ctx->take_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

@@ -5,6 +5,7 @@ every byte of the hot path runs in libmsj_stage1.so's HIP kernels through the C
 ABI (``msj_stage1_device`` / ``msj_stage1_shard_device``, include/msj_stage1.h).
 """
 import ctypes
+import struct
 
 import torch
 
@@ -50,6 +51,64 @@ class Paths:
             self.handle = None
 
 
+class Predicates:
+    """Compiled row predicates (``msj_predicates``), from ``Stage1Device.compile_predicates``."""
+
+    def __init__(self, lib, handle, n_predicates, max_column, any_):
+        self.lib, self.handle = lib, handle
+        self.n_predicates, self.max_column, self.any = n_predicates, max_column, any_
+
+    def close(self):
+        if self.handle:
+            self.lib.msj_predicates_destroy(self.handle)
+            self.handle = None
+
+
+_TYPE_NAMES = {"object": 1, "array": 2, "string": 4, "int": 8, "double": 16, "number": 8 | 16, "true": 32, "false": 64, "bool": 32 | 64,
+               "null": 128}
+_NUM_OPS = {"==": _lib.PRED_NUM_EQ, "<": _lib.PRED_NUM_LT, "<=": _lib.PRED_NUM_LE, ">": _lib.PRED_NUM_GT, ">=": _lib.PRED_NUM_GE}
+_STR_OPS = {"==": _lib.PRED_STR_EQ, "prefix": _lib.PRED_STR_PREFIX}
+
+
+def predicate_struct(spec, keep_alive):
+    """One spec of ``Stage1Device.compile_predicates`` -> ``_lib.MsjPredicate``; operand bytes are appended to keep_alive"""
+    flags = 0
+    while len(spec) == 2 and spec[0] == "not":
+        flags ^= _lib.PRED_NOT
+        spec = spec[1]
+    if len(spec) not in (2, 3) or isinstance(spec[0], bool) or not isinstance(spec[0], int) or not isinstance(spec[1], str):
+        raise ValueError(f"a predicate is (column, op, operand), (column, 'found') or ('not', predicate): {spec!r}")
+    column, op = spec[0], spec[1]
+    operand = spec[2] if len(spec) == 3 else None
+    if column < 0:
+        raise ValueError(f"a column is 0..{_lib.MAX_COLUMNS - 1}: {spec!r}")
+    if op == "found" and operand is None:
+        return _lib.MsjPredicate(column, _lib.PRED_FOUND, flags, 0, 0, None)
+    if op == "type":
+        names = [operand] if isinstance(operand, str) else list(operand or ())
+        if not names or any(n not in _TYPE_NAMES for n in names):
+            raise ValueError(f"a type is one or several of {sorted(_TYPE_NAMES)}: {spec!r}")
+        mask = 0
+        for n in names:
+            mask |= _TYPE_NAMES[n]
+        return _lib.MsjPredicate(column, _lib.PRED_TYPE, flags, 0, mask, None)
+    if isinstance(operand, bool):
+        raise ValueError(f"a bool is no operand (use (column, 'type', 'true')): {spec!r}")
+    if isinstance(operand, (str, bytes)) and op in _STR_OPS:
+        data = operand.encode("utf-8") if isinstance(operand, str) else bytes(operand)
+        buf = ctypes.create_string_buffer(data, max(len(data), 1))
+        keep_alive.append(buf)
+        return _lib.MsjPredicate(column, _STR_OPS[op], flags, len(data), 0, ctypes.addressof(buf))
+    if isinstance(operand, int) and op in _NUM_OPS:
+        if not -(1 << 63) <= operand < (1 << 63):
+            raise ValueError(f"an int operand is an int64 (write a float for more): {spec!r}")
+        return _lib.MsjPredicate(column, _NUM_OPS[op], flags, 0, operand & 0xFFFFFFFFFFFFFFFF, None)
+    if isinstance(operand, float) and op in _NUM_OPS:
+        bits = int.from_bytes(struct.pack("<d", operand), "little")
+        return _lib.MsjPredicate(column, _NUM_OPS[op], flags | _lib.PRED_DOUBLE, 0, bits, None)
+    raise ValueError(f"no such predicate: {spec!r}")
+
+
 class Stage1Device:
     """One ``msj_ctx`` bound to one GPU (one process per GPU)."""
 
@@ -64,7 +123,7 @@ class Stage1Device:
         if rc != 0:
             raise RuntimeError(f"msj_ctx_create failed: {rc}")
         self.ctx = h
-        self._paths = []  # what compile_paths handed out: closed with the device
+        self._paths = []  # what compile_paths and compile_predicates handed out: closed with the device
 
     def close(self):
         if self.ctx:
@@ -652,6 +711,106 @@ class Stage1Device:
                 dict_bytes_capacity = d_dict_bytes.numel()
         call(dict_capacity, dict_bytes_capacity, d_dict_offsets, d_dict_first, d_dict_bytes)
         return (read() if sync else d_result), d_codes, d_dict_offsets, d_dict_first, d_dict_bytes
+
+    def compile_predicates(self, specs, any=False):
+        """Compile 1 to 16 row predicates for ``filter_rows`` (``msj_predicates_create``).  A spec is a tuple (column, op,
+        operand): ``(0, "==", "error")``, ``(0, "prefix", b"err")``, ``(1, ">", 250)``, ``(1, "<=", 0.5)``, ``(2, "type",
+        "object")`` (or a list of "object" "array" "string" "int" "double" "number" "true" "false" "bool" "null"), ``(0,
+        "found")``, or ``("not", spec)``.  column: 0..15, the column of the records the call is given.  A str (UTF-8) or
+        bytes operand picks the string ops == and prefix; an int (an int64) or a float (finite) the numeric ops == < <= > >=,
+        which compare as real numbers, exactly; a bool is rejected.  "not" inverts the truth value also for a row without a
+        value.  any=True: a row is kept when any predicate holds (default: all).  The handle is immutable, usable by any
+        number of calls, and closed with the device.  ValueError for what is no predicate or beyond the limits."""
+        specs = list(specs)
+        alive = []
+        table = (_lib.MsjPredicate * max(len(specs), 1))(*[predicate_struct(s, alive) for s in specs])
+        h = ctypes.c_void_p()
+        rc = self.lib.msj_predicates_create(self.ctx, table, len(specs), _lib.PREDICATES_ANY if any else 0, ctypes.byref(h))
+        if rc == -1:
+            raise ValueError(f"1 to {_lib.MAX_PREDICATES} predicates on columns 0..{_lib.MAX_COLUMNS - 1}, operands of at most "
+                             f"{_lib.MAX_OPERAND_BYTES} bytes or finite: {specs}")
+        if rc != 0:
+            raise RuntimeError(f"msj_predicates_create failed: {rc}")
+        predicates = Predicates(self.lib, h, len(specs), max(int(t.column) for t in table), bool(any))
+        self._paths.append(predicates)
+        return predicates
+
+    @staticmethod
+    def _record_columns(d_fields, what):
+        """Records as int64 of shape (rows, 2) or (n_columns, rows, 2) -> (n_columns, rows, stride in records)"""
+        if d_fields.dim() == 2:
+            _check_records(d_fields, what)
+            return 1, d_fields.shape[0], d_fields.shape[0]
+        _check_records(d_fields[0], what)
+        stride = d_fields.stride(0) // 2 if d_fields.shape[0] > 1 else d_fields.shape[1]
+        if d_fields.shape[0] > 1 and d_fields.stride(0) % 2:
+            raise ValueError(f"{what} must be contiguous")
+        return d_fields.shape[0], d_fields.shape[1], stride
+
+    def filter_rows(self, predicates, d_buf, length, d_fields, d_rows_select, capacity=None, d_keep=None, d_kept=None, kept=True,
+                    d_list_offsets=None, list_rows=None, d_list_n_rows=None, d_list_offsets_out=None, d_result=None, d_kept_select=None,
+                    sync=True):
+        """Rows by predicate (``msj_filter_rows_device``): a keep byte per row and the kept row numbers ascending, all on
+        the device.  predicates: from ``compile_predicates``; d_buf / length: the window the records were written over;
+        d_fields: int64 of shape (n_columns, rows, 2) -- what ``select_documents`` or ``select_elements`` wrote -- or (rows, 2)
+        for a single column; d_rows_select: the device ``msj_select_documents_result`` that counts the rows, read on the
+        device.  capacity: default the rows of d_fields.  d_keep: uint8 tensor of capacity entries, d_kept: int32 tensor of
+        capacity entries (default: new ones); kept=False: the mask-only form (d_kept None).  d_list_offsets: int64 tensor,
+        the offsets of a list column whose elements are these rows, list_rows + 1 entries (default: its room), d_list_n_rows
+        an int64 device word that holds the list's rows; d_list_offsets_out receives the re-based offsets (default: a new
+        one).  d_kept_select: uint8[48] that receives the ``msj_select_documents_result`` that counts the kept rows (default:
+        a new one) -- what ``take_rows`` reads as d_take_select.  Returns (``MsjFilterRowsResult``, d_keep, d_kept,
+        d_kept_select, d_list_offsets_out) -- blocking for the 48-byte result; with sync=False the device tensor that holds
+        it, nothing waited for."""
+        n_columns, rows, stride = self._record_columns(d_fields, "the records")
+        capacity = rows if capacity is None else int(capacity)
+        if d_keep is None:
+            d_keep = torch.empty(max(capacity, 1), dtype=torch.uint8, device=self.device)
+        if not kept:
+            d_kept = None
+        elif d_kept is None:
+            d_kept = torch.empty(max(capacity, 1), dtype=torch.int32, device=self.device)
+        if d_list_offsets is not None:
+            list_rows = d_list_offsets.numel() - 1 if list_rows is None else int(list_rows)
+            if d_list_offsets_out is None:
+                d_list_offsets_out = torch.empty(list_rows + 1, dtype=torch.int64, device=self.device)
+        d_result, d_kept_select = self._result(d_result), self._result(d_kept_select)
+        rc = self.lib.msj_filter_rows_device(
+            self.ctx, predicates.handle, _ptr(d_buf), int(length), _ptr(d_fields), stride, n_columns, _ptr(d_rows_select), _ptr(d_keep),
+            _opt(d_kept), capacity, _opt(d_list_offsets), int(list_rows or 0), _opt(d_list_n_rows), _opt(d_list_offsets_out), _ptr(d_result),
+            _ptr(d_kept_select), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_filter_rows_device failed: {rc}")
+        res = _lib.MsjFilterRowsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_keep, d_kept, d_kept_select, d_list_offsets_out
+
+    def take_rows(self, d_take, d_take_select, d_fields, d_rows_select, d_out=None, out_capacity=None, d_result=None, d_out_select=None,
+                  sync=True):
+        """Records gathered by a selection vector (``msj_take_rows_device``): d_out[c, j] = d_fields[c, d_take[j]], all on
+        the device.  d_take: int32 tensor of row numbers, any order, repeats allowed -- ``filter_rows``' d_kept, ``dictionary``'s
+        d_dict_first; d_take_select: the device ``msj_select_documents_result`` whose n_documents counts them
+        (``filter_rows``' d_kept_select), read on the device; d_fields / d_rows_select: the records, int64 of shape
+        (n_columns, rows, 2) or (rows, 2), and the select result that counts their rows.  An index at or past the rows gives
+        the record of a missing value.  d_out: int64 tensor of shape (n_columns, out_capacity, 2) (default: a new one,
+        out_capacity = the entries of d_take).  d_out_select: uint8[48] that receives the ``msj_select_documents_result`` of
+        d_out (default: a new one), so that every call that takes records takes these.  Returns (``MsjTakeRowsResult``, d_out,
+        d_out_select) -- blocking for the 48-byte result; with sync=False the device tensor that holds it, nothing waited
+        for."""
+        n_columns, _, stride = self._record_columns(d_fields, "the records")
+        if d_out is None:
+            out_capacity = d_take.numel() if out_capacity is None else int(out_capacity)
+            d_out = torch.empty((n_columns, max(out_capacity, 1), 2), dtype=torch.int64, device=self.device)
+        out_columns, out_rows, out_stride = self._record_columns(d_out, "the output records")
+        if out_columns != n_columns:
+            raise ValueError("d_out has as many columns as d_fields")
+        out_capacity = out_rows if out_capacity is None else int(out_capacity)
+        d_result, d_out_select = self._result(d_result), self._result(d_out_select)
+        rc = self.lib.msj_take_rows_device(self.ctx, _ptr(d_take), _ptr(d_take_select), _ptr(d_fields), stride, n_columns, _ptr(d_rows_select),
+                                           _ptr(d_out), out_stride, out_capacity, _ptr(d_result), _ptr(d_out_select), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_take_rows_device failed: {rc}")
+        res = _lib.MsjTakeRowsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_out, d_out_select
 
     def array_column(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_fields, p, d_select_result,
                      d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_offsets=None, d_valid=None, d_elements=None,

@@ -153,6 +153,59 @@ def _object_entries(window, d_rows, d_rows_select, rows, entries_capacity, paren
     return MapColumn(w, d_off, valid, d_keys[:n], d_values[:n], d_ksel, d_vsel, parent)
 
 
+def _column_specs(specs, index):
+    """Predicate specs whose columns are named by pointer or index -> the specs ``Stage1Device.compile_predicates`` takes;
+    index: what turns a name into the column's number"""
+    def one(spec):
+        spec = tuple(spec)
+        if len(spec) == 2 and spec[0] == "not":
+            return ("not", one(spec[1]))
+        return (index(spec[0]),) + spec[1:]
+
+    return [one(s) for s in specs]
+
+
+def _select_word(dvc, n):
+    """A ``msj_select_documents_result`` on the device that counts n records of one column"""
+    return torch.tensor(list(bytes(_lib.MsjSelectDocumentsResult(0, 0, int(n), 1, int(n), 0, 0))), dtype=torch.uint8, device=dvc)
+
+
+def _take(window, d_take, d_take_select, n_take, d_fields, d_rows_select, what):
+    """``take_rows`` of n_take row numbers from d_fields (int64[n_columns, rows, 2], or [rows, 2] for one column)
+    -> (fields int64[n_columns, n_take, 2], the uint8[48] select result that goes with them)"""
+    w = window
+    if d_fields.dim() == 2:
+        d_fields = d_fields.unsqueeze(0)
+    if d_fields.shape[1] == 0:   # (no row to take from: every index is out of range)
+        d_fields = torch.zeros((d_fields.shape[0], 1, 2), dtype=torch.int64, device=d_fields.device)
+    d_res, d_out, d_out_select = w.dev.take_rows(d_take, d_take_select, d_fields, d_rows_select, out_capacity=n_take, sync=False)
+    code = int(d_res[:4].view(torch.int32).item())
+    if code != 0:
+        raise DocumentStreamError(code, f"window at {w.base}: {what} could not be taken")
+    return d_out[:, :n_take], d_out_select
+
+
+def _filter(window, specs, any, d_fields, d_rows_select, rows, what, d_list_offsets=None):
+    """``filter_rows`` over `rows` records per column of d_fields -> (keep bool[rows], kept int32[n_kept], the uint8[48] select
+    result that counts them, the re-based list offsets or None).  The predicates live for the call; its 48-byte result comes
+    to the host, which sizes what follows by n_kept."""
+    w = window
+    if d_fields.dim() == 2:
+        d_fields = d_fields.unsqueeze(0)
+    if rows == 0:
+        d_fields = torch.zeros((d_fields.shape[0], 1, 2), dtype=torch.int64, device=d_fields.device)
+    predicates = w.dev.compile_predicates(specs, any=any)
+    try:
+        res, d_keep, d_kept, d_kept_select, d_list_out = w.dev.filter_rows(predicates, w.d_window, w.length, d_fields, d_rows_select, capacity=rows,
+                                                                           d_list_offsets=d_list_offsets)
+    finally:
+        predicates.close()
+        w.dev._paths.remove(predicates)
+    if res.code != 0 or res.n_rows != rows:
+        raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be filtered")
+    return d_keep[:rows].view(torch.bool), d_kept[:int(res.n_kept)], d_kept_select, d_list_out
+
+
 _TAGS = '{["ldtfn'  # the value tags of an msj_field
 
 
@@ -336,6 +389,22 @@ class ListColumn:
             raise DocumentStreamError(code, f"window at {w.base}: the fields of the elements could not be selected")
         return ElementFields(self, paths, d_fields[:, :self.n_elements], res)
 
+    def _kept_elements(self, specs, any, d_fields, d_rows_select, what):
+        """The filter over one record (or more, path-major) per element, the offsets re-based, the element records taken
+        -> (kept int32[n_kept], its select result, the new ``ListColumn``)"""
+        w, n = self.window, self.n_elements
+        _, kept, d_kept_select, d_off = _filter(w, specs, any, d_fields, d_rows_select, n, what, d_list_offsets=self.offsets)
+        fields, d_esel = _take(w, kept, d_kept_select, kept.shape[0], self.fields, self.d_select, what)
+        return kept, d_kept_select, ListColumn(w, d_off, fields[0], self.valid, d_esel, self.parent)
+
+    def where(self, specs, any=False):
+        """The elements that pass predicates -- ``tags[*] == "red"``, ``scores[*] > 0.5`` -- ON THE DEVICE
+        (``msj_filter_rows_device`` with the list offsets re-based, ``msj_take_rows_device``) -> a ``ListColumn`` with this
+        column's rows and validity, new offsets, and the records of the kept elements in their order.  specs: as for
+        ``Stage1Device.compile_predicates``, the elements themselves being column 0."""
+        specs = _column_specs(specs, lambda c: range(1)[c])
+        return self._kept_elements(specs, any, self.fields, self.d_select, "the elements")[2]
+
     def elements(self, elements_capacity=None):
         """The arrays among this column's elements as a list column of their own -- a list of lists -- ON THE DEVICE
         (``msj_array_elements_device``) -> ``ListColumn`` with one row per element of this column, aligned with this column's
@@ -396,6 +465,19 @@ class ElementFields:
         return _raw_column(self.list_column.window, self.fields[p], self.d_select, self.n_elements, compact, bytes_capacity,
                            f"the text of path {p} of the elements")
 
+    def where(self, specs, any=False):
+        """The elements whose fields pass predicates -- ``items[*].qty > 1`` -- ON THE DEVICE (``msj_filter_rows_device`` with
+        the list offsets re-based, ``msj_take_rows_device``) -> ``ElementFields`` over the kept elements, whose ``list_column``
+        is a new ``ListColumn`` with the parent's rows and validity, the re-based offsets and the element records taken with
+        the same vector: ``items[*]`` stays a list column.  specs: as for ``Stage1Device.compile_predicates``, the columns
+        named by pointer or index."""
+        col, w = self.list_column, self.list_column.window
+        specs = _column_specs(specs, self.paths.index)
+        what = "the fields of the elements"
+        kept, d_kept_select, column = col._kept_elements(specs, any, self.fields, self.d_select, what)
+        fields, d_fsel = _take(w, kept, d_kept_select, kept.shape[0], self.fields, self.d_select, what)
+        return ElementFields(column, self.paths, fields, d_fsel)
+
     def elements(self, path_or_index, elements_capacity=None):
         """The arrays of one path as a list column -- ``items[*].tags`` -- ON THE DEVICE (``msj_array_elements_device``) ->
         ``ListColumn`` with one row per element of the list column the fields were selected in; a missing key and a value
@@ -428,6 +510,66 @@ class ElementFields:
         cols = [(pointer, self.column(p)) for p, pointer in enumerate(self.paths.pointers)]
         struct_of = lambda j: {pointer: field_value(c[j], *host) for pointer, c in cols if c[j]["code"] == 0}
         return [[struct_of(j) for j in range(off[k], off[k + 1])] if ok[k] else None for k in range(len(ok))]
+
+
+class RowSelection:
+    """Rows of a window chosen by predicate or by number ON THE DEVICE (``Window.where``, ``Window.take``).  keep bool[D]: the
+    mask over the window's documents (None for ``Window.take``); rows int32[n_rows]: the chosen documents' numbers -- ascending
+    from ``where``; fields int64[n_paths, n_rows, 2]: their records, each path a column; d_select uint8[48], the
+    ``msj_select_documents_result`` that goes with them.  The methods mean what they mean on ``Window``, over the chosen rows.
+    Like every array a Window carries, the window's own arrays are reused by the next window."""
+
+    def __init__(self, window, keep, rows, fields, d_select):
+        self.window, self.paths, self.keep, self.rows, self.fields, self.d_select = window, window.paths, keep, rows, fields, d_select
+
+    @property
+    def n_rows(self):
+        return self.rows.shape[0]
+
+    def column(self, path_or_index):
+        """The records of one path as a numpy structured array (FIELD_DTYPE), one per chosen row: one host copy."""
+        p = self.paths.index(path_or_index)
+        return np.ascontiguousarray(self.fields[p].cpu().numpy()).view(FIELD_DTYPE).reshape(-1)
+
+    def values(self, path_or_index):
+        """The values of one path as a Python list, one per chosen row, see ``Window.values``."""
+        host = self.window._host_arrays()
+        return [field_value(r, *host) for r in self.column(path_or_index)]
+
+    def number_column(self, path_or_index, dtype=torch.float64):
+        """The numbers of one path as ``Window.number_column`` gives them: (values dtype[n_rows], valid bool[n_rows])."""
+        return number_column(self.fields[self.paths.index(path_or_index)], dtype)
+
+    def strings(self, path_or_index, bytes_capacity=None):
+        """The strings of one path as a column on the device, see ``Window.strings``: (offsets int64[n_rows + 1], bytes
+        uint8[total], valid bool[n_rows])."""
+        w, p = self.window, self.paths.index(path_or_index)
+        return _string_column(w.dev, w.d_window, w.length, self.fields, p, self.d_select, self.n_rows, bytes_capacity,
+                              f"window at {w.base}: the strings of path {p} of the chosen rows")
+
+    def categories(self, path_or_index, bytes_capacity=None):
+        """The strings of one path in the dictionary layout, see ``Window.categories`` -> ``DictionaryColumn``."""
+        w = self.window
+        return _dictionary(w.dev, self.strings(path_or_index, bytes_capacity), f"window at {w.base}: the strings of a path of the chosen rows")
+
+    def raw(self, path_or_index, compact=False, bytes_capacity=None):
+        """The JSON text of one path's values, see ``Window.raw``; ``raw("", compact=True)`` is the chosen documents as
+        minified NDJSON lines."""
+        p = self.paths.index(path_or_index)
+        return _raw_column(self.window, self.fields[p], self.d_select, self.n_rows, compact, bytes_capacity, f"the text of path {p} of the chosen rows")
+
+    def elements(self, path_or_index, elements_capacity=None):
+        """The arrays of one path as a ``ListColumn`` with one row per chosen row (``msj_array_elements_device``: the rows are
+        records, no longer the documents)."""
+        p = self.paths.index(path_or_index)
+        return _array_elements(self.window, self.fields[p], self.d_select, self.n_rows, elements_capacity, None,
+                               f"the arrays of path {p} of the chosen rows")
+
+    def entries(self, path_or_index, entries_capacity=None):
+        """The objects of one path as a ``MapColumn`` with one row per chosen row (``msj_object_entries_device``)."""
+        p = self.paths.index(path_or_index)
+        return _object_entries(self.window, self.fields[p], self.d_select, self.n_rows, entries_capacity, None,
+                               f"the objects of path {p} of the chosen rows")
 
 
 def _skip_flag(n):
@@ -560,6 +702,31 @@ class Window:
             raise ValueError("no fields: the stream was not created with select=[...]")
         p = self.paths.index(path_or_index)
         return _object_entries(self, self.d_fields[p], self.d_select, self.n_documents, entries_capacity, None, f"the objects of path {p}")
+
+    def where(self, specs, any=False):
+        """The documents that pass predicates on their selected fields ON THE DEVICE (``msj_filter_rows_device``,
+        ``msj_take_rows_device``) -> ``RowSelection``: ``win.where([("/status", "==", "error"), ("/latency_ms", ">", 250)])``.
+        specs: as for ``Stage1Device.compile_predicates`` with the columns named by pointer or index; a string compare is
+        on the unescaped value, a number compare exact between int64 and double; ("not", spec) also passes a document
+        without the value.  any=True: one predicate is enough.  Only the call's 48-byte result comes to the host."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        specs = _column_specs(specs, self.paths.index)
+        keep, kept, d_kept_select, _ = _filter(self, specs, any, self.d_fields, self.d_select, self.n_documents, "the documents")
+        fields, d_fsel = _take(self, kept, d_kept_select, kept.shape[0], self.d_fields, self.d_select, "the documents")
+        return RowSelection(self, keep, kept, fields, d_fsel)
+
+    def take(self, rows):
+        """The documents with the given numbers ON THE DEVICE (``msj_take_rows_device``) -> ``RowSelection``.  rows: an int32
+        device tensor, any order, repeats allowed -- ``categories(path).first`` gives one document per distinct value; a
+        number at or past n_documents gives a row of missing values."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        rows = rows.to(device=self.d_fields.device, dtype=torch.int32).contiguous()
+        n = rows.shape[0]
+        d_take = rows if n else torch.zeros(1, dtype=torch.int32, device=rows.device)
+        fields, d_fsel = _take(self, d_take, _select_word(rows.device, n), n, self.d_fields, self.d_select, "the documents")
+        return RowSelection(self, None, rows, fields, d_fsel)
 
     def number_column(self, path_or_index, dtype=torch.float64):
         """The numbers of one path as a column ON THE DEVICE, from the records alone (torch operations, no call): (values
