@@ -1584,6 +1584,91 @@ int32_t msj_take_rows_device(msj_ctx *ctx, const uint32_t *d_take, const msj_sel
 uint64_t msj_filter_rows_workspace_bytes(uint64_t capacity);
 
 /*
+ * ---- timestamps and numbers written as strings (DERIVED) ----------------------------------------------
+ * JSON has no type for a timestamp, and producers quote numbers to protect them from double-only readers: "ts":
+ * "2024-05-01T12:34:56.789Z", "id":"9007199254740993", "price":"12.50".  msj_cast_strings_device reads such a column of
+ * strings and writes msj_field records of type 'l' or 'd' WITH a msj_select_documents_result, which is all that
+ * msj_filter_rows_device, msj_take_rows_device and a number column ask of a column: "/ts >= T0 and /ts < T1" is two
+ * MSJ_PRED_NUM_* predicates on an exact int64, on the device, without building the string column first.
+ *
+ * R = d_rows_select->n_documents is read on the device.  The output record of row k < R:
+ *   the input has a code       the input record, unchanged
+ *   a string row               a string by msj_string_column_device's test: code == 0, type == '"', the span inside the window
+ *                              (a record whose span leaves the window is no string and is never dereferenced).  The row's
+ *                              VALUE is by definition the bytes the string column would write, escapes resolved as the tape
+ *                              does: "\u0032024-05-01" is 2024-05-01.  The value is of the kind's grammar and in range: bits =
+ *                              the value, token = the input's token (ascending rows stay ascending, and the raw text is still
+ *                              found), type 'l' or 'd', flags 0, code 0.  Otherwise: code 9 (NUMBER_ERROR of the reference's
+ *                              error table), token 0xFFFFFFFF, everything else 0, and the row is counted in n_syntax (the
+ *                              value is not of the grammar) or n_range (it is, and has no int64 / binary64)
+ *   no string, code 0          with MSJ_CAST_KEEP_NUMBERS an 'l' / 'd' record is copied as it is, MSJ_FIELD_NO_BITS included,
+ *                              and counted in n_cast; every other record becomes code 17 (INCORRECT_TYPE), token 0xFFFFFFFF,
+ *                              everything else 0, and is counted in n_other
+ * MSJ_CAST_NUMBER: the value, WHOLE, is one JSON number -- no blank in front of it or behind it, no '+' -- and the record is
+ * exactly what msj_number_values_device gives for the same text as a token: MSJ_NUMBER_INT64 'l', MSJ_NUMBER_DOUBLE 'd',
+ * MSJ_NUMBER_ERR_SYNTAX n_syntax, MSJ_NUMBER_ERR_RANGE n_range.  "9007199254740993" stays an exact int64; "-0" is the int64
+ * 0; "1e400" is n_range.  LIMIT: a value of more than 128 bytes is n_syntax without being read (an escaped body of more than
+ * 6 * 128 raw bytes likewise) -- where MSJ_SPAN_LONG starts at 1 024 characters for a number token, a quoted number ends at
+ * 128.  `unit` must be 0.
+ * MSJ_CAST_TIMESTAMP: RFC 3339 with the relaxations real producers need:
+ *   date      = YYYY "-" MM "-" DD                      year 0000..9999, proleptic Gregorian, the day valid for month and leap year
+ *   time      = hh ":" mm [ ":" ss [ ("." | ",") 1*9DIGIT ] ]     hh 00..23, mm 00..59, ss 00..59 (a leap second 60 is n_syntax)
+ *   offset    = "Z" | "z" | ("+" | "-") hh [ [":"] mm ]           hh 00..23, mm 00..59; none: UTC
+ *   timestamp = date [ ("T" | "t" | " ") time [offset] ]          a date alone is its midnight UTC
+ * The longest member has 35 bytes: a longer value is n_syntax without being read, an escaped body of more than 6 * 35 raw
+ * bytes likewise.  The value is (days_from_civil(date) * 86400 + hh * 3600 + mm * 60 + ss - offset_seconds) * U + the fraction
+ * CUT to the unit's digits (a floor: the fraction is not negative), U = 1, 10^3, 10^6, 10^9 for MSJ_CAST_UNIT_S / _MS / _US /
+ * _NS, as an int64 ('l').  0000-01-01T00:00:00Z is -62167219200 s, 9999-12-31T23:59:59Z is 253402300799 s; an offset may
+ * push the instant outside that span, which is a value like any other.  A result outside int64 is n_range, which only
+ * MSJ_CAST_UNIT_NS can meet: 2262-04-11T23:47:16.854775807Z is 2^63 - 1, 1677-09-21T00:12:43.145224192Z is -2^63, one step
+ * further is n_range -- decided without a multiply that wraps.
+ *
+ * d_result: code; flags = kind | unit << 8 | flags << 16; n_rows = R; n_cast the records written with code 0, kept numbers
+ * included; n_syntax; n_range; n_other.  d_rows_select->code != 0: a zero result with that code (flags kept), d_out_select
+ * likewise, nothing else written.  R > capacity or R >= 2^31: MSJ_CAPACITY with n_rows = R, nothing else written.  R == 0
+ * writes zero results, flags kept.  d_out_select: NULL, or a msj_select_documents_result with code = this call's,
+ * n_documents = R, n_paths = 1, n_found = n_cast and n_no_bits RECOUNTED over what was written, so that any downstream call
+ * runs on d_out as on a select call's output.  d_out == d_rows exactly is allowed, a cast in place: a row is read by the lane
+ * that writes it, before it writes.  Every output is a pure function of the input.
+ * Arguments, checked in this order: NULL ctx / d_result / d_rows_select / d_buf; NULL d_rows / d_out with capacity > 0; an
+ * unknown kind, unit or flag, a unit other than 0 with MSJ_CAST_NUMBER: MSJ_ERR_BAD_ARGUMENT.  len > MSJ_MAX_SEGMENT_BYTES or
+ * a capacity of 2^40 records or more: MSJ_CAPACITY.  Then d_out overlapping d_rows in any way but d_out == d_rows, d_result ==
+ * a select result, d_out_select == d_rows_select, and alignment -- d_rows, d_out 16-byte; the result and select results
+ * 8-byte: MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of them.  Asynchronous on `stream`, no host round trip, workspace
+ * in the context.  Safe on ANY records: the window is read only inside [0, len), nothing at or past R or capacity is touched.
+ * Out of scope: format strings (%d/%m/%Y), time-zone names, week and ordinal dates, the basic format without dashes, leap
+ * seconds; durations; booleans in strings; casting to a dictionary code; numbers of more than 128 bytes.
+ */
+#define MSJ_CAST_TIMESTAMP 1u
+#define MSJ_CAST_NUMBER    2u
+#define MSJ_CAST_UNIT_S  0u   /* timestamps: the int64 counts seconds / milli / micro / nanoseconds since 1970-01-01T00:00:00Z */
+#define MSJ_CAST_UNIT_MS 1u
+#define MSJ_CAST_UNIT_US 2u
+#define MSJ_CAST_UNIT_NS 3u
+#define MSJ_CAST_KEEP_NUMBERS 1u   /* flags: a row that already is a number ('l' / 'd') is copied as it is instead of code 17 */
+typedef struct msj_cast_strings_result {   /* 48 bytes */
+    int32_t  code;      /* 0; MSJ_CAPACITY (R > capacity or R >= 2^31: n_rows = R, nothing else written); or d_rows_select->code */
+    uint32_t flags;     /* kind | unit << 8 | flags << 16 */
+    uint64_t n_rows;    /* R */
+    uint64_t n_cast;    /* records written with code 0 (kept numbers included) */
+    uint64_t n_syntax;  /* string rows whose value is not of the kind's grammar */
+    uint64_t n_range;   /* string rows of the grammar whose value has no int64 / binary64 */
+    uint64_t n_other;   /* rows with code 0 that are neither a string nor a kept number */
+} msj_cast_strings_result;
+int32_t msj_cast_strings_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len,
+        const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
+        uint32_t kind, uint32_t unit, uint32_t flags,
+        msj_field *d_out, uint64_t capacity,
+        msj_cast_strings_result *d_result, msj_select_documents_result *d_out_select, void *stream);
+/* Device workspace of one msj_cast_strings_device call (the context keeps it): the counters and 4 bytes per row (the list of
+ * the rows whose body is escaped or whose number needs the exact path). */
+uint64_t msj_cast_strings_workspace_bytes(uint64_t capacity);
+/* Measurement only (scripts/cast_strings_rate.py): how the kernel fetches a body's bytes.  Both forms write the same records. */
+#define MSJ_CAST_FETCH_WINDOW 0u   /* the aligned 16-byte words that cover the body, through LDS (the default) */
+#define MSJ_CAST_FETCH_BYTES  1u   /* byte loads from the window */
+int32_t msj_debug_set_cast_fetch(msj_ctx *ctx, uint32_t fetch);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

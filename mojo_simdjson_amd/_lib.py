@@ -179,6 +179,21 @@ class MsjTakeRowsResult(ctypes.Structure):
                 ("n_found", ctypes.c_uint64), ("n_no_bits", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
 
 
+class MsjCastStringsResult(ctypes.Structure):
+    """``msj_cast_strings_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_cast", ctypes.c_uint64),
+                ("n_syntax", ctypes.c_uint64), ("n_range", ctypes.c_uint64), ("n_other", ctypes.c_uint64)]
+
+
+# msj_cast_strings_device: kind, unit, flags; msj_debug_set_cast_fetch
+CAST_TIMESTAMP, CAST_NUMBER = 1, 2
+CAST_KINDS = {"timestamp": CAST_TIMESTAMP, "number": CAST_NUMBER}
+CAST_UNITS = {"s": 0, "ms": 1, "us": 2, "ns": 3}
+CAST_UNIT_PER_SECOND = {"s": 1, "ms": 10**3, "us": 10**6, "ns": 10**9}
+CAST_KEEP_NUMBERS = 1
+CAST_FETCH_WINDOW, CAST_FETCH_BYTES = 0, 1
+
 # msj_predicate.op, .flags, msj_predicates_create's flags, MSJ_PRED_TYPE's mask bits by tape tag
 PRED_FOUND, PRED_TYPE, PRED_NUM_EQ, PRED_NUM_LT, PRED_NUM_LE, PRED_NUM_GT, PRED_NUM_GE, PRED_STR_EQ, PRED_STR_PREFIX = range(9)
 PRED_NOT, PRED_DOUBLE, PREDICATES_ANY = 1, 2, 1
@@ -404,6 +419,14 @@ def load():
                                          ctypes.c_void_p]
     lib.msj_filter_rows_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_filter_rows_workspace_bytes.argtypes = [ctypes.c_uint64]
+    lib.msj_cast_strings_device.restype = ctypes.c_int32
+    lib.msj_cast_strings_device.argtypes = [ctypes.c_void_p, u8p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_cast_strings_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_cast_strings_workspace_bytes.argtypes = [ctypes.c_uint64]
+    lib.msj_debug_set_cast_fetch.restype = ctypes.c_int32
+    lib.msj_debug_set_cast_fetch.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

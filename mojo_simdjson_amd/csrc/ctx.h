@@ -118,6 +118,8 @@ struct msj_ctx {
     DeviceBuffer dict_ws;         // msj_dictionary_device: a hash and a slot per row, the table of rows, the block sums, the list of long rows
     DeviceBuffer frow_ws;         // msj_filter_rows_device: the counters, a count per block of rows, a rank per row
     DeviceBuffer take_ws;         // msj_take_rows_device: the counters
+    DeviceBuffer cast_ws;         // msj_cast_strings_device: the counters, the list of the rows the lane path leaves over
+    uint32_t cast_fetch = 0;      // msj_debug_set_cast_fetch: MSJ_CAST_FETCH_*
 };
 
 // ---- api.cpp ----

@@ -187,3 +187,10 @@ extern "C" int msj_launch_take_rows(const uint32_t *d_take, const msj_select_doc
                                     uint64_t stride, uint32_t n_columns, const msj_select_documents_result *d_rows_select, msj_field *d_out,
                                     uint64_t out_stride, uint64_t out_capacity, msj_take_rows_result *d_result,
                                     msj_select_documents_result *d_out_select, void *d_ws, void *stream);
+
+// ---- cast_strings_kernel.hip ----
+// d_rows / d_rows_select: any records with their select result; kind / unit / flags: checked by the caller
+// (cast_strings_math.h: check_kind); fetch: MSJ_CAST_FETCH_*; d_out == d_rows: in place
+extern "C" int msj_launch_cast_strings(const uint8_t *d_buf, uint64_t len, const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
+                                       uint32_t kind, uint32_t unit, uint32_t flags, uint32_t fetch, msj_field *d_out, uint64_t capacity,
+                                       msj_cast_strings_result *d_result, msj_select_documents_result *d_out_select, void *d_ws, void *stream);

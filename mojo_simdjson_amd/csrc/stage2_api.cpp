@@ -7,6 +7,7 @@
 #include <new>
 
 #include "ctx.h"
+#include "cast_strings_math.h"
 #include "filter_rows_math.h"
 #include "select_math.h"
 
@@ -606,6 +607,32 @@ int32_t msj_take_rows_device(msj_ctx *ctx, const uint32_t *d_take, const msj_sel
     if (rc != MSJ_SUCCESS) return rc;
     return launched(msj_launch_take_rows(d_take, d_take_select, d_fields, stride, n_columns, d_rows_select, d_out, out_stride, out_capacity, d_result,
                                          d_out_select, ctx->take_ws.p, stream));
+}
+
+int32_t msj_cast_strings_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len, const msj_field *d_rows,
+                                const msj_select_documents_result *d_rows_select, uint32_t kind, uint32_t unit, uint32_t flags, msj_field *d_out,
+                                uint64_t capacity, msj_cast_strings_result *d_result, msj_select_documents_result *d_out_select, void *stream) {
+    if (!ctx || !d_result || !d_rows_select || !d_buf) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && (!d_rows || !d_out)) return MSJ_ERR_BAD_ARGUMENT;
+    if (msj::cast::check_kind(kind, unit, flags) != 0) return MSJ_ERR_BAD_ARGUMENT;
+    if (len > MSJ_MAX_SEGMENT_BYTES || capacity >= (1ull << 40)) return MSJ_CAPACITY;  // (the extent below: no overflow)
+    if (d_out && d_rows && d_out != d_rows) {  // in place, or no byte shared
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_rows), b = reinterpret_cast<uintptr_t>(d_out);
+        if (a < b + 16 * capacity && b < a + 16 * capacity) return MSJ_ERR_BAD_ARGUMENT;
+    }
+    if ((const void *)d_result == (const void *)d_rows_select || (const void *)d_result == (const void *)d_out_select ||
+        d_out_select == d_rows_select)
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (!all_aligned(16, d_rows, d_out) || !all_aligned(8, d_rows_select, d_result, d_out_select)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->cast_ws, msj_cast_strings_workspace_bytes(capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_cast_strings(d_buf, len, d_rows, d_rows_select, kind, unit, flags, ctx->cast_fetch, d_out, capacity, d_result,
+                                            d_out_select, ctx->cast_ws.p, stream));
+}
+int32_t msj_debug_set_cast_fetch(msj_ctx *ctx, uint32_t fetch) {
+    if (!ctx || fetch > MSJ_CAST_FETCH_BYTES) return MSJ_ERR_BAD_ARGUMENT;
+    ctx->cast_fetch = fetch;
+    return MSJ_SUCCESS;
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

@@ -812,6 +812,37 @@ class Stage1Device:
         res = _lib.MsjTakeRowsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
         return res, d_out, d_out_select
 
+    def cast_strings(self, d_window, length, d_rows, d_rows_select, kind, unit="ns", keep_numbers=False, capacity=None, d_out=None,
+                     d_result=None, d_out_select=None, sync=True):
+        """Timestamps and numbers written as strings, as number records (``msj_cast_strings_device``), all on the device.
+        d_window / length: the window the records were written over; d_rows: int64 of shape (rows, 2), any ``msj_field``
+        records -- a path of ``select_documents`` or ``select_elements``, the elements of a list column, taken rows;
+        d_rows_select: the device ``msj_select_documents_result`` that counts them, read on the device.  kind: "timestamp"
+        (RFC 3339; the int64 counts `unit` -- "s" "ms" "us" "ns" -- since 1970-01-01T00:00:00Z, a fraction cut to the unit)
+        or "number" (the string, whole, is one JSON number: an exact int64 or the nearest double; the unit is ignored).
+        keep_numbers: a row that already is a number is copied instead of becoming code 17.  capacity: default the rows of
+        d_rows.  d_out: int64 tensor of shape (capacity, 2) (default: a new one); d_rows itself casts in place.  d_out_select:
+        uint8[48] that receives the ``msj_select_documents_result`` of d_out (default: a new one), so that ``filter_rows``,
+        ``take_rows`` and ``number_column`` take the cast records as they take a select call's.  Returns
+        (``MsjCastStringsResult``, d_out, d_out_select) -- blocking for the 48-byte result; with sync=False the device tensor
+        that holds it, nothing waited for."""
+        _check_records(d_rows, "the records")
+        if kind not in _lib.CAST_KINDS or unit not in _lib.CAST_UNITS:
+            raise ValueError(f"kind is one of {sorted(_lib.CAST_KINDS)}, unit one of {sorted(_lib.CAST_UNITS)}: {kind!r}, {unit!r}")
+        capacity = d_rows.shape[0] if capacity is None else int(capacity)
+        if d_out is None:
+            d_out = torch.empty((max(capacity, 1), 2), dtype=torch.int64, device=self.device)
+        _check_records(d_out, "the output records")
+        d_result, d_out_select = self._result(d_result), self._result(d_out_select)
+        number = kind == "number"
+        rc = self.lib.msj_cast_strings_device(self.ctx, _ptr(d_window), int(length), _ptr(d_rows), _ptr(d_rows_select), _lib.CAST_KINDS[kind],
+                                              0 if number else _lib.CAST_UNITS[unit], _lib.CAST_KEEP_NUMBERS if keep_numbers else 0,
+                                              _ptr(d_out), capacity, _ptr(d_result), _ptr(d_out_select), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_cast_strings_device failed: {rc}")
+        res = _lib.MsjCastStringsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_out, d_out_select
+
     def array_column(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_fields, p, d_select_result,
                      d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_offsets=None, d_valid=None, d_elements=None,
                      capacity=None, elements_capacity=None, elements=True, d_result=None, d_elements_select=None, sync=True):

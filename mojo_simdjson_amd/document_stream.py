@@ -14,6 +14,7 @@ Every window starts at a document.  Stage 1 wants a 16-byte aligned base, so the
 the document's offset rounded down and the up to 15 bytes in front (the end of the previous document)
 read as blanks (``MSJ_FLAG_SKIP``).  Offsets in ``d_idx`` are relative to ``Window.base``.
 """
+import datetime
 import json
 import struct
 from dataclasses import dataclass, field
@@ -206,6 +207,82 @@ def _filter(window, specs, any, d_fields, d_rows_select, rows, what, d_list_offs
     return d_keep[:rows].view(torch.bool), d_kept[:int(res.n_kept)], d_kept_select, d_list_out
 
 
+_EPOCH = datetime.datetime(1970, 1, 1, tzinfo=datetime.timezone.utc)
+
+
+def datetime_units(when, unit):
+    """A ``datetime.datetime`` as the int64 ``cast_strings`` gives a timestamp of that instant in `unit` ("s" "ms" "us" "ns"):
+    integer arithmetic on the timedelta since 1970-01-01T00:00:00Z, never a float; microseconds the unit has no digits for
+    are cut (a floor), as the call cuts a fraction.  Aware, or naive, which means UTC."""
+    if when.tzinfo is None or when.utcoffset() is None:
+        when = when.replace(tzinfo=datetime.timezone.utc)
+    delta = when - _EPOCH
+    micros = (delta.days * 86400 + delta.seconds) * 10**6 + delta.microseconds
+    per = _lib.CAST_UNIT_PER_SECOND[unit]
+    return micros * (per // 10**6) if per >= 10**6 else micros // (10**6 // per)
+
+
+def _cast_spec(spec):
+    """"number", "timestamp" or ("timestamp", unit) -> (kind, unit)"""
+    kind, unit = (spec, "ns") if isinstance(spec, str) else tuple(spec)
+    if kind not in _lib.CAST_KINDS or unit not in _lib.CAST_UNITS:
+        raise ValueError(f"a cast is 'number', 'timestamp' or ('timestamp', 's' | 'ms' | 'us' | 'ns'): {spec!r}")
+    return kind, unit
+
+
+def _cast(window, d_rows, d_rows_select, rows, kind, unit, keep_numbers, what):
+    """``cast_strings`` over `rows` records (int64[rows, 2]) -> (the cast records int64[rows, 2], the uint8[48] select result
+    that goes with them).  Only the call's 48-byte result comes to the host."""
+    w = window
+    if rows == 0:
+        d_rows = torch.zeros((1, 2), dtype=torch.int64, device=d_rows.device)
+    d_res, d_out, d_out_select = w.dev.cast_strings(w.d_window, w.length, d_rows.contiguous(), d_rows_select, kind, unit, keep_numbers,
+                                                    capacity=rows, sync=False)
+    code = int(d_res[:4].view(torch.int32).item())
+    if code != 0:
+        raise DocumentStreamError(code, f"window at {w.base}: {what} could not be cast")
+    return d_out[:rows], d_out_select
+
+
+def _cast_numbers(window, d_rows, d_rows_select, rows, kind, unit, keep_numbers, dtype, what):
+    """``number_column`` over the cast records: (values dtype[rows], valid bool[rows])"""
+    return number_column(_cast(window, d_rows, d_rows_select, rows, kind, unit, keep_numbers, what)[0], dtype)
+
+
+def _cast_for_filter(window, specs, cast, index, d_fields, d_rows_select, rows, what):
+    """What ``where(..., cast=...)`` hands the filter: the columns the predicates name, copied, the cast ones replaced by
+    their cast records (a quoted number next to a plain one is kept), and the specs re-numbered onto that copy with every
+    ``datetime.datetime`` operand turned into its column's unit.  specs: already by column number.  -> (specs, d_fields)"""
+    if d_fields.dim() == 2:
+        d_fields = d_fields.unsqueeze(0)
+    kinds = {index(name): _cast_spec(spec) for name, spec in cast.items()}
+
+    def columns(spec):
+        return columns(spec[1]) if len(spec) == 2 and spec[0] == "not" else {spec[0]}
+
+    used = sorted(set().union(*[columns(s) for s in specs])) if specs else []
+    place = {c: j for j, c in enumerate(used)}
+
+    def one(spec):
+        if len(spec) == 2 and spec[0] == "not":
+            return ("not", one(spec[1]))
+        c, rest = spec[0], list(spec[1:])
+        if len(rest) == 2 and isinstance(rest[1], datetime.datetime):
+            if kinds.get(c, ("", ""))[0] != "timestamp":
+                raise ValueError(f"a datetime operand needs its column cast to a timestamp: {spec!r}")
+            rest[1] = datetime_units(rest[1], kinds[c][1])
+        return (place[c],) + tuple(rest)
+
+    out = torch.zeros((max(len(used), 1), max(rows, 1), 2), dtype=torch.int64, device=d_fields.device)
+    for c in used:
+        if c in kinds and rows:
+            kind, unit = kinds[c]
+            out[place[c], :rows] = _cast(window, d_fields[c], d_rows_select, rows, kind, unit, kind == "number", what)[0]
+        elif rows:
+            out[place[c], :rows] = d_fields[c, :rows]
+    return [one(s) for s in specs], out
+
+
 _TAGS = '{["ldtfn'  # the value tags of an msj_field
 
 
@@ -344,6 +421,19 @@ class ListColumn:
         bool[n_elements])."""
         return number_column(self.fields, dtype)
 
+    def timestamps(self, unit="ns"):
+        """The elements that are RFC 3339 strings as int64 counts of `unit` since 1970-01-01T00:00:00Z ON THE DEVICE
+        (``msj_cast_strings_device`` over the element records), see ``Window.timestamps``: (values int64[n_elements], valid
+        bool[n_elements])."""
+        return _cast_numbers(self.window, self.fields, self.d_select, self.n_elements, "timestamp", unit, False, torch.int64,
+                             "the timestamps of the elements")
+
+    def parsed_numbers(self, dtype=torch.float64, keep_numbers=True):
+        """The elements that are numbers written as strings, see ``Window.parsed_numbers``: (values dtype[n_elements], valid
+        bool[n_elements])."""
+        return _cast_numbers(self.window, self.fields, self.d_select, self.n_elements, "number", "ns", keep_numbers, dtype,
+                             "the quoted numbers of the elements")
+
     def strings(self, bytes_capacity=None):
         """The elements that are strings as a column on the device (``msj_string_column_device`` over the element records):
         (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements])."""
@@ -397,13 +487,18 @@ class ListColumn:
         fields, d_esel = _take(w, kept, d_kept_select, kept.shape[0], self.fields, self.d_select, what)
         return kept, d_kept_select, ListColumn(w, d_off, fields[0], self.valid, d_esel, self.parent)
 
-    def where(self, specs, any=False):
+    def where(self, specs, any=False, cast=None):
         """The elements that pass predicates -- ``tags[*] == "red"``, ``scores[*] > 0.5`` -- ON THE DEVICE
         (``msj_filter_rows_device`` with the list offsets re-based, ``msj_take_rows_device``) -> a ``ListColumn`` with this
         column's rows and validity, new offsets, and the records of the kept elements in their order.  specs: as for
-        ``Stage1Device.compile_predicates``, the elements themselves being column 0."""
-        specs = _column_specs(specs, lambda c: range(1)[c])
-        return self._kept_elements(specs, any, self.fields, self.d_select, "the elements")[2]
+        ``Stage1Device.compile_predicates``, the elements themselves being column 0.  cast: ``{0: ("timestamp", "ms")}`` or
+        ``{0: "number"}``, see ``Window.where``; the records kept are the originals."""
+        index = lambda c: range(1)[c]
+        specs = _column_specs(specs, index)
+        d_fields = self.fields
+        if cast:
+            specs, d_fields = _cast_for_filter(self.window, specs, cast, index, self.fields, self.d_select, self.n_elements, "the elements")
+        return self._kept_elements(specs, any, d_fields, self.d_select, "the elements")[2]
 
     def elements(self, elements_capacity=None):
         """The arrays among this column's elements as a list column of their own -- a list of lists -- ON THE DEVICE
@@ -444,6 +539,20 @@ class ElementFields:
         """The numbers of one path as ``number_column`` gives them: (values dtype[n_elements], valid bool[n_elements])."""
         return number_column(self.fields[self.paths.index(path_or_index)], dtype)
 
+    def timestamps(self, path_or_index, unit="ns"):
+        """The RFC 3339 strings of one path -- ``items[*].at`` -- as int64 counts of `unit` since 1970-01-01T00:00:00Z ON THE
+        DEVICE, see ``Window.timestamps``: (values int64[n_elements], valid bool[n_elements])."""
+        p = self.paths.index(path_or_index)
+        return _cast_numbers(self.list_column.window, self.fields[p], self.d_select, self.n_elements, "timestamp", unit, False, torch.int64,
+                             f"the timestamps of path {p} of the elements")
+
+    def parsed_numbers(self, path_or_index, dtype=torch.float64, keep_numbers=True):
+        """The numbers written as strings of one path -- ``items[*].price`` -- see ``Window.parsed_numbers``: (values
+        dtype[n_elements], valid bool[n_elements])."""
+        p = self.paths.index(path_or_index)
+        return _cast_numbers(self.list_column.window, self.fields[p], self.d_select, self.n_elements, "number", "ns", keep_numbers, dtype,
+                             f"the quoted numbers of path {p} of the elements")
+
     def strings(self, path_or_index, bytes_capacity=None):
         """The strings of one path as a column on the device (``msj_string_column_device`` over the path's records):
         (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements])."""
@@ -465,16 +574,20 @@ class ElementFields:
         return _raw_column(self.list_column.window, self.fields[p], self.d_select, self.n_elements, compact, bytes_capacity,
                            f"the text of path {p} of the elements")
 
-    def where(self, specs, any=False):
+    def where(self, specs, any=False, cast=None):
         """The elements whose fields pass predicates -- ``items[*].qty > 1`` -- ON THE DEVICE (``msj_filter_rows_device`` with
         the list offsets re-based, ``msj_take_rows_device``) -> ``ElementFields`` over the kept elements, whose ``list_column``
         is a new ``ListColumn`` with the parent's rows and validity, the re-based offsets and the element records taken with
         the same vector: ``items[*]`` stays a list column.  specs: as for ``Stage1Device.compile_predicates``, the columns
-        named by pointer or index."""
+        named by pointer or index.  cast: ``{"/at": ("timestamp", "ms"), "/price": "number"}``, see ``Window.where``; the
+        records kept are the originals."""
         col, w = self.list_column, self.list_column.window
         specs = _column_specs(specs, self.paths.index)
         what = "the fields of the elements"
-        kept, d_kept_select, column = col._kept_elements(specs, any, self.fields, self.d_select, what)
+        d_fields = self.fields
+        if cast:
+            specs, d_fields = _cast_for_filter(w, specs, cast, self.paths.index, self.fields, self.d_select, self.n_elements, what)
+        kept, d_kept_select, column = col._kept_elements(specs, any, d_fields, self.d_select, what)
         fields, d_fsel = _take(w, kept, d_kept_select, kept.shape[0], self.fields, self.d_select, what)
         return ElementFields(column, self.paths, fields, d_fsel)
 
@@ -539,6 +652,20 @@ class RowSelection:
     def number_column(self, path_or_index, dtype=torch.float64):
         """The numbers of one path as ``Window.number_column`` gives them: (values dtype[n_rows], valid bool[n_rows])."""
         return number_column(self.fields[self.paths.index(path_or_index)], dtype)
+
+    def timestamps(self, path_or_index, unit="ns"):
+        """The RFC 3339 strings of one path as int64 counts of `unit`, see ``Window.timestamps``: (values int64[n_rows], valid
+        bool[n_rows])."""
+        p = self.paths.index(path_or_index)
+        return _cast_numbers(self.window, self.fields[p], self.d_select, self.n_rows, "timestamp", unit, False, torch.int64,
+                             f"the timestamps of path {p} of the chosen rows")
+
+    def parsed_numbers(self, path_or_index, dtype=torch.float64, keep_numbers=True):
+        """The numbers written as strings of one path, see ``Window.parsed_numbers``: (values dtype[n_rows], valid
+        bool[n_rows])."""
+        p = self.paths.index(path_or_index)
+        return _cast_numbers(self.window, self.fields[p], self.d_select, self.n_rows, "number", "ns", keep_numbers, dtype,
+                             f"the quoted numbers of path {p} of the chosen rows")
 
     def strings(self, path_or_index, bytes_capacity=None):
         """The strings of one path as a column on the device, see ``Window.strings``: (offsets int64[n_rows + 1], bytes
@@ -703,16 +830,50 @@ class Window:
         p = self.paths.index(path_or_index)
         return _object_entries(self, self.d_fields[p], self.d_select, self.n_documents, entries_capacity, None, f"the objects of path {p}")
 
-    def where(self, specs, any=False):
+    def cast(self, path_or_index, kind, unit="ns", keep_numbers=False):
+        """One path's strings cast to numbers ON THE DEVICE (``msj_cast_strings_device``) -> (records int64[D, 2], the
+        uint8[48] ``msj_select_documents_result`` that goes with them), for callers who chain further: ``filter_rows``,
+        ``take_rows`` and ``number_column`` take them as they take a select call's records.  kind: "timestamp" (RFC 3339; the
+        int64 counts `unit` since 1970-01-01T00:00:00Z) or "number" (the string, whole, is one JSON number).  A string that is
+        neither becomes code 9, a value that is no string code 17 -- or itself, when it is a number and keep_numbers is set."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        p = self.paths.index(path_or_index)
+        return _cast(self, self.d_fields[p], self.d_select, self.n_documents, kind, unit, keep_numbers, f"path {p}")
+
+    def timestamps(self, path_or_index, unit="ns"):
+        """The RFC 3339 strings of one path -- "ts":"2024-05-01T12:34:56.789Z" -- as a column ON THE DEVICE: (values int64[D],
+        valid bool[D]), the count of `unit` ("s" "ms" "us" "ns") since 1970-01-01T00:00:00Z, offsets applied, a fraction cut
+        to the unit.  Not valid, value 0: a string that is no timestamp (or, in "ns", one outside 1677-09-21 .. 2262-04-11),
+        a value that is no string, a missing key, a document with a verdict code.  ``cast`` and ``number_column``; only the
+        call's 48-byte result comes to the host."""
+        records, _ = self.cast(path_or_index, "timestamp", unit)
+        return number_column(records, torch.int64)
+
+    def parsed_numbers(self, path_or_index, dtype=torch.float64, keep_numbers=True):
+        """The numbers of one path that are written as strings -- "price":"12.50", "id":"9007199254740993" -- as a column ON
+        THE DEVICE: (values dtype[D], valid bool[D]) as ``number_column`` gives them, over the cast records: an integer stays
+        an exact int64.  keep_numbers: a value that already is a number counts as well."""
+        records, _ = self.cast(path_or_index, "number", keep_numbers=keep_numbers)
+        return number_column(records, dtype)
+
+    def where(self, specs, any=False, cast=None):
         """The documents that pass predicates on their selected fields ON THE DEVICE (``msj_filter_rows_device``,
         ``msj_take_rows_device``) -> ``RowSelection``: ``win.where([("/status", "==", "error"), ("/latency_ms", ">", 250)])``.
         specs: as for ``Stage1Device.compile_predicates`` with the columns named by pointer or index; a string compare is
         on the unescaped value, a number compare exact between int64 and double; ("not", spec) also passes a document
-        without the value.  any=True: one predicate is enough.  Only the call's 48-byte result comes to the host."""
+        without the value.  any=True: one predicate is enough.  Only the call's 48-byte result comes to the host.
+        cast: ``{"/ts": ("timestamp", "ms"), "/price": "number"}`` makes the predicates see those columns cast
+        (``msj_cast_strings_device``), so that ``[("/ts", ">=", t0), ("/ts", "<", t1)]`` is two exact int64 compares; a
+        ``datetime.datetime`` operand -- aware, or naive, which means UTC -- becomes the column's unit by integer arithmetic
+        (``datetime_units``).  The records the selection carries stay the originals."""
         if self.d_fields is None:
             raise ValueError("no fields: the stream was not created with select=[...]")
         specs = _column_specs(specs, self.paths.index)
-        keep, kept, d_kept_select, _ = _filter(self, specs, any, self.d_fields, self.d_select, self.n_documents, "the documents")
+        d_fields = self.d_fields
+        if cast:
+            specs, d_fields = _cast_for_filter(self, specs, cast, self.paths.index, self.d_fields, self.d_select, self.n_documents, "the documents")
+        keep, kept, d_kept_select, _ = _filter(self, specs, any, d_fields, self.d_select, self.n_documents, "the documents")
         fields, d_fsel = _take(self, kept, d_kept_select, kept.shape[0], self.d_fields, self.d_select, "the documents")
         return RowSelection(self, keep, kept, fields, d_fsel)
 
