@@ -174,10 +174,10 @@ def dictionary_of(t, col, rows, D):
 class Expected:
     """One window through the whole chain on the host.  calls: {call: [Out]} in the order of the chain."""
 
-    def __init__(self, name):
+    def __init__(self, name, lines=None):
         t = twins()
         self.name = name
-        self.data, self.lines = corpus()[name]
+        self.data, self.lines = corpus()[name] if lines is None else (tdk.join(lines, b"\n"), list(lines))
         data, self.length = self.data, len(self.data)
         w = self.w = tdm.WindowArrays(t.oracle, t.nm, data, is_final=False)
         self.n, self.D, self.ncap = w.n, w.D, int(w.records.size)
@@ -246,6 +246,12 @@ class Expected:
         """The bounds of tests/test_dictionary.py: same"""
         res = (self.dict_strings if call == "dictionary_strings" else self.dict_raw).res
         return (longest == 0) == (res.max_probe == 0) and longest <= max(tdc.MIN_SLOTS, 4 * int(res.n_rows))
+
+
+    @classmethod
+    def from_lines(cls, name, lines):
+        """A window of the caller's own lines (tests/stale_tails.py) through the same chain"""
+        return cls(name, lines)
 
 
 @functools.lru_cache(maxsize=None)

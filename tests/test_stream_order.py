@@ -152,12 +152,14 @@ class Tensors:
         return self.i64(call, name).view(-1, width)
 
 
-def chain(c, d_buf, t):
+def chain(c, d_buf, t, refill=True):
     """The whole chain over the window in d_buf into the tensors t: nothing is read back, nothing is sized from a first
-    call.  A generator that stops behind every call (its name), so that two chains can be enqueued in turns."""
+    call.  A generator that stops behind every call (its name), so that two chains can be enqueued in turns.  refill False:
+    the arrays keep what they hold (tests/test_stale_tails.py puts a larger window's leftovers there)."""
     dev, x = c.dev, t.x
     n, L, rows, erows, ncap = x.n, x.length, x.rows, x.erows, x.ncap
-    t.refill()
+    if refill:
+        t.refill()
     yield "fill"
     d_idx, d_carry = t.i32("shard", "idx"), t.u8("shard", "carry")
     dev.shard(d_buf, L, d_idx, t.zero, d_carry, is_final=False)
