@@ -1669,6 +1669,92 @@ uint64_t msj_cast_strings_workspace_bytes(uint64_t capacity);
 int32_t msj_debug_set_cast_fetch(msj_ctx *ctx, uint32_t fetch);
 
 /*
+ * ---- count, sum, min, max per group (DERIVED) ---------------------------------------------------------
+ * msj_aggregate_device answers "how many lines, what total, smallest and largest /latency_ms per /status" on the device:
+ * one 48-byte msj_aggregate per (column, group) over msj_field records of type 'l' / 'd' -- a path of a select call, cast
+ * strings, taken rows, list elements -- grouped by any int32 codes, msj_dictionary_device's d_codes first of all.  EXACT and
+ * REPRODUCIBLE: an int64 is never cast to a double, and every output is a pure function of the input, bit for bit from run
+ * to run and under any permutation of the rows (codes permuted with them): the kernels use integer atomics alone.
+ *
+ * Column c is d_fields + c * stride, as msj_filter_rows_device takes them; `stride` is also the room of a column.
+ * R = d_rows_select->n_documents and G = d_n_groups ? *d_n_groups : n_groups are read on the device (d_n_groups =
+ * &dictionary_result->n_distinct groups by a dictionary without a host wait).  d_groups[c * groups_capacity + g] is the
+ * record of column c and group g < G; nothing at or past G is written.
+ *   Grouping      row k < R belongs to group d_codes[k] when that lies in [0, G); otherwise it is counted in n_ungrouped and
+ *                 in no group.  d_codes == NULL: every row is group 0.  d_codes holds `stride` entries
+ *   Number value  a record is a number value iff its code == 0, its type is 'l' or 'd', MSJ_FIELD_NO_BITS is not set and,
+ *                 for 'd', its bits are finite.  Any other record of a grouped row adds to its group's n_rows only; one
+ *                 with code == 0 and type 'l' / 'd' but no usable bits (MSJ_FIELD_NO_BITS; a NaN or an infinity, which no
+ *                 number call writes) is counted in n_skipped
+ *   min / max     the values compared AS REAL NUMBERS, an int64 against a double exactly (the compare of
+ *                 MSJ_PRED_NUM_*): 9007199254740993 lies above 9007199254740992.0.  Between equal reals the 'l' record wins,
+ *                 for the minimum and for the maximum; among doubles -0.0 lies below +0.0.  min_type / max_type say what
+ *                 min_bits / max_bits hold
+ *   sum, 'l'      every value of the group is an 'l' and the exact integer sum fits an int64: sum_bits is that sum.  The
+ *                 running sum is never clipped: INT64_MAX, 1, -1 sum to the exact 'l' INT64_MAX
+ *   sum, 'd'      otherwise.  Let E be the largest floor(log2|v|) over the group's non-zero values.  Every value becomes
+ *                 the integer t = trunc(v * 2^(95 - E)), exact for every value whose lowest set bit lies at or above
+ *                 2^(E - 95): every int64 while E <= 95, every double within 2^42 of the largest.  S = the sum of the t,
+ *                 exact (R < 2^31: |S| < 2^127).  sum_bits is S * 2^(E - 95) rounded ONCE to the nearest binary64, ties to
+ *                 even, subnormals included; beyond DBL_MAX it is +-infinity with MSJ_AGG_INFINITE.  A group of 'l' alone
+ *                 that left the int path sets MSJ_AGG_INT_OVERFLOW (its sum is the exact integer sum, rounded once).  No
+ *                 non-zero value, or S == 0: +0.0.  The error is below R * 2^(E - 95), that of a double sum up to
+ *                 R * 2^(E - 52), and it is the same for every order of the rows: 2^53, 1.0, 1.0 gives 2^53 + 2.  What
+ *                 lies more than 95 binary places below the group's largest value is cut: 1e308, -1e308, 1.0 gives +0.0
+ *                 (the double sum in that order 1.0, in another 0.0)
+ * A group without a value: n_rows, and every other member 0.  sum_type == 0 says so.
+ * d_result: code; flags, the OR of every record's; n_rows = R; n_groups = G; n_ungrouped; n_values and n_skipped over all
+ * columns (grouped rows only: n_values is the sum of the records').  d_rows_select->code != 0: a zero result with that code,
+ * nothing else written.  R > stride or R >= 2^31, or G > groups_capacity: MSJ_CAPACITY with n_rows = R and n_groups = G,
+ * nothing else written.  R == 0 or G == 0: the same definition -- zeroed records for g < G, n_ungrouped = R.
+ * Merging two windows' records: n_rows and n_values add, min and max merge by the rule above, an 'l' sum adds to an 'l' sum
+ * while it fits; two 'd' sums do NOT merge exactly (each was rounded): aggregate the windows' rows in one call for that.
+ * Arguments, checked in this order: NULL ctx / d_result / d_rows_select; NULL d_fields with stride > 0, NULL d_groups with
+ * groups_capacity > 0; n_columns outside 1..16: MSJ_ERR_BAD_ARGUMENT.  A stride or groups_capacity of 2^40 or more:
+ * MSJ_CAPACITY.  Then d_result == d_rows_select, and alignment -- d_fields, d_groups 16-byte;
+ * d_codes 4-byte; d_n_groups, the result and the select result 8-byte: MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of
+ * them.  Asynchronous on `stream`, no host round trip, workspace in the context (96 bytes per (column, group) of
+ * groups_capacity).  Safe on ANY arrays: a record is read only at k < R <= stride, a code only there, nothing at or past G
+ * or groups_capacity is written.
+ * Two paths, chosen on the device from G: up to the context's limit (256 groups) a block sums its rows in LDS and adds what
+ * it touched to the group's words once; above it every lane adds to the group's words directly.  Both give the same bytes.
+ * msj_debug_set_aggregate_limits moves the limit (0: never LDS; at most 256) so that tests run both on small inputs.
+ * Out of scope: mean and variance (the caller divides); grouping by a numeric key or a time bucket; more than one key;
+ * argmin / argmax rows; sums across windows (above); sorting the groups.
+ */
+#define MSJ_AGG_INT_OVERFLOW 1u   /* msj_aggregate.flags: every value an 'l', the exact sum outside int64: sum_type 'd' */
+#define MSJ_AGG_INFINITE 2u       /* the sum lies beyond DBL_MAX: sum_bits is +-infinity */
+typedef struct msj_aggregate {      /* 48 bytes, 16-byte aligned, one per (column, group) */
+    uint64_t n_rows;    /* rows of the group */
+    uint64_t n_values;  /* of them, rows whose record is a number value */
+    uint64_t sum_bits;  /* 'l': the int64; 'd': the binary64 pattern */
+    uint64_t min_bits, max_bits;
+    uint8_t  sum_type, min_type, max_type;   /* 'l' / 'd'; 0 when n_values == 0 */
+    uint8_t  flags;     /* MSJ_AGG_INT_OVERFLOW, MSJ_AGG_INFINITE */
+    uint32_t reserved;
+} msj_aggregate;
+typedef struct msj_aggregate_result {   /* 48 bytes */
+    int32_t  code;         /* 0; MSJ_CAPACITY; or the code of d_rows_select */
+    uint32_t flags;        /* the OR of every written record's flags */
+    uint64_t n_rows;       /* R */
+    uint64_t n_groups;     /* G */
+    uint64_t n_ungrouped;  /* rows whose code lies outside [0, G) */
+    uint64_t n_values;     /* number values, over all columns */
+    uint64_t n_skipped;    /* 'l' / 'd' records without usable bits, over all columns */
+} msj_aggregate_result;
+int32_t msj_aggregate_device(msj_ctx *ctx,
+        const msj_field *d_fields, uint64_t stride, uint32_t n_columns,
+        const msj_select_documents_result *d_rows_select,
+        const int32_t *d_codes,
+        uint64_t n_groups, const uint64_t *d_n_groups,
+        msj_aggregate *d_groups, uint64_t groups_capacity,
+        msj_aggregate_result *d_result, void *stream);
+/* Device workspace of one msj_aggregate_device call (the context keeps it): the counters and 96 bytes per (column, group). */
+uint64_t msj_aggregate_workspace_bytes(uint64_t capacity, uint64_t groups_capacity, uint32_t n_columns);
+/* TEST AID: the most groups the LDS path takes (0: none; more than 256: MSJ_ERR_BAD_ARGUMENT).  Both paths write the same bytes. */
+int32_t msj_debug_set_aggregate_limits(msj_ctx *ctx, uint32_t lds_groups);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

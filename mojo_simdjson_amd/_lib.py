@@ -186,6 +186,25 @@ class MsjCastStringsResult(ctypes.Structure):
                 ("n_syntax", ctypes.c_uint64), ("n_range", ctypes.c_uint64), ("n_other", ctypes.c_uint64)]
 
 
+class MsjAggregate(ctypes.Structure):
+    """``msj_aggregate`` (include/msj_stage1.h): the record of one (column, group)."""
+
+    _fields_ = [("n_rows", ctypes.c_uint64), ("n_values", ctypes.c_uint64), ("sum_bits", ctypes.c_uint64), ("min_bits", ctypes.c_uint64),
+                ("max_bits", ctypes.c_uint64), ("sum_type", ctypes.c_uint8), ("min_type", ctypes.c_uint8), ("max_type", ctypes.c_uint8),
+                ("flags", ctypes.c_uint8), ("reserved", ctypes.c_uint32)]
+
+
+class MsjAggregateResult(ctypes.Structure):
+    """``msj_aggregate_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_groups", ctypes.c_uint64),
+                ("n_ungrouped", ctypes.c_uint64), ("n_values", ctypes.c_uint64), ("n_skipped", ctypes.c_uint64)]
+
+
+# msj_aggregate.flags; the most groups msj_debug_set_aggregate_limits takes
+AGG_INT_OVERFLOW, AGG_INFINITE = 1, 2
+AGG_MAX_LDS_GROUPS = 256
+
 # msj_cast_strings_device: kind, unit, flags; msj_debug_set_cast_fetch
 CAST_TIMESTAMP, CAST_NUMBER = 1, 2
 CAST_KINDS = {"timestamp": CAST_TIMESTAMP, "number": CAST_NUMBER}
@@ -427,6 +446,13 @@ def load():
     lib.msj_cast_strings_workspace_bytes.argtypes = [ctypes.c_uint64]
     lib.msj_debug_set_cast_fetch.restype = ctypes.c_int32
     lib.msj_debug_set_cast_fetch.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    lib.msj_aggregate_device.restype = ctypes.c_int32
+    lib.msj_aggregate_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_aggregate_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_aggregate_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
+    lib.msj_debug_set_aggregate_limits.restype = ctypes.c_int32
+    lib.msj_debug_set_aggregate_limits.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

@@ -120,6 +120,8 @@ struct msj_ctx {
     DeviceBuffer take_ws;         // msj_take_rows_device: the counters
     DeviceBuffer cast_ws;         // msj_cast_strings_device: the counters, the list of the rows the lane path leaves over
     uint32_t cast_fetch = 0;      // msj_debug_set_cast_fetch: MSJ_CAST_FETCH_*
+    DeviceBuffer agg_ws;          // msj_aggregate_device: the counters, the accumulators of every (column, group)
+    uint32_t agg_lds_groups = kAggregateMaxLdsGroups;  // msj_debug_set_aggregate_limits: the most groups the LDS path takes
 };
 
 // ---- api.cpp ----

@@ -1,7 +1,7 @@
 // launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 /
 // f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
 // validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
-// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, filter_rows_kernel.hip.  Every launcher and every internal workspace size is declared
+// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip.  Every launcher and every internal workspace size is declared
 // here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
 // compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
 // (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.
@@ -194,3 +194,12 @@ extern "C" int msj_launch_take_rows(const uint32_t *d_take, const msj_select_doc
 extern "C" int msj_launch_cast_strings(const uint8_t *d_buf, uint64_t len, const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
                                        uint32_t kind, uint32_t unit, uint32_t flags, uint32_t fetch, msj_field *d_out, uint64_t capacity,
                                        msj_cast_strings_result *d_result, msj_select_documents_result *d_out_select, void *d_ws, void *stream);
+
+// ---- aggregate_kernel.hip ----
+// d_fields: column c at c * stride, `stride` also the room of a column and of d_codes (null: every row is group 0);
+// d_n_groups: G on the device, or null for `n_groups`; d_groups: column c's records at c * groups_capacity; lds_groups: the
+// most groups the LDS path takes (at most kAggregateMaxLdsGroups)
+constexpr uint32_t kAggregateMaxLdsGroups = 256;
+extern "C" int msj_launch_aggregate(const msj_field *d_fields, uint64_t stride, uint32_t n_columns, const msj_select_documents_result *d_rows_select,
+                                    const int32_t *d_codes, uint64_t n_groups, const uint64_t *d_n_groups, msj_aggregate *d_groups,
+                                    uint64_t groups_capacity, uint32_t lds_groups, msj_aggregate_result *d_result, void *d_ws, void *stream);

@@ -2,11 +2,12 @@
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
 // window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
 // elements, the arrays inside list rows, an object's members as a map column, a selected value's JSON text as a column, a byte column as codes plus distinct
-// values, rows by predicate.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// values, rows by predicate, strings cast to numbers, count / sum / min / max per group.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
 // see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
 #include <new>
 
 #include "ctx.h"
+#include "aggregate_math.h"
 #include "cast_strings_math.h"
 #include "filter_rows_math.h"
 #include "select_math.h"
@@ -632,6 +633,28 @@ int32_t msj_cast_strings_device(msj_ctx *ctx, const uint8_t *d_buf, uint64_t len
 int32_t msj_debug_set_cast_fetch(msj_ctx *ctx, uint32_t fetch) {
     if (!ctx || fetch > MSJ_CAST_FETCH_BYTES) return MSJ_ERR_BAD_ARGUMENT;
     ctx->cast_fetch = fetch;
+    return MSJ_SUCCESS;
+}
+
+int32_t msj_aggregate_device(msj_ctx *ctx, const msj_field *d_fields, uint64_t stride, uint32_t n_columns,
+                             const msj_select_documents_result *d_rows_select, const int32_t *d_codes, uint64_t n_groups,
+                             const uint64_t *d_n_groups, msj_aggregate *d_groups, uint64_t groups_capacity, msj_aggregate_result *d_result,
+                             void *stream) {
+    if (!ctx || !d_result || !d_rows_select) return MSJ_ERR_BAD_ARGUMENT;
+    if ((stride > 0 && !d_fields) || (groups_capacity > 0 && !d_groups)) return MSJ_ERR_BAD_ARGUMENT;
+    if (n_columns == 0 || n_columns > msj::agg::kMaxColumns) return MSJ_ERR_BAD_ARGUMENT;
+    if (stride >= (1ull << 40) || groups_capacity >= (1ull << 40)) return MSJ_CAPACITY;  // (the workspace's size below: no overflow)
+    if ((const void *)d_result == (const void *)d_rows_select) return MSJ_ERR_BAD_ARGUMENT;
+    if (!all_aligned(16, d_fields, d_groups) || !aligned(d_codes, 4) || !all_aligned(8, d_n_groups, d_rows_select, d_result))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->agg_ws, msj_aggregate_workspace_bytes(stride, groups_capacity, n_columns));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_aggregate(d_fields, stride, n_columns, d_rows_select, d_codes, n_groups, d_n_groups, d_groups, groups_capacity,
+                                         ctx->agg_lds_groups, d_result, ctx->agg_ws.p, stream));
+}
+int32_t msj_debug_set_aggregate_limits(msj_ctx *ctx, uint32_t lds_groups) {
+    if (!ctx || lds_groups > kAggregateMaxLdsGroups) return MSJ_ERR_BAD_ARGUMENT;
+    ctx->agg_lds_groups = lds_groups;
     return MSJ_SUCCESS;
 }
 

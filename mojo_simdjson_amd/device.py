@@ -843,6 +843,42 @@ class Stage1Device:
         res = _lib.MsjCastStringsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
         return res, d_out, d_out_select
 
+    def aggregate(self, d_fields, d_rows_select, d_codes=None, n_groups=1, d_n_groups=None, d_groups=None, groups_capacity=None,
+                  d_result=None, sync=True):
+        """Count, sum, min and max per group (``msj_aggregate_device``), exact and bit for bit the same from run to run, all
+        on the device.  d_fields: int64 of shape (n_columns, rows, 2) or (rows, 2), any ``msj_field`` records -- paths of
+        ``select_documents`` or ``select_elements``, cast strings, taken rows; d_rows_select: the device
+        ``msj_select_documents_result`` that counts the rows, read on the device.  d_codes: int32 tensor, a group per row --
+        ``dictionary``'s d_codes, or any codes; a row whose code lies outside [0, G) is in no group; None: every row is
+        group 0.  G is n_groups, or with d_n_groups an int64 device word read on the device (the ``n_distinct`` of a
+        dictionary's result tensor: ``d_res[24:32].view(torch.int64)``).  d_groups: uint8 tensor of n_columns *
+        groups_capacity * 48 bytes that receives the ``msj_aggregate`` records, column c's at c * groups_capacity (default: a
+        new one; groups_capacity: default n_groups).  Returns (``MsjAggregateResult``, d_groups) -- blocking for the 48-byte
+        result; with sync=False the device tensor that holds it, nothing waited for."""
+        n_columns, rows, stride = self._record_columns(d_fields, "the records")
+        if d_codes is not None and (d_codes.dtype != torch.int32 or d_codes.stride(-1) != 1 or d_codes.numel() < stride):
+            raise ValueError("d_codes is a contiguous int32 tensor with an entry per row of d_fields")
+        if groups_capacity is None:
+            groups_capacity = int(n_groups) if d_groups is None else d_groups.numel() // (48 * n_columns)
+        groups_capacity = int(groups_capacity)
+        if d_groups is None:
+            d_groups = torch.empty(max(n_columns * groups_capacity, 1) * 48, dtype=torch.uint8, device=self.device)
+        if d_groups.dtype != torch.uint8 or d_groups.numel() < n_columns * groups_capacity * 48:
+            raise ValueError("d_groups is a uint8 tensor of n_columns * groups_capacity * 48 bytes")
+        d_result = self._result(d_result)
+        rc = self.lib.msj_aggregate_device(self.ctx, _ptr(d_fields), stride, n_columns, _ptr(d_rows_select), _opt(d_codes), int(n_groups),
+                                           _opt(d_n_groups), _ptr(d_groups), groups_capacity, _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_aggregate_device failed: {rc}")
+        res = _lib.MsjAggregateResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_groups
+
+    def set_aggregate_limits(self, lds_groups=_lib.AGG_MAX_LDS_GROUPS):
+        """Test hook: the most groups ``aggregate`` sums in LDS (0: never; default and most: 256).  The records do not
+        change."""
+        if self.lib.msj_debug_set_aggregate_limits(self.ctx, int(lds_groups)) != 0:
+            raise ValueError(f"lds_groups lies in 0..{_lib.AGG_MAX_LDS_GROUPS}: {lds_groups!r}")
+
     def array_column(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_fields, p, d_select_result,
                      d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_offsets=None, d_valid=None, d_elements=None,
                      capacity=None, elements_capacity=None, elements=True, d_result=None, d_elements_select=None, sync=True):

@@ -328,6 +328,84 @@ def _dictionary(dev, column, what):
     return DictionaryColumn(codes[:rows], d_off[:n + 1], d_bytes[:int(res.dict_bytes)], d_first[:n], valid)
 
 
+class GroupStats:
+    """Count, sum, min and max per group ON THE DEVICE (``msj_aggregate_device``; ``Window.stats``, ``RowSelection.stats``,
+    ``ElementFields.stats``, ``ListColumn.stats``).  keys: the ``DictionaryColumn`` of the grouping path, whose value g names
+    group g (None: one group, or a group per row of a list column); pointers: the aggregated columns' names; records
+    uint8[n_columns, n_groups, 48], the ``msj_aggregate`` records as the call wrote them, and as views of them: n_rows
+    int64[n_groups]; n_values, sums, mins, maxs int64[n_columns, n_groups] -- sums, mins and maxs hold an int64 where
+    sum_types / min_types / max_types (uint8, the same shape) say ord("l"), the pattern of a double where they say ord("d"),
+    nothing where they say 0; flags uint8[n_columns, n_groups]: ``_lib.AGG_INT_OVERFLOW``, ``_lib.AGG_INFINITE``.  n_ungrouped,
+    n_skipped: the result's counts.  Every bit is a pure function of the rows: the same from run to run, for every order."""
+
+    def __init__(self, keys, pointers, records, result):
+        self.keys, self.pointers, self.records = keys, list(pointers), records
+        words = records.view(torch.int64).view(records.shape[0], records.shape[1], 6)
+        self.n_rows, self.n_values = words[0, :, 0], words[:, :, 1]
+        self.sums, self.mins, self.maxs = words[:, :, 2], words[:, :, 3], words[:, :, 4]
+        self.sum_types, self.min_types, self.max_types, self.flags = (records[:, :, 40 + i] for i in range(4))
+        self.n_ungrouped, self.n_skipped = int(result.n_ungrouped), int(result.n_skipped)
+
+    @property
+    def n_groups(self):
+        return self.records.shape[1]
+
+    def to_python(self):
+        """A dict per group: "key" (the group's value; absent without keys) and per aggregated column its pointer with
+        {"n_rows", "n_values", "sum", "min", "max", "flags"} -- an 'l' as a Python ``int``, a 'd' as a ``float``, None for a
+        group without a number value.  The records and the dictionary come to the host."""
+        rec = self.records.cpu().numpy()
+        words = rec.view("<u8").reshape(rec.shape[0], rec.shape[1], 6)
+
+        def number(tag, bits):
+            bits = int(bits)
+            if tag == ord("l"):
+                return bits - (1 << 64) if bits >> 63 else bits
+            return struct.unpack("<d", struct.pack("<Q", bits))[0] if tag == ord("d") else None
+
+        keys = self.keys.values() if self.keys is not None else None
+        out = []
+        for g in range(rec.shape[1]):
+            row = {} if keys is None else {"key": keys[g]}
+            for c, pointer in enumerate(self.pointers):
+                w, tags = words[c, g], rec[c, g, 40:44]
+                row[pointer] = {"n_rows": int(w[0]), "n_values": int(w[1]), "sum": number(tags[0], w[2]), "min": number(tags[1], w[3]),
+                                "max": number(tags[2], w[4]), "flags": int(tags[3])}
+            out.append(row)
+        return out
+
+
+def _stats(window, d_fields, d_rows_select, rows, columns, pointers, cast, keys, d_codes, n_groups, what):
+    """``aggregate`` over the named columns of d_fields (int64[n_columns, rows, 2]), cast first where asked -> ``GroupStats``.
+    columns: their numbers in d_fields; cast: {column number: spec}; d_codes: int32[rows] or None; the 48-byte result comes to
+    the host."""
+    w = window
+    if not columns:
+        raise ValueError("stats of no column")
+    fields = torch.zeros((len(columns), max(rows, 1), 2), dtype=torch.int64, device=d_fields.device)
+    for j, c in enumerate(columns):
+        if not rows:
+            break
+        if c in cast:
+            kind, unit = _cast_spec(cast[c])
+            fields[j, :rows] = _cast(w, d_fields[c], d_rows_select, rows, kind, unit, kind == "number", what)[0]
+        else:
+            fields[j, :rows] = d_fields[c, :rows]
+    if d_codes is not None:
+        d_codes = d_codes.to(torch.int32).contiguous() if rows else torch.zeros(1, dtype=torch.int32, device=fields.device)
+    res, d_groups = w.dev.aggregate(fields, d_rows_select, d_codes, n_groups=n_groups, groups_capacity=max(n_groups, 1))
+    if res.code != 0 or res.n_rows != rows:
+        raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be aggregated")
+    records = d_groups[:len(columns) * max(n_groups, 1) * 48].view(len(columns), max(n_groups, 1), 48)[:, :n_groups]
+    return GroupStats(keys, pointers, records, res)
+
+
+def _rows_of_elements(offsets, n_elements):
+    """The row of every element of a list column, int32[n_elements], from its offsets (torch)"""
+    at = torch.arange(n_elements, dtype=torch.int64, device=offsets.device)
+    return torch.searchsorted(offsets[1:].contiguous(), at, right=True).to(torch.int32)
+
+
 class MapColumn:
     """Objects as a map column ON THE DEVICE (``Window.entries``, ``ListColumn.entries``, ``ElementFields.entries``): the
     members of objects whose keys are data.  offsets int64[rows + 1]; key_fields and value_fields int64[n_entries, 2], one
@@ -461,6 +539,16 @@ class ListColumn:
         host = w._host_arrays()
         return [[field_value(r, *host) for r in recs[off[k]:off[k + 1]]] if ok[k] else None for k in range(len(ok))]
 
+    def stats(self, per_row=False, cast=None):
+        """Count, sum, min and max of the elements that are numbers ON THE DEVICE (``msj_aggregate_device``) ->
+        ``GroupStats`` with one column, "": over all elements as one group, or with per_row=True a group per row of this
+        column -- ``sum(scores[*])`` per document -- the element's row number, computed from the offsets with torch, being
+        its code.  cast: "number", "timestamp" or ("timestamp", unit) for elements that are strings, see ``Window.where``."""
+        n, rows = self.n_elements, self.offsets.shape[0] - 1
+        d_codes = _rows_of_elements(self.offsets, n) if per_row else None
+        return _stats(self.window, self.fields.unsqueeze(0), self.d_select, n, [0], [""], {0: cast} if cast else {}, None, d_codes,
+                      rows if per_row else 1, "the elements")
+
     def select(self, pointers_or_paths):
         """Fields by path inside the elements -- ``items[*].sku`` -- ON THE DEVICE (``msj_select_elements_device``) ->
         ``ElementFields``: one ``msj_field`` per (path, element), each path a column aligned with this column's offsets.
@@ -574,6 +662,21 @@ class ElementFields:
         return _raw_column(self.list_column.window, self.fields[p], self.d_select, self.n_elements, compact, bytes_capacity,
                            f"the text of path {p} of the elements")
 
+    def stats(self, paths, by=None, cast=None, per_row=False):
+        """Count, sum, min and max of paths of the elements ON THE DEVICE (``msj_aggregate_device``) -> ``GroupStats``, see
+        ``Window.stats``.  by: a path whose strings group the elements; per_row=True instead: a group per row of the list
+        column -- ``sum(items[*].qty)`` per document -- the element's row number, computed from the offsets with torch,
+        being its code."""
+        col, w = self.list_column, self.list_column.window
+        if by is not None and per_row:
+            raise ValueError("by and per_row exclude each other")
+        columns = [self.paths.index(p) for p in paths]
+        keys = self.categories(by) if by is not None else None
+        d_codes = keys.codes if keys is not None else _rows_of_elements(col.offsets, self.n_elements) if per_row else None
+        n_groups = keys.n_distinct if keys is not None else col.offsets.shape[0] - 1 if per_row else 1
+        return _stats(w, self.fields, self.d_select, self.n_elements, columns, [self.paths.pointers[c] for c in columns],
+                      {self.paths.index(k): v for k, v in (cast or {}).items()}, keys, d_codes, n_groups, "the fields of the elements")
+
     def where(self, specs, any=False, cast=None):
         """The elements whose fields pass predicates -- ``items[*].qty > 1`` -- ON THE DEVICE (``msj_filter_rows_device`` with
         the list offsets re-based, ``msj_take_rows_device``) -> ``ElementFields`` over the kept elements, whose ``list_column``
@@ -684,6 +787,14 @@ class RowSelection:
         minified NDJSON lines."""
         p = self.paths.index(path_or_index)
         return _raw_column(self.window, self.fields[p], self.d_select, self.n_rows, compact, bytes_capacity, f"the text of path {p} of the chosen rows")
+
+    def stats(self, paths, by=None, cast=None):
+        """Count, sum, min and max of paths over the chosen rows, see ``Window.stats`` -> ``GroupStats``."""
+        columns = [self.paths.index(p) for p in paths]
+        keys = self.categories(by) if by is not None else None
+        return _stats(self.window, self.fields, self.d_select, self.n_rows, columns, [self.paths.pointers[c] for c in columns],
+                      {self.paths.index(k): v for k, v in (cast or {}).items()}, keys, keys.codes if keys is not None else None,
+                      keys.n_distinct if keys is not None else 1, "the chosen rows")
 
     def elements(self, path_or_index, elements_capacity=None):
         """The arrays of one path as a ``ListColumn`` with one row per chosen row (``msj_array_elements_device``: the rows are
@@ -876,6 +987,22 @@ class Window:
         keep, kept, d_kept_select, _ = _filter(self, specs, any, d_fields, self.d_select, self.n_documents, "the documents")
         fields, d_fsel = _take(self, kept, d_kept_select, kept.shape[0], self.d_fields, self.d_select, "the documents")
         return RowSelection(self, keep, kept, fields, d_fsel)
+
+    def stats(self, paths, by=None, cast=None):
+        """Count, sum, min and max of paths per group ON THE DEVICE (``msj_aggregate_device``) -> ``GroupStats``:
+        ``win.stats(["/latency_ms"], by="/status")`` is how many lines, what total, smallest and largest latency per status.
+        by: a path whose strings are dictionary-encoded first (``categories``): group g is the g-th distinct value, a row
+        without a string is in no group; None: the window is one group.  An int64 stays an int64 -- the sum of integers is
+        the exact integer while it fits -- and a sum with doubles is rounded once: the same bits from run to run and for every
+        order of the lines.  cast: ``{"/ts": ("timestamp", "ms"), "/price": "number"}`` as in ``where``, so that a timestamp
+        has a minimum and a maximum and a quoted number a sum.  The call's 48-byte result comes to the host."""
+        if self.d_fields is None:
+            raise ValueError("no fields: the stream was not created with select=[...]")
+        columns = [self.paths.index(p) for p in paths]
+        keys = self.categories(by) if by is not None else None
+        return _stats(self, self.d_fields, self.d_select, self.n_documents, columns, [self.paths.pointers[c] for c in columns],
+                      {self.paths.index(k): v for k, v in (cast or {}).items()}, keys, keys.codes if keys is not None else None,
+                      keys.n_distinct if keys is not None else 1, "the documents")
 
     def take(self, rows):
         """The documents with the given numbers ON THE DEVICE (``msj_take_rows_device``) -> ``RowSelection``.  rows: an int32
