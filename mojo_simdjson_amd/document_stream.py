@@ -85,15 +85,31 @@ def number_column(col, dtype=torch.float64):
     return torch.where(valid, values, torch.zeros_like(values)), valid
 
 
-def _grow_once(call, d_rows, rows, room, total, what):
+def _or_blank(t, rows):
+    """t, or where there is no row one blank row in its place: a call takes no empty array.  The rows are the last axis but
+    one of records -- [rows, 2], [n_columns, rows, 2] -- and the only axis of a vector."""
+    if rows:
+        return t
+    shape = list(t.shape)
+    shape[max(t.dim() - 2, 0)] = 1
+    return torch.zeros(shape, dtype=t.dtype, device=t.device)
+
+
+def _code(d_result):
+    """The code word of a result left on the device: the one read that waits for the call"""
+    return int(d_result[:4].view(torch.int32).item())
+
+
+# The helpers below take (the Window, records int64[rows, 2] or [n_columns, rows, 2], the device msj_select_documents_result
+# that counts them, rows, ...) and `what`: the records' name, which a message puts behind "window at {base}:".
+
+def _grow_once(window, call, d_rows, rows, room, total, what):
     """A column call over `rows` records whose output buffer starts from a guess of `room` items and, when the call says it
     was too small, is made as large as the call asks (the result field `total`) once.  call(d_rows, room, **outputs) is the
     ``Stage1Device`` method with everything else bound; outputs: d_offsets int64[rows + 1], d_valid uint8[rows] and the
-    capacity, made here; d_rows: the records, or the d_fields whose path holds them -- one blank record per path stands in for
-    none.  -> (result, what the call returned behind d_valid, offsets, valid bool[rows]); DocumentStreamError for a code"""
-    dvc = d_rows.device
-    if rows == 0:
-        d_rows = torch.zeros(d_rows.shape[:-2] + (1, 2), dtype=torch.int64, device=dvc)
+    capacity, made here; d_rows: the records, or the fields whose column holds them.
+    -> (result, what the call returned behind d_valid, offsets, valid bool[rows]); DocumentStreamError for a code"""
+    d_rows, dvc = _or_blank(d_rows, rows), d_rows.device
     d_off = torch.empty(rows + 1, dtype=torch.int64, device=dvc)
     d_valid = torch.empty(max(rows, 1), dtype=torch.uint8, device=dvc)
     for _ in range(2):
@@ -102,54 +118,53 @@ def _grow_once(call, d_rows, rows, room, total, what):
             break
         room = int(getattr(res, total))
     if res.code != 0:
-        raise DocumentStreamError(int(res.code), f"{what} could not be laid out")
+        raise DocumentStreamError(int(res.code), f"window at {window.base}: {what} could not be laid out")
     return res, out, d_off, d_valid[:rows].view(torch.bool)
 
 
-def _string_column(dev, d_window, length, d_fields, p, d_select, rows, bytes_capacity, what):
-    """``string_column`` over `rows` records of path p of d_fields, its byte buffer grown once (``_grow_once``)
+def _string_column(window, d_fields, d_select, rows, p, bytes_capacity, what):
+    """``string_column`` over `rows` records of column p of d_fields, its byte buffer grown once (``_grow_once``)
     -> (offsets int64[rows + 1], bytes uint8[total], valid bool[rows])"""
-    room = min(length, 32 * rows + 4096) if bytes_capacity is None else int(bytes_capacity)
+    w = window
+    room = min(w.length, 32 * rows + 4096) if bytes_capacity is None else int(bytes_capacity)
     res, (d_bytes,), d_off, valid = _grow_once(
-        lambda d_f, room, **out: dev.string_column(d_window, length, d_f, p, d_select, bytes_capacity=room, **out),
-        d_fields, rows, room, "total_bytes", what)
+        w, lambda d_f, room, **out: w.dev.string_column(w.d_window, w.length, d_f, p, d_select, bytes_capacity=room, **out),
+        d_fields, rows, room, "total_bytes", f"the strings of {what}")
     return d_off, d_bytes[:int(res.total_bytes)], valid
 
 
-def _raw_column(window, d_rows, d_rows_select, rows, compact, bytes_capacity, what):
+def _raw_column(window, d_rows, d_select, rows, compact, bytes_capacity, what):
     """``raw_column`` over `rows` records, its byte buffer grown once (``_grow_once``)
     -> (offsets int64[rows + 1], bytes uint8[total], valid bool[rows])"""
     w = window
     room = min(w.length, 64 * rows + 4096) if bytes_capacity is None else int(bytes_capacity)
     res, (d_bytes,), d_off, valid = _grow_once(
-        lambda d_r, room, **out: w.dev.raw_column(w.d_window, w.length, w.d_idx, w.n_tokens, w.d_type, w.d_match, w.d_end, w.d_flags, d_r,
-                                                  d_rows_select, bytes_capacity=room, compact=compact, **out),
-        d_rows, rows, room, "total_bytes", f"window at {w.base}: {what}")
+        w, lambda d_r, room, **out: w.dev.raw_column(w.d_window, w.length, w.d_idx, w.n_tokens, w.d_type, w.d_match, w.d_end, w.d_flags, d_r,
+                                                     d_select, bytes_capacity=room, compact=compact, **out),
+        d_rows, rows, room, "total_bytes", f"the text of {what}")
     return d_off, d_bytes[:int(res.total_bytes)], valid
 
 
-def _array_elements(window, d_rows, d_rows_select, rows, elements_capacity, parent, what):
-    """``array_elements`` over `rows` records, its element buffer grown once (``_grow_once``) -> ``ListColumn`` with `parent`"""
+def _array_elements(window, d_rows, d_select, rows, elements_capacity, parent, what, call=None):
+    """``array_elements`` over `rows` records -- or call(d_rows, **outputs), ``Window.elements``' call over the documents --
+    its element buffer grown once (``_grow_once``) -> ``ListColumn`` with `parent`"""
     w = window
+    if call is None:
+        call = lambda d_r, **out: w.dev.array_elements(*w._token_arrays(), d_r, d_select, **w._number_records(), **out)
     room = min(w.n_tokens, 4 * rows + 4096) if elements_capacity is None else int(elements_capacity)
-    res, (d_elements, d_esel), d_off, valid = _grow_once(
-        lambda d_r, room, **out: w.dev.array_elements(
-            w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_r, d_rows_select, d_numbers=w.d_numbers,
-            numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, elements_capacity=room, **out),
-        d_rows, rows, room, "n_elements", f"window at {w.base}: {what}")
+    res, (d_elements, d_esel), d_off, valid = _grow_once(w, lambda d_r, room, **out: call(d_r, elements_capacity=room, **out),
+                                                         d_rows, rows, room, "n_elements", f"the arrays of {what}")
     return ListColumn(w, d_off, d_elements[:int(res.n_elements)], valid, d_esel, parent)
 
 
-def _object_entries(window, d_rows, d_rows_select, rows, entries_capacity, parent, what):
+def _object_entries(window, d_rows, d_select, rows, entries_capacity, parent, what):
     """``object_entries`` over `rows` records, its key and value buffers grown once (``_grow_once``) -> ``MapColumn`` with
     `parent`"""
     w = window
     room = min(w.n_tokens, 4 * rows + 4096) if entries_capacity is None else int(entries_capacity)
     res, (d_keys, d_values, d_ksel, d_vsel), d_off, valid = _grow_once(
-        lambda d_r, room, **out: w.dev.object_entries(
-            w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_r, d_rows_select, d_numbers=w.d_numbers,
-            numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, entries_capacity=room, **out),
-        d_rows, rows, room, "n_entries", f"window at {w.base}: {what}")
+        w, lambda d_r, room, **out: w.dev.object_entries(*w._token_arrays(), d_r, d_select, **w._number_records(), entries_capacity=room, **out),
+        d_rows, rows, room, "n_entries", f"the objects of {what}")
     n = int(res.n_entries)
     return MapColumn(w, d_off, valid, d_keys[:n], d_values[:n], d_ksel, d_vsel, parent)
 
@@ -171,34 +186,26 @@ def _select_word(dvc, n):
     return torch.tensor(list(bytes(_lib.MsjSelectDocumentsResult(0, 0, int(n), 1, int(n), 0, 0))), dtype=torch.uint8, device=dvc)
 
 
-def _take(window, d_take, d_take_select, n_take, d_fields, d_rows_select, what):
-    """``take_rows`` of n_take row numbers from d_fields (int64[n_columns, rows, 2], or [rows, 2] for one column)
+def _take(window, d_fields, d_select, d_take, d_take_select, n_take, what):
+    """``take_rows`` of n_take row numbers from d_fields (int64[n_columns, rows, 2]; from no row, every index is out of range)
     -> (fields int64[n_columns, n_take, 2], the uint8[48] select result that goes with them)"""
-    w = window
-    if d_fields.dim() == 2:
-        d_fields = d_fields.unsqueeze(0)
-    if d_fields.shape[1] == 0:   # (no row to take from: every index is out of range)
-        d_fields = torch.zeros((d_fields.shape[0], 1, 2), dtype=torch.int64, device=d_fields.device)
-    d_res, d_out, d_out_select = w.dev.take_rows(d_take, d_take_select, d_fields, d_rows_select, out_capacity=n_take, sync=False)
-    code = int(d_res[:4].view(torch.int32).item())
+    d_res, d_out, d_out_select = window.dev.take_rows(d_take, d_take_select, _or_blank(d_fields, d_fields.shape[1]), d_select,
+                                                      out_capacity=n_take, sync=False)
+    code = _code(d_res)
     if code != 0:
-        raise DocumentStreamError(code, f"window at {w.base}: {what} could not be taken")
+        raise DocumentStreamError(code, f"window at {window.base}: {what} could not be taken")
     return d_out[:, :n_take], d_out_select
 
 
-def _filter(window, specs, any, d_fields, d_rows_select, rows, what, d_list_offsets=None):
-    """``filter_rows`` over `rows` records per column of d_fields -> (keep bool[rows], kept int32[n_kept], the uint8[48] select
-    result that counts them, the re-based list offsets or None).  The predicates live for the call; its 48-byte result comes
-    to the host, which sizes what follows by n_kept."""
+def _filter(window, d_fields, d_select, rows, specs, any, what, d_list_offsets=None):
+    """``filter_rows`` over `rows` records per column of d_fields (int64[n_columns, rows, 2]) -> (keep bool[rows], kept
+    int32[n_kept], the uint8[48] select result that counts them, the re-based list offsets or None).  The predicates live for
+    the call; its 48-byte result comes to the host, which sizes what follows by n_kept."""
     w = window
-    if d_fields.dim() == 2:
-        d_fields = d_fields.unsqueeze(0)
-    if rows == 0:
-        d_fields = torch.zeros((d_fields.shape[0], 1, 2), dtype=torch.int64, device=d_fields.device)
     predicates = w.dev.compile_predicates(specs, any=any)
     try:
-        res, d_keep, d_kept, d_kept_select, d_list_out = w.dev.filter_rows(predicates, w.d_window, w.length, d_fields, d_rows_select, capacity=rows,
-                                                                           d_list_offsets=d_list_offsets)
+        res, d_keep, d_kept, d_kept_select, d_list_out = w.dev.filter_rows(predicates, w.d_window, w.length, _or_blank(d_fields, rows), d_select,
+                                                                           capacity=rows, d_list_offsets=d_list_offsets)
     finally:
         predicates.close()
         w.dev._paths.remove(predicates)
@@ -230,31 +237,22 @@ def _cast_spec(spec):
     return kind, unit
 
 
-def _cast(window, d_rows, d_rows_select, rows, kind, unit, keep_numbers, what):
+def _cast(window, d_rows, d_select, rows, kind, unit, keep_numbers, what):
     """``cast_strings`` over `rows` records (int64[rows, 2]) -> (the cast records int64[rows, 2], the uint8[48] select result
     that goes with them).  Only the call's 48-byte result comes to the host."""
     w = window
-    if rows == 0:
-        d_rows = torch.zeros((1, 2), dtype=torch.int64, device=d_rows.device)
-    d_res, d_out, d_out_select = w.dev.cast_strings(w.d_window, w.length, d_rows.contiguous(), d_rows_select, kind, unit, keep_numbers,
-                                                    capacity=rows, sync=False)
-    code = int(d_res[:4].view(torch.int32).item())
+    d_res, d_out, d_out_select = w.dev.cast_strings(w.d_window, w.length, _or_blank(d_rows, rows).contiguous(), d_select, kind, unit,
+                                                    keep_numbers, capacity=rows, sync=False)
+    code = _code(d_res)
     if code != 0:
         raise DocumentStreamError(code, f"window at {w.base}: {what} could not be cast")
     return d_out[:rows], d_out_select
 
 
-def _cast_numbers(window, d_rows, d_rows_select, rows, kind, unit, keep_numbers, dtype, what):
-    """``number_column`` over the cast records: (values dtype[rows], valid bool[rows])"""
-    return number_column(_cast(window, d_rows, d_rows_select, rows, kind, unit, keep_numbers, what)[0], dtype)
-
-
-def _cast_for_filter(window, specs, cast, index, d_fields, d_rows_select, rows, what):
+def _cast_for_filter(window, d_fields, d_select, rows, specs, cast, index, what):
     """What ``where(..., cast=...)`` hands the filter: the columns the predicates name, copied, the cast ones replaced by
     their cast records (a quoted number next to a plain one is kept), and the specs re-numbered onto that copy with every
     ``datetime.datetime`` operand turned into its column's unit.  specs: already by column number.  -> (specs, d_fields)"""
-    if d_fields.dim() == 2:
-        d_fields = d_fields.unsqueeze(0)
     kinds = {index(name): _cast_spec(spec) for name, spec in cast.items()}
 
     def columns(spec):
@@ -277,7 +275,7 @@ def _cast_for_filter(window, specs, cast, index, d_fields, d_rows_select, rows, 
     for c in used:
         if c in kinds and rows:
             kind, unit = kinds[c]
-            out[place[c], :rows] = _cast(window, d_fields[c], d_rows_select, rows, kind, unit, kind == "number", what)[0]
+            out[place[c], :rows] = _cast(window, d_fields[c], d_select, rows, kind, unit, kind == "number", what)[0]
         elif rows:
             out[place[c], :rows] = d_fields[c, :rows]
     return [one(s) for s in specs], out
@@ -315,15 +313,14 @@ class DictionaryColumn:
         return self.values(), self.codes.cpu().tolist()
 
 
-def _dictionary(dev, column, what):
+def _dictionary(window, column, what):
     """``dictionary`` over a column (offsets int64[rows + 1], bytes uint8[total], valid bool[rows]) as the column calls
     return it, sized from the call's own layout-only pass -> ``DictionaryColumn``"""
     offsets, data, valid = column
     rows = valid.shape[0]
-    d_valid = valid.view(torch.uint8) if rows else torch.zeros(1, dtype=torch.uint8, device=offsets.device)
-    res, codes, d_off, d_first, d_bytes = dev.dictionary(offsets, data, d_valid, rows=rows)
+    res, codes, d_off, d_first, d_bytes = window.dev.dictionary(offsets, data, _or_blank(valid.view(torch.uint8), rows), rows=rows)
     if res.code != 0:
-        raise DocumentStreamError(int(res.code), f"{what} could not be dictionary-encoded")
+        raise DocumentStreamError(int(res.code), f"window at {window.base}: the strings of {what} could not be dictionary-encoded")
     n = int(res.n_distinct)
     return DictionaryColumn(codes[:rows], d_off[:n + 1], d_bytes[:int(res.dict_bytes)], d_first[:n], valid)
 
@@ -375,7 +372,7 @@ class GroupStats:
         return out
 
 
-def _stats(window, d_fields, d_rows_select, rows, columns, pointers, cast, keys, d_codes, n_groups, what):
+def _stats(window, d_fields, d_select, rows, columns, pointers, cast, keys, d_codes, n_groups, what):
     """``aggregate`` over the named columns of d_fields (int64[n_columns, rows, 2]), cast first where asked -> ``GroupStats``.
     columns: their numbers in d_fields; cast: {column number: spec}; d_codes: int32[rows] or None; the 48-byte result comes to
     the host."""
@@ -388,12 +385,12 @@ def _stats(window, d_fields, d_rows_select, rows, columns, pointers, cast, keys,
             break
         if c in cast:
             kind, unit = _cast_spec(cast[c])
-            fields[j, :rows] = _cast(w, d_fields[c], d_rows_select, rows, kind, unit, kind == "number", what)[0]
+            fields[j, :rows] = _cast(w, d_fields[c], d_select, rows, kind, unit, kind == "number", what)[0]
         else:
             fields[j, :rows] = d_fields[c, :rows]
     if d_codes is not None:
-        d_codes = d_codes.to(torch.int32).contiguous() if rows else torch.zeros(1, dtype=torch.int32, device=fields.device)
-    res, d_groups = w.dev.aggregate(fields, d_rows_select, d_codes, n_groups=n_groups, groups_capacity=max(n_groups, 1))
+        d_codes = _or_blank(d_codes, rows).to(torch.int32).contiguous()
+    res, d_groups = w.dev.aggregate(fields, d_select, d_codes, n_groups=n_groups, groups_capacity=max(n_groups, 1))
     if res.code != 0 or res.n_rows != rows:
         raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be aggregated")
     records = d_groups[:len(columns) * max(n_groups, 1) * 48].view(len(columns), max(n_groups, 1), 48)[:, :n_groups]
@@ -404,6 +401,176 @@ def _rows_of_elements(offsets, n_elements):
     """The row of every element of a list column, int32[n_elements], from its offsets (torch)"""
     at = torch.arange(n_elements, dtype=torch.int64, device=offsets.device)
     return torch.searchsorted(offsets[1:].contiguous(), at, right=True).to(torch.int32)
+
+
+class _Records:
+    """Records by column over a window: what ``Window``, ``RowSelection`` and ``ElementFields`` are and, as ``_OneColumn``,
+    what a ``ListColumn`` and the keys of a ``MapColumn`` run on.  A class says what its rows are through: window, the
+    ``Window``; fields int64[n_columns, rows, 2], one ``msj_field`` per (column, row); d_select uint8[48], the device
+    ``msj_select_documents_result`` that counts the rows; paths, whose ``index`` turns a pointer or an index into a column's
+    number and whose ``pointers`` name the columns; _rows_are, the rows' name in messages; _parent, what ``elements`` and
+    ``entries`` hand on as the new column's parent.
+
+    The calls run on the window's arrays and on the records where they lie; of a call only its small result comes to the
+    host.  A row is not valid, and empty, where the value is not of the kind asked for, the key is missing or the document
+    has a verdict code.  Like every array a Window carries, the window's own arrays are reused by the next window: use what
+    a method returns before the iterator advances."""
+
+    _rows_are = "the rows"
+    _parent = None
+
+    @property
+    def _window(self):
+        return self.window
+
+    @property
+    def _records(self):
+        return self.fields
+
+    def _at(self, path_or_index):
+        """(the window, the records, the rows, the column's number, the column's name in messages)"""
+        fields = self._records
+        p = self.paths.index(path_or_index)
+        return self._window, fields, fields.shape[1], p, f"path {p} of {self._rows_are}"
+
+    def column(self, path_or_index):
+        """The records of one path as a numpy structured array (FIELD_DTYPE), one per row: one host copy."""
+        _, fields, _, p, _ = self._at(path_or_index)
+        return np.ascontiguousarray(fields[p].cpu().numpy()).view(FIELD_DTYPE).reshape(-1)
+
+    def values(self, path_or_index):
+        """The values of one path as a Python list, one per row: None where the record has a code (20 NO_SUCH_FIELD, 17
+        INCORRECT_TYPE, an invalid document's), see ``field_value``.  The window's bytes, d_idx and d_end come to the host
+        once per window."""
+        col = self.column(path_or_index)
+        host = self._window._host_arrays()
+        return [field_value(r, *host) for r in col]
+
+    def _number_column(self, path_or_index, dtype):
+        """The numbers of one path as a column ON THE DEVICE, from the records alone (torch operations, no call), as the
+        module's ``number_column`` gives them: (values dtype[rows], valid bool[rows])"""
+        _, fields, _, p, _ = self._at(path_or_index)
+        return number_column(fields[p], dtype)
+
+    def _cast_column(self, path_or_index, kind, unit, keep_numbers):
+        """``_cast`` over one path's records"""
+        w, fields, rows, p, what = self._at(path_or_index)
+        return _cast(w, fields[p], self.d_select, rows, kind, unit, keep_numbers, what)
+
+    def timestamps(self, path_or_index, unit="ns"):
+        """The RFC 3339 strings of one path -- "ts":"2024-05-01T12:34:56.789Z" -- as a column ON THE DEVICE
+        (``msj_cast_strings_device``, then ``number_column``): (values int64[rows], valid bool[rows]), the count of `unit` ("s"
+        "ms" "us" "ns") since 1970-01-01T00:00:00Z, offsets applied, a fraction cut to the unit.  Not valid, value 0: a string
+        that is no timestamp (or, in "ns", one outside 1677-09-21 .. 2262-04-11), a value that is no string, a missing key, a
+        document with a verdict code.  Only the call's 48-byte result comes to the host."""
+        return number_column(self._cast_column(path_or_index, "timestamp", unit, False)[0], torch.int64)
+
+    def parsed_numbers(self, path_or_index, dtype=torch.float64, keep_numbers=True):
+        """The numbers of one path that are written as strings -- "price":"12.50", "id":"9007199254740993" -- as a column ON
+        THE DEVICE: (values dtype[rows], valid bool[rows]) as ``number_column`` gives them, over the cast records: an integer
+        stays an exact int64.  keep_numbers: a value that already is a number counts as well."""
+        return number_column(self._cast_column(path_or_index, "number", "ns", keep_numbers)[0], dtype)
+
+    def strings(self, path_or_index, bytes_capacity=None):
+        """The string values of one path as a column ON THE DEVICE (``msj_string_column_device``): (offsets int64[rows + 1],
+        bytes uint8[total], valid bool[rows]) -- row k's unescaped UTF-8 is bytes[offsets[k]:offsets[k + 1]], empty where
+        valid[k] is False (the value is no string, the key is missing, the document has a verdict code).  The byte buffer
+        starts from a guess (bytes_capacity: the caller's) and, when the call says it was too small, is made as large as the
+        call asks and the call runs once more."""
+        w, fields, rows, p, what = self._at(path_or_index)
+        return _string_column(w, fields, self.d_select, rows, p, bytes_capacity, what)
+
+    def categories(self, path_or_index, bytes_capacity=None):
+        """The string values of one path in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over
+        ``strings(path)``) -> ``DictionaryColumn``: codes int32[rows], -1 where the row has no string, else the value's
+        number in the order of first appearance, and the distinct values once.  A low-cardinality column -- a status, a
+        country, a device id -- is grouped, compared and counted (``counts()``) without moving a byte to the host."""
+        column = self.strings(path_or_index, bytes_capacity)
+        return _dictionary(self._window, column, self._at(path_or_index)[-1])
+
+    def raw(self, path_or_index, compact=False, bytes_capacity=None):
+        """The JSON text of one path's values as a column ON THE DEVICE (``msj_raw_column_device``): (offsets int64[rows + 1],
+        bytes uint8[total], valid bool[rows]) -- row k's text is bytes[offsets[k]:offsets[k + 1]], the source's own bytes from
+        the value's first to its last, whatever the value is: the way to a container's text without the window on the host.
+        "" is the whole document, or the whole element.  Empty where valid[k] is False (the key is missing, the document has
+        a verdict code).  compact: the blanks between tokens dropped, so that a pretty-printed window gives the bytes of its
+        minified twin: ``raw("", compact=True)`` over documents is those documents as minified NDJSON lines.  The byte buffer
+        starts from a guess (bytes_capacity: the caller's) and is grown once, as in ``strings``."""
+        w, fields, rows, p, what = self._at(path_or_index)
+        return _raw_column(w, fields[p], self.d_select, rows, compact, bytes_capacity, what)
+
+    def elements(self, path_or_index, elements_capacity=None):
+        """The arrays of one path as a list column -- ``tags``, ``items[*].tags`` -- ON THE DEVICE
+        (``msj_array_elements_device``) -> ``ListColumn`` with one row per row of these records: offsets int64[rows + 1], one
+        ``msj_field`` per element back to back, valid bool[rows]; a missing key and a value that is no array are rows that are
+        not valid.  The element buffer starts from a guess (elements_capacity: the caller's) and, when the call says it was
+        too small, is made as large as the call asks and the call runs once more."""
+        w, fields, rows, p, what = self._at(path_or_index)
+        return _array_elements(w, fields[p], self.d_select, rows, elements_capacity, self._parent, what)
+
+    def entries(self, path_or_index, entries_capacity=None):
+        """The objects of one path as a map column -- "attrs":{"color":"red",...} with the keys as data, ``items[*].dims`` --
+        ON THE DEVICE (``msj_object_entries_device``) -> ``MapColumn`` with one row per row of these records: offsets
+        int64[rows + 1], a key and a value ``msj_field`` per entry back to back, valid bool[rows]; a missing key and a value
+        that is no object are rows that are not valid.  The buffers start from a guess (entries_capacity: the caller's) and
+        are grown once, as in ``elements``."""
+        w, fields, rows, p, what = self._at(path_or_index)
+        return _object_entries(w, fields[p], self.d_select, rows, entries_capacity, self._parent, what)
+
+    def stats(self, paths, by=None, cast=None):
+        """Count, sum, min and max of paths per group ON THE DEVICE (``msj_aggregate_device``) -> ``GroupStats``:
+        ``win.stats(["/latency_ms"], by="/status")`` is how many lines, what total, smallest and largest latency per status.
+        by: a path whose strings are dictionary-encoded first (``categories``): group g is the g-th distinct value, a row
+        without a string is in no group; None: all rows are one group.  An int64 stays an int64 -- the sum of integers is
+        the exact integer while it fits -- and a sum with doubles is rounded once: the same bits from run to run and for every
+        order of the lines.  cast: ``{"/ts": ("timestamp", "ms"), "/price": "number"}`` as in ``where``, so that a timestamp
+        has a minimum and a maximum and a quoted number a sum.  The call's 48-byte result comes to the host."""
+        return self._grouped(paths, by, cast)
+
+    def _grouped(self, paths, by, cast, d_list_offsets=None):
+        """``stats``; d_list_offsets: a list column's offsets over these rows, for a group per row of it -- the element's
+        row number, computed from the offsets with torch, being its code"""
+        w, fields, index = self._window, self._records, self.paths.index
+        rows = fields.shape[1]
+        columns = [index(p) for p in paths]
+        keys = self.categories(by) if by is not None else None
+        if keys is not None:
+            d_codes, n_groups = keys.codes, keys.n_distinct
+        elif d_list_offsets is not None:
+            d_codes, n_groups = _rows_of_elements(d_list_offsets, rows), d_list_offsets.shape[0] - 1
+        else:
+            d_codes, n_groups = None, 1
+        return _stats(w, fields, self.d_select, rows, columns, [self.paths.pointers[c] for c in columns],
+                      {index(k): v for k, v in (cast or {}).items()}, keys, d_codes, n_groups, self._rows_are)
+
+    def _filtered(self, specs, any, cast, d_list_offsets=None):
+        """``where``'s filter: specs with the columns named by pointer or index, the cast columns cast for the predicates to
+        see -> what ``_filter`` returns"""
+        w, fields, index = self._window, self._records, self.paths.index
+        rows = fields.shape[1]
+        specs, seen = _column_specs(specs, index), fields
+        if cast:
+            specs, seen = _cast_for_filter(w, fields, self.d_select, rows, specs, cast, index, self._rows_are)
+        return _filter(w, seen, self.d_select, rows, specs, any, self._rows_are, d_list_offsets)
+
+    def _taken(self, d_take, d_take_select, n_take):
+        """``_take`` of these records by n_take row numbers"""
+        return _take(self._window, self._records, self.d_select, d_take, d_take_select, n_take, self._rows_are)
+
+
+class _Unnamed:
+    """The paths of one column without a name: column 0, pointer "" """
+    pointers = [""]
+    index = staticmethod(range(1).__getitem__)
+
+
+class _OneColumn(_Records):
+    """One unnamed column of records int64[rows, 2] as a record view: the elements of a ``ListColumn``, the keys of a
+    ``MapColumn``"""
+    paths = _Unnamed
+
+    def __init__(self, window, fields, d_select, rows_are, parent=None):
+        self.window, self.fields, self.d_select, self._rows_are, self._parent = window, fields.unsqueeze(0), d_select, rows_are, parent
 
 
 class MapColumn:
@@ -425,18 +592,20 @@ class MapColumn:
     def n_entries(self):
         return self.key_fields.shape[0]
 
+    @property
+    def _keys(self):
+        return _OneColumn(self.window, self.key_fields, self.d_keys_select, "the keys of the entries")
+
     def keys(self, bytes_capacity=None):
         """The keys, unescaped, as a string column on the device (``msj_string_column_device`` over the key records):
         (offsets int64[n_entries + 1], bytes uint8[total], valid bool[n_entries])."""
-        w = self.window
-        return _string_column(w.dev, w.d_window, w.length, self.key_fields.unsqueeze(0), 0, self.d_keys_select, self.n_entries, bytes_capacity,
-                              f"window at {w.base}: the keys of the entries")
+        return self._keys.strings(0, bytes_capacity)
 
     def key_categories(self, bytes_capacity=None):
         """The keys in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over ``keys()``) ->
         ``DictionaryColumn`` with one code per entry: the same few names repeated millions of times become one int32 each
         and the names once."""
-        return _dictionary(self.window.dev, self.keys(bytes_capacity), f"window at {self.window.base}: the keys of the entries")
+        return self._keys.categories(0, bytes_capacity)
 
     def schema(self):
         """Which keys these objects have: for each distinct key in the order of first appearance (the key, how many entries
@@ -483,8 +652,9 @@ class ListColumn:
     fields[offsets[k]:offsets[k + 1]]; valid bool[rows], False where the value is no array, the key is missing or the
     document has a verdict code (the row is empty then); d_select uint8[48], the ``msj_select_documents_result`` of the
     element records; parent, the ``ListColumn`` or ``ElementFields`` whose records are this column's rows -- None for
-    ``Window.elements``, whose rows are the documents.  Like every array a Window carries, the window's own arrays are reused
-    by the next window: use the column before the iterator advances."""
+    ``Window.elements``, whose rows are the documents.  The methods that ``Window`` has by path run here on the elements, the
+    one column there is, and mean the same: see ``Window``'s.  Like every array a Window carries, the window's own arrays are
+    reused by the next window: use the column before the iterator advances."""
 
     def __init__(self, window, offsets, fields, valid, d_select, parent=None):
         self.window, self.offsets, self.fields, self.valid, self.d_select = window, offsets, fields, valid, d_select
@@ -494,41 +664,58 @@ class ListColumn:
     def n_elements(self):
         return self.fields.shape[0]
 
+    @property
+    def _one(self):
+        return _OneColumn(self.window, self.fields, self.d_select, "the elements", self)
+
     def numbers(self, dtype=torch.float64):
-        """The elements that are numbers, as ``Window.number_column`` gives them: (values dtype[n_elements], valid
+        """The elements that are numbers, as ``number_column`` gives them: (values dtype[n_elements], valid
         bool[n_elements])."""
-        return number_column(self.fields, dtype)
+        return self._one._number_column(0, dtype)
 
     def timestamps(self, unit="ns"):
-        """The elements that are RFC 3339 strings as int64 counts of `unit` since 1970-01-01T00:00:00Z ON THE DEVICE
-        (``msj_cast_strings_device`` over the element records), see ``Window.timestamps``: (values int64[n_elements], valid
-        bool[n_elements])."""
-        return _cast_numbers(self.window, self.fields, self.d_select, self.n_elements, "timestamp", unit, False, torch.int64,
-                             "the timestamps of the elements")
+        """The elements that are RFC 3339 strings as int64 counts of `unit` since 1970-01-01T00:00:00Z ON THE DEVICE: (values
+        int64[n_elements], valid bool[n_elements])."""
+        return self._one.timestamps(0, unit)
 
     def parsed_numbers(self, dtype=torch.float64, keep_numbers=True):
-        """The elements that are numbers written as strings, see ``Window.parsed_numbers``: (values dtype[n_elements], valid
-        bool[n_elements])."""
-        return _cast_numbers(self.window, self.fields, self.d_select, self.n_elements, "number", "ns", keep_numbers, dtype,
-                             "the quoted numbers of the elements")
+        """The elements that are numbers written as strings: (values dtype[n_elements], valid bool[n_elements])."""
+        return self._one.parsed_numbers(0, dtype, keep_numbers)
 
     def strings(self, bytes_capacity=None):
-        """The elements that are strings as a column on the device (``msj_string_column_device`` over the element records):
-        (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements])."""
-        w = self.window
-        return _string_column(w.dev, w.d_window, w.length, self.fields.unsqueeze(0), 0, self.d_select, self.n_elements, bytes_capacity,
-                              f"window at {w.base}: the strings of the elements")
+        """The elements that are strings as a column on the device: (offsets int64[n_elements + 1], bytes uint8[total],
+        valid bool[n_elements])."""
+        return self._one.strings(0, bytes_capacity)
 
     def categories(self, bytes_capacity=None):
-        """The elements that are strings in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over
-        ``strings()``) -> ``DictionaryColumn`` with one code per element, -1 where the element is no string."""
-        return _dictionary(self.window.dev, self.strings(bytes_capacity), f"window at {self.window.base}: the strings of the elements")
+        """The elements that are strings in the dictionary layout ON THE DEVICE -> ``DictionaryColumn`` with one code per
+        element, -1 where the element is no string."""
+        return self._one.categories(0, bytes_capacity)
 
     def raw(self, compact=False, bytes_capacity=None):
-        """The JSON text of every element as a column on the device (``msj_raw_column_device`` over the element records):
-        (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements]) -- a container's text too, without the
-        window on the host.  compact: the blanks between tokens dropped."""
-        return _raw_column(self.window, self.fields, self.d_select, self.n_elements, compact, bytes_capacity, "the text of the elements")
+        """The JSON text of every element as a column on the device: (offsets int64[n_elements + 1], bytes uint8[total],
+        valid bool[n_elements]) -- a container's text too, without the window on the host.  compact: the blanks between
+        tokens dropped."""
+        return self._one.raw(0, compact, bytes_capacity)
+
+    def elements(self, elements_capacity=None):
+        """The arrays among this column's elements as a list column of their own -- a list of lists -- ON THE DEVICE ->
+        ``ListColumn`` with one row per element of this column, aligned with this column's offsets; an element that is no
+        array is a row that is not valid."""
+        return self._one.elements(0, elements_capacity)
+
+    def entries(self, entries_capacity=None):
+        """The objects among this column's elements as a map column -- a list of maps, or the values of a ``MapColumn`` (a map
+        of maps) -- ON THE DEVICE -> ``MapColumn`` with one row per element of this column; an element that is no object is a
+        row that is not valid."""
+        return self._one.entries(0, entries_capacity)
+
+    def stats(self, per_row=False, cast=None):
+        """Count, sum, min and max of the elements that are numbers ON THE DEVICE (``msj_aggregate_device``) ->
+        ``GroupStats`` with one column, "": over all elements as one group, or with per_row=True a group per row of this
+        column -- ``sum(scores[*])`` per document -- the element's row number, computed from the offsets with torch, being
+        its code.  cast: "number", "timestamp" or ("timestamp", unit) for elements that are strings, see ``Window.where``."""
+        return self._one._grouped([0], None, {0: cast} if cast else None, self.offsets if per_row else None)
 
     def to_python(self):
         """A list per row, None where the row is no array; the elements as ``field_value`` gives them.  The element records
@@ -539,41 +726,26 @@ class ListColumn:
         host = w._host_arrays()
         return [[field_value(r, *host) for r in recs[off[k]:off[k + 1]]] if ok[k] else None for k in range(len(ok))]
 
-    def stats(self, per_row=False, cast=None):
-        """Count, sum, min and max of the elements that are numbers ON THE DEVICE (``msj_aggregate_device``) ->
-        ``GroupStats`` with one column, "": over all elements as one group, or with per_row=True a group per row of this
-        column -- ``sum(scores[*])`` per document -- the element's row number, computed from the offsets with torch, being
-        its code.  cast: "number", "timestamp" or ("timestamp", unit) for elements that are strings, see ``Window.where``."""
-        n, rows = self.n_elements, self.offsets.shape[0] - 1
-        d_codes = _rows_of_elements(self.offsets, n) if per_row else None
-        return _stats(self.window, self.fields.unsqueeze(0), self.d_select, n, [0], [""], {0: cast} if cast else {}, None, d_codes,
-                      rows if per_row else 1, "the elements")
-
     def select(self, pointers_or_paths):
         """Fields by path inside the elements -- ``items[*].sku`` -- ON THE DEVICE (``msj_select_elements_device``) ->
         ``ElementFields``: one ``msj_field`` per (path, element), each path a column aligned with this column's offsets.
         pointers_or_paths: JSON pointers (object keys only, "" the element itself) or what ``compile_paths`` made of them.
         The call runs on the window's arrays and the element records where they lie; only its 48-byte result comes to the
         host."""
-        w = self.window
+        w, n = self.window, self.n_elements
         paths = pointers_or_paths if hasattr(pointers_or_paths, "handle") else w.dev.compile_paths(list(pointers_or_paths))
-        d_rows = self.fields if self.n_elements else torch.zeros((1, 2), dtype=torch.int64, device=self.fields.device)
-        res, d_fields = w.dev.select_elements(
-            paths, w.d_window, w.length, w.d_idx, w.n_tokens, w.d_type, w.d_depth, w.d_match, w.d_end, w.d_flags, d_rows, self.d_select,
-            d_numbers=w.d_numbers, numbers_capacity=w.d_numbers.shape[0], d_numbers_result=w.d_numbers_result, capacity=self.n_elements,
-            sync=False)
-        code = int(res[:4].view(torch.int32).item())
+        res, d_fields = w.dev.select_elements(paths, w.d_window, w.length, *w._token_arrays(), _or_blank(self.fields, n), self.d_select,
+                                              **w._number_records(), capacity=n, sync=False)
+        code = _code(res)
         if code != 0:
             raise DocumentStreamError(code, f"window at {w.base}: the fields of the elements could not be selected")
-        return ElementFields(self, paths, d_fields[:, :self.n_elements], res)
+        return ElementFields(self, paths, d_fields[:, :n], res)
 
-    def _kept_elements(self, specs, any, d_fields, d_rows_select, what):
-        """The filter over one record (or more, path-major) per element, the offsets re-based, the element records taken
-        -> (kept int32[n_kept], its select result, the new ``ListColumn``)"""
-        w, n = self.window, self.n_elements
-        _, kept, d_kept_select, d_off = _filter(w, specs, any, d_fields, d_rows_select, n, what, d_list_offsets=self.offsets)
-        fields, d_esel = _take(w, kept, d_kept_select, kept.shape[0], self.fields, self.d_select, what)
-        return kept, d_kept_select, ListColumn(w, d_off, fields[0], self.valid, d_esel, self.parent)
+    def _kept_elements(self, kept, d_kept_select, d_offsets):
+        """What a filter over one record (or more, path-major) per element kept, as a list column: the element records taken,
+        the offsets the re-based ones -> ``ListColumn`` with this column's rows and validity"""
+        fields, d_esel = self._one._taken(kept, d_kept_select, kept.shape[0])
+        return ListColumn(self.window, d_offsets, fields[0], self.valid, d_esel, self.parent)
 
     def where(self, specs, any=False, cast=None):
         """The elements that pass predicates -- ``tags[*] == "red"``, ``scores[*] > 0.5`` -- ON THE DEVICE
@@ -581,35 +753,18 @@ class ListColumn:
         column's rows and validity, new offsets, and the records of the kept elements in their order.  specs: as for
         ``Stage1Device.compile_predicates``, the elements themselves being column 0.  cast: ``{0: ("timestamp", "ms")}`` or
         ``{0: "number"}``, see ``Window.where``; the records kept are the originals."""
-        index = lambda c: range(1)[c]
-        specs = _column_specs(specs, index)
-        d_fields = self.fields
-        if cast:
-            specs, d_fields = _cast_for_filter(self.window, specs, cast, index, self.fields, self.d_select, self.n_elements, "the elements")
-        return self._kept_elements(specs, any, d_fields, self.d_select, "the elements")[2]
-
-    def elements(self, elements_capacity=None):
-        """The arrays among this column's elements as a list column of their own -- a list of lists -- ON THE DEVICE
-        (``msj_array_elements_device``) -> ``ListColumn`` with one row per element of this column, aligned with this column's
-        offsets; an element that is no array is a row that is not valid.  The element buffer starts from a guess
-        (elements_capacity: the caller's) and is grown once, as in ``Window.elements``."""
-        return _array_elements(self.window, self.fields, self.d_select, self.n_elements, elements_capacity, self,
-                               "the arrays among the elements")
-
-    def entries(self, entries_capacity=None):
-        """The objects among this column's elements as a map column -- a list of maps, or the values of a ``MapColumn`` (a map
-        of maps) -- ON THE DEVICE (``msj_object_entries_device``) -> ``MapColumn`` with one row per element of this column; an
-        element that is no object is a row that is not valid.  The buffers start from a guess (entries_capacity: the
-        caller's) and are grown once, as in ``Window.elements``."""
-        return _object_entries(self.window, self.fields, self.d_select, self.n_elements, entries_capacity, self,
-                               "the objects among the elements")
+        _, kept, d_kept_select, d_offsets = self._one._filtered(specs, any, cast, self.offsets)
+        return self._kept_elements(kept, d_kept_select, d_offsets)
 
 
-class ElementFields:
-    """Fields by path inside the elements of a ``ListColumn`` ON THE DEVICE (``ListColumn.select``).  fields int64[n_paths,
-    n_elements, 2], one ``msj_field`` per (path, element): element j of row k of the list column is fields[p, offsets[k] + j],
-    so every path is a column of a list of structs.  d_select uint8[48], the call's ``msj_select_documents_result``; paths,
-    the compiled paths; column, the list column the rows came from."""
+class ElementFields(_Records):
+    """Fields by path inside the elements of a ``ListColumn`` ON THE DEVICE (``ListColumn.select``): the rows are the
+    elements.  fields int64[n_paths, n_elements, 2], one ``msj_field`` per (path, element): element j of row k of the list
+    column is fields[p, offsets[k] + j], so every path is a column of a list of structs -- ``items[*].at``,
+    ``items[*].price``.  d_select uint8[48], the call's ``msj_select_documents_result``; paths, the compiled paths;
+    list_column, the list column the rows came from.  The methods mean what they mean on ``Window``, over the elements."""
+
+    _rows_are = "the elements"
 
     def __init__(self, column, paths, fields, d_select):
         self.list_column, self.paths, self.fields, self.d_select = column, paths, fields, d_select
@@ -618,64 +773,26 @@ class ElementFields:
     def n_elements(self):
         return self.fields.shape[1]
 
-    def column(self, path_or_index):
-        """The records of one path as a numpy structured array (FIELD_DTYPE), one per element: one host copy."""
-        p = self.paths.index(path_or_index)
-        return np.ascontiguousarray(self.fields[p].cpu().numpy()).view(FIELD_DTYPE).reshape(-1)
+    @property
+    def _window(self):
+        return self.list_column.window
+
+    @property
+    def _parent(self):
+        return self
 
     def numbers(self, path_or_index, dtype=torch.float64):
         """The numbers of one path as ``number_column`` gives them: (values dtype[n_elements], valid bool[n_elements])."""
-        return number_column(self.fields[self.paths.index(path_or_index)], dtype)
-
-    def timestamps(self, path_or_index, unit="ns"):
-        """The RFC 3339 strings of one path -- ``items[*].at`` -- as int64 counts of `unit` since 1970-01-01T00:00:00Z ON THE
-        DEVICE, see ``Window.timestamps``: (values int64[n_elements], valid bool[n_elements])."""
-        p = self.paths.index(path_or_index)
-        return _cast_numbers(self.list_column.window, self.fields[p], self.d_select, self.n_elements, "timestamp", unit, False, torch.int64,
-                             f"the timestamps of path {p} of the elements")
-
-    def parsed_numbers(self, path_or_index, dtype=torch.float64, keep_numbers=True):
-        """The numbers written as strings of one path -- ``items[*].price`` -- see ``Window.parsed_numbers``: (values
-        dtype[n_elements], valid bool[n_elements])."""
-        p = self.paths.index(path_or_index)
-        return _cast_numbers(self.list_column.window, self.fields[p], self.d_select, self.n_elements, "number", "ns", keep_numbers, dtype,
-                             f"the quoted numbers of path {p} of the elements")
-
-    def strings(self, path_or_index, bytes_capacity=None):
-        """The strings of one path as a column on the device (``msj_string_column_device`` over the path's records):
-        (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements])."""
-        w, p = self.list_column.window, self.paths.index(path_or_index)
-        return _string_column(w.dev, w.d_window, w.length, self.fields, p, self.d_select, self.n_elements, bytes_capacity,
-                              f"window at {w.base}: the strings of path {p} of the elements")
-
-    def categories(self, path_or_index, bytes_capacity=None):
-        """The strings of one path in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over ``strings(path)``)
-        -> ``DictionaryColumn`` with one code per element, -1 where the value is no string or the key is missing."""
-        w = self.list_column.window
-        return _dictionary(w.dev, self.strings(path_or_index, bytes_capacity), f"window at {w.base}: the strings of a path of the elements")
-
-    def raw(self, path_or_index, compact=False, bytes_capacity=None):
-        """The JSON text of one path's values as a column on the device (``msj_raw_column_device`` over the path's records):
-        (offsets int64[n_elements + 1], bytes uint8[total], valid bool[n_elements]); a missing key is a row that is not
-        valid.  compact: the blanks between tokens dropped."""
-        p = self.paths.index(path_or_index)
-        return _raw_column(self.list_column.window, self.fields[p], self.d_select, self.n_elements, compact, bytes_capacity,
-                           f"the text of path {p} of the elements")
+        return self._number_column(path_or_index, dtype)
 
     def stats(self, paths, by=None, cast=None, per_row=False):
         """Count, sum, min and max of paths of the elements ON THE DEVICE (``msj_aggregate_device``) -> ``GroupStats``, see
         ``Window.stats``.  by: a path whose strings group the elements; per_row=True instead: a group per row of the list
         column -- ``sum(items[*].qty)`` per document -- the element's row number, computed from the offsets with torch,
         being its code."""
-        col, w = self.list_column, self.list_column.window
         if by is not None and per_row:
             raise ValueError("by and per_row exclude each other")
-        columns = [self.paths.index(p) for p in paths]
-        keys = self.categories(by) if by is not None else None
-        d_codes = keys.codes if keys is not None else _rows_of_elements(col.offsets, self.n_elements) if per_row else None
-        n_groups = keys.n_distinct if keys is not None else col.offsets.shape[0] - 1 if per_row else 1
-        return _stats(w, self.fields, self.d_select, self.n_elements, columns, [self.paths.pointers[c] for c in columns],
-                      {self.paths.index(k): v for k, v in (cast or {}).items()}, keys, d_codes, n_groups, "the fields of the elements")
+        return self._grouped(paths, by, cast, self.list_column.offsets if per_row else None)
 
     def where(self, specs, any=False, cast=None):
         """The elements whose fields pass predicates -- ``items[*].qty > 1`` -- ON THE DEVICE (``msj_filter_rows_device`` with
@@ -684,37 +801,10 @@ class ElementFields:
         the same vector: ``items[*]`` stays a list column.  specs: as for ``Stage1Device.compile_predicates``, the columns
         named by pointer or index.  cast: ``{"/at": ("timestamp", "ms"), "/price": "number"}``, see ``Window.where``; the
         records kept are the originals."""
-        col, w = self.list_column, self.list_column.window
-        specs = _column_specs(specs, self.paths.index)
-        what = "the fields of the elements"
-        d_fields = self.fields
-        if cast:
-            specs, d_fields = _cast_for_filter(w, specs, cast, self.paths.index, self.fields, self.d_select, self.n_elements, what)
-        kept, d_kept_select, column = col._kept_elements(specs, any, d_fields, self.d_select, what)
-        fields, d_fsel = _take(w, kept, d_kept_select, kept.shape[0], self.fields, self.d_select, what)
+        _, kept, d_kept_select, d_offsets = self._filtered(specs, any, cast, self.list_column.offsets)
+        column = self.list_column._kept_elements(kept, d_kept_select, d_offsets)
+        fields, d_fsel = self._taken(kept, d_kept_select, kept.shape[0])
         return ElementFields(column, self.paths, fields, d_fsel)
-
-    def elements(self, path_or_index, elements_capacity=None):
-        """The arrays of one path as a list column -- ``items[*].tags`` -- ON THE DEVICE (``msj_array_elements_device``) ->
-        ``ListColumn`` with one row per element of the list column the fields were selected in; a missing key and a value
-        that is no array are rows that are not valid.  The element buffer starts from a guess (elements_capacity: the
-        caller's) and is grown once, as in ``Window.elements``."""
-        p = self.paths.index(path_or_index)
-        return _array_elements(self.list_column.window, self.fields[p], self.d_select, self.n_elements, elements_capacity, self,
-                               f"the arrays of path {p} of the elements")
-
-    def entries(self, path_or_index, entries_capacity=None):
-        """The objects of one path as a map column -- ``items[*].dims`` -- ON THE DEVICE (``msj_object_entries_device``) ->
-        ``MapColumn`` with one row per element of the list column the fields were selected in; a missing key and a value that
-        is no object are rows that are not valid."""
-        p = self.paths.index(path_or_index)
-        return _object_entries(self.list_column.window, self.fields[p], self.d_select, self.n_elements, entries_capacity, self,
-                               f"the objects of path {p} of the elements")
-
-    def values(self, path_or_index):
-        """The values of one path as a Python list, one per element: None where the record has a code, see ``field_value``."""
-        host = self.list_column.window._host_arrays()
-        return [field_value(r, *host) for r in self.column(path_or_index)]
 
     def to_python(self):
         """A list per row of the list column, None where the row is no array; per element a dict {pointer: value} over the
@@ -728,12 +818,16 @@ class ElementFields:
         return [[struct_of(j) for j in range(off[k], off[k + 1])] if ok[k] else None for k in range(len(ok))]
 
 
-class RowSelection:
-    """Rows of a window chosen by predicate or by number ON THE DEVICE (``Window.where``, ``Window.take``).  keep bool[D]: the
-    mask over the window's documents (None for ``Window.take``); rows int32[n_rows]: the chosen documents' numbers -- ascending
-    from ``where``; fields int64[n_paths, n_rows, 2]: their records, each path a column; d_select uint8[48], the
-    ``msj_select_documents_result`` that goes with them.  The methods mean what they mean on ``Window``, over the chosen rows.
-    Like every array a Window carries, the window's own arrays are reused by the next window."""
+class RowSelection(_Records):
+    """Rows of a window chosen by predicate or by number ON THE DEVICE (``Window.where``, ``Window.take``): the rows are the
+    chosen documents.  keep bool[D]: the mask over the window's documents (None for ``Window.take``); rows int32[n_rows]: the
+    chosen documents' numbers -- ascending from ``where``; fields int64[n_paths, n_rows, 2]: their records, each path a
+    column; d_select uint8[48], the ``msj_select_documents_result`` that goes with them.  The methods mean what they mean on
+    ``Window``, over the chosen rows: ``raw("", compact=True)`` is the chosen documents as minified NDJSON lines, and
+    ``elements`` and ``entries`` give a row per chosen row.  Like every array a Window carries, the window's own arrays are
+    reused by the next window."""
+
+    _rows_are = "the chosen rows"
 
     def __init__(self, window, keep, rows, fields, d_select):
         self.window, self.paths, self.keep, self.rows, self.fields, self.d_select = window, window.paths, keep, rows, fields, d_select
@@ -742,72 +836,9 @@ class RowSelection:
     def n_rows(self):
         return self.rows.shape[0]
 
-    def column(self, path_or_index):
-        """The records of one path as a numpy structured array (FIELD_DTYPE), one per chosen row: one host copy."""
-        p = self.paths.index(path_or_index)
-        return np.ascontiguousarray(self.fields[p].cpu().numpy()).view(FIELD_DTYPE).reshape(-1)
-
-    def values(self, path_or_index):
-        """The values of one path as a Python list, one per chosen row, see ``Window.values``."""
-        host = self.window._host_arrays()
-        return [field_value(r, *host) for r in self.column(path_or_index)]
-
     def number_column(self, path_or_index, dtype=torch.float64):
         """The numbers of one path as ``Window.number_column`` gives them: (values dtype[n_rows], valid bool[n_rows])."""
-        return number_column(self.fields[self.paths.index(path_or_index)], dtype)
-
-    def timestamps(self, path_or_index, unit="ns"):
-        """The RFC 3339 strings of one path as int64 counts of `unit`, see ``Window.timestamps``: (values int64[n_rows], valid
-        bool[n_rows])."""
-        p = self.paths.index(path_or_index)
-        return _cast_numbers(self.window, self.fields[p], self.d_select, self.n_rows, "timestamp", unit, False, torch.int64,
-                             f"the timestamps of path {p} of the chosen rows")
-
-    def parsed_numbers(self, path_or_index, dtype=torch.float64, keep_numbers=True):
-        """The numbers written as strings of one path, see ``Window.parsed_numbers``: (values dtype[n_rows], valid
-        bool[n_rows])."""
-        p = self.paths.index(path_or_index)
-        return _cast_numbers(self.window, self.fields[p], self.d_select, self.n_rows, "number", "ns", keep_numbers, dtype,
-                             f"the quoted numbers of path {p} of the chosen rows")
-
-    def strings(self, path_or_index, bytes_capacity=None):
-        """The strings of one path as a column on the device, see ``Window.strings``: (offsets int64[n_rows + 1], bytes
-        uint8[total], valid bool[n_rows])."""
-        w, p = self.window, self.paths.index(path_or_index)
-        return _string_column(w.dev, w.d_window, w.length, self.fields, p, self.d_select, self.n_rows, bytes_capacity,
-                              f"window at {w.base}: the strings of path {p} of the chosen rows")
-
-    def categories(self, path_or_index, bytes_capacity=None):
-        """The strings of one path in the dictionary layout, see ``Window.categories`` -> ``DictionaryColumn``."""
-        w = self.window
-        return _dictionary(w.dev, self.strings(path_or_index, bytes_capacity), f"window at {w.base}: the strings of a path of the chosen rows")
-
-    def raw(self, path_or_index, compact=False, bytes_capacity=None):
-        """The JSON text of one path's values, see ``Window.raw``; ``raw("", compact=True)`` is the chosen documents as
-        minified NDJSON lines."""
-        p = self.paths.index(path_or_index)
-        return _raw_column(self.window, self.fields[p], self.d_select, self.n_rows, compact, bytes_capacity, f"the text of path {p} of the chosen rows")
-
-    def stats(self, paths, by=None, cast=None):
-        """Count, sum, min and max of paths over the chosen rows, see ``Window.stats`` -> ``GroupStats``."""
-        columns = [self.paths.index(p) for p in paths]
-        keys = self.categories(by) if by is not None else None
-        return _stats(self.window, self.fields, self.d_select, self.n_rows, columns, [self.paths.pointers[c] for c in columns],
-                      {self.paths.index(k): v for k, v in (cast or {}).items()}, keys, keys.codes if keys is not None else None,
-                      keys.n_distinct if keys is not None else 1, "the chosen rows")
-
-    def elements(self, path_or_index, elements_capacity=None):
-        """The arrays of one path as a ``ListColumn`` with one row per chosen row (``msj_array_elements_device``: the rows are
-        records, no longer the documents)."""
-        p = self.paths.index(path_or_index)
-        return _array_elements(self.window, self.fields[p], self.d_select, self.n_rows, elements_capacity, None,
-                               f"the arrays of path {p} of the chosen rows")
-
-    def entries(self, path_or_index, entries_capacity=None):
-        """The objects of one path as a ``MapColumn`` with one row per chosen row (``msj_object_entries_device``)."""
-        p = self.paths.index(path_or_index)
-        return _object_entries(self.window, self.fields[p], self.d_select, self.n_rows, entries_capacity, None,
-                               f"the objects of path {p} of the chosen rows")
+        return self._number_column(path_or_index, dtype)
 
 
 def _skip_flag(n):
@@ -821,7 +852,11 @@ class DocumentStreamError(RuntimeError):
 
 
 @dataclass
-class Window:
+class Window(_Records):
+    """One window of complete documents, as ``DocumentStream`` yields it.  With select=[...] it is a record view whose rows are
+    the window's D = n_documents complete documents: ``column``, ``values``, ``number_column``, ``strings``, ``categories``,
+    ``raw``, ``timestamps``, ``parsed_numbers``, ``elements``, ``entries`` and ``stats`` by path, and ``cast``, ``where`` and
+    ``take``.  Every array a Window carries is reused by the next window."""
     base: int           # byte offset of the window in the stream (16-byte aligned)
     length: int         # bytes indexed from there
     consumed: int       # bytes that belong to this window's complete documents (the next window starts at base + consumed)
@@ -858,88 +893,44 @@ class Window:
     _documents: list = field(default=None, repr=False, compare=False)  # what documents() built: host copies, kept
     _host: tuple = field(default=None, repr=False, compare=False)      # what values() reads: host copies, kept
 
-    def column(self, path_or_index):
-        """The records of one path as a numpy structured array (FIELD_DTYPE), one per complete document: one host copy.
-        Like every array a Window carries, d_fields is reused by the next window."""
+    _rows_are = "the documents"
+
+    @property
+    def _window(self):
+        return self
+
+    @property
+    def _records(self):
         if self.d_fields is None:
             raise ValueError("no fields: the stream was not created with select=[...]")
-        p = self.paths.index(path_or_index)
-        return np.ascontiguousarray(self.d_fields[p].cpu().numpy()).view(FIELD_DTYPE).reshape(-1)
+        return self.d_fields
 
-    def values(self, path_or_index):
-        """The values of one path as a Python list, one per complete document: None where the record has a code (20
-        NO_SUCH_FIELD, 17 INCORRECT_TYPE, an invalid document's), see ``field_value``.  The window's bytes, d_idx and d_end
-        come to the host once per window."""
-        col = self.column(path_or_index)
-        host = self._host_arrays()
-        return [field_value(r, *host) for r in col]
+    def _token_arrays(self):
+        """The token arrays as the calls take them in front of their records"""
+        return self.d_idx, self.n_tokens, self.d_type, self.d_depth, self.d_match, self.d_end, self.d_flags
+
+    def _number_records(self):
+        """The number call's records and result as the calls take them"""
+        return dict(d_numbers=self.d_numbers, numbers_capacity=self.d_numbers.shape[0], d_numbers_result=self.d_numbers_result)
 
     def _host_arrays(self):
         if self._host is None:
             self._host = (self.d_window.cpu().numpy(), self.d_idx.cpu().numpy().view(np.uint32), self.d_end.cpu().numpy().view(np.uint32))
         return self._host
 
-    def strings(self, path_or_index, bytes_capacity=None):
-        """The string values of one path as a column ON THE DEVICE (``msj_string_column_device``): (offsets int64[D + 1],
-        bytes uint8[total], valid bool[D]) -- row k's unescaped UTF-8 is bytes[offsets[k]:offsets[k + 1]], empty where valid[k]
-        is False (the value is no string, the key is missing, the document has a verdict code).  The call runs on the
-        window's records and bytes where they lie; only its 48-byte result comes to the host.  The byte buffer starts from
-        a guess (bytes_capacity: the caller's) and, when the call says it was too small, is made as large as the call asks and
-        the call runs once more."""
-        if self.d_fields is None:
-            raise ValueError("no fields: the stream was not created with select=[...]")
-        p = self.paths.index(path_or_index)
-        return _string_column(self.dev, self.d_window, self.length, self.d_fields, p, self.d_select, self.n_documents, bytes_capacity,
-                              f"window at {self.base}: the strings of path {p}")
-
-    def categories(self, path_or_index, bytes_capacity=None):
-        """The string values of one path in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over
-        ``strings(path)``) -> ``DictionaryColumn``: codes int32[D], -1 where the row has no string, else the value's number
-        in the order of first appearance, and the distinct values once.  A low-cardinality column -- a status, a country, a
-        device id -- is grouped, compared and counted (``counts()``) without moving a byte to the host."""
-        return _dictionary(self.dev, self.strings(path_or_index, bytes_capacity), f"window at {self.base}: the strings of a path")
-
-    def raw(self, path_or_index, compact=False, bytes_capacity=None):
-        """The JSON text of one path's values as a column ON THE DEVICE (``msj_raw_column_device``): (offsets int64[D + 1],
-        bytes uint8[total], valid bool[D]) -- row k's text is bytes[offsets[k]:offsets[k + 1]], the source's own bytes from the
-        value's first to its last, whatever the value is: the way to a container's text without the window on the host.  ""
-        is the whole document.  Empty where valid[k] is False (the key is missing, the document has a verdict code).
-        compact: the blanks between tokens dropped, so that a pretty-printed window gives the bytes of its minified twin.
-        The byte buffer starts from a guess (bytes_capacity: the caller's) and is grown once, as in ``strings``."""
-        if self.d_fields is None:
-            raise ValueError("no fields: the stream was not created with select=[...]")
-        p = self.paths.index(path_or_index)
-        return _raw_column(self, self.d_fields[p], self.d_select, self.n_documents, compact, bytes_capacity, f"the text of path {p}")
+    def number_column(self, path_or_index, dtype=torch.float64):
+        """The numbers of one path as a column ON THE DEVICE, from the records alone (torch operations, no call): (values
+        dtype[D], valid bool[D]).  torch.int64: valid where the value is an integer (tag 'l'); torch.float64: the doubles
+        (tag 'd') as they are and the integers converted.  A number without bits (MSJ_FIELD_NO_BITS), a value of another
+        kind and a record with a code are not valid; their value is 0."""
+        return self._number_column(path_or_index, dtype)
 
     def elements(self, path_or_index, elements_capacity=None):
-        """The arrays of one path as a list column ON THE DEVICE (``msj_array_column_device``) -> ``ListColumn``: offsets
-        int64[D + 1], one ``msj_field`` per element back to back, valid bool[D].  The call runs on the window's arrays and
-        records where they lie; only its 48-byte result comes to the host.  The element buffer starts from a guess
-        (elements_capacity: the caller's) and, when the call says it was too small, is made as large as the call asks and the
-        call runs once more."""
-        if self.d_fields is None:
-            raise ValueError("no fields: the stream was not created with select=[...]")
-        p = self.paths.index(path_or_index)
-        nd, nt = self.n_documents, self.n_tokens
-        room = min(nt, 4 * nd + 4096) if elements_capacity is None else int(elements_capacity)
-        res, (d_elements, d_esel), d_off, valid = _grow_once(
-            lambda d_f, room, **out: self.dev.array_column(
-                self.d_idx, nt, self.d_type, self.d_depth, self.d_match, self.d_end, self.d_flags, self.d_doc_first, self.d_docs, d_f, p,
-                self.d_select, d_numbers=self.d_numbers, numbers_capacity=self.d_numbers.shape[0], d_numbers_result=self.d_numbers_result,
-                elements_capacity=room, **out),
-            self.d_fields, nd, room, "n_elements", f"window at {self.base}: the arrays of path {p}")
-        return ListColumn(self, d_off, d_elements[:int(res.n_elements)], valid, d_esel)
-
-    def entries(self, path_or_index, entries_capacity=None):
-        """The objects of one path as a map column ON THE DEVICE (``msj_object_entries_device``) -> ``MapColumn``: offsets
-        int64[D + 1], a key and a value ``msj_field`` per entry back to back, valid bool[D] -- "attrs":{"color":"red",...}
-        with the keys as data.  The rows are the documents: the path's records of the window's select call.  The call runs
-        on the window's arrays and records where they lie; only its 48-byte result comes to the host.  The buffers start
-        from a guess (entries_capacity: the caller's) and are grown once, as in ``Window.elements``."""
-        if self.d_fields is None:
-            raise ValueError("no fields: the stream was not created with select=[...]")
-        p = self.paths.index(path_or_index)
-        return _object_entries(self, self.d_fields[p], self.d_select, self.n_documents, entries_capacity, None, f"the objects of path {p}")
+        """The arrays of one path as a list column ON THE DEVICE -> ``ListColumn``, as every record view's ``elements``; the
+        rows being the documents, the call is ``msj_array_column_device``, which finds them by the document split."""
+        w, fields, rows, p, what = self._at(path_or_index)
+        return _array_elements(w, fields, self.d_select, rows, elements_capacity, None, what, call=lambda d_f, **out: self.dev.array_column(
+            *self._token_arrays(), self.d_doc_first, self.d_docs, d_f, p, self.d_select, **self._number_records(), **out))
 
     def cast(self, path_or_index, kind, unit="ns", keep_numbers=False):
         """One path's strings cast to numbers ON THE DEVICE (``msj_cast_strings_device``) -> (records int64[D, 2], the
@@ -947,26 +938,7 @@ class Window:
         ``take_rows`` and ``number_column`` take them as they take a select call's records.  kind: "timestamp" (RFC 3339; the
         int64 counts `unit` since 1970-01-01T00:00:00Z) or "number" (the string, whole, is one JSON number).  A string that is
         neither becomes code 9, a value that is no string code 17 -- or itself, when it is a number and keep_numbers is set."""
-        if self.d_fields is None:
-            raise ValueError("no fields: the stream was not created with select=[...]")
-        p = self.paths.index(path_or_index)
-        return _cast(self, self.d_fields[p], self.d_select, self.n_documents, kind, unit, keep_numbers, f"path {p}")
-
-    def timestamps(self, path_or_index, unit="ns"):
-        """The RFC 3339 strings of one path -- "ts":"2024-05-01T12:34:56.789Z" -- as a column ON THE DEVICE: (values int64[D],
-        valid bool[D]), the count of `unit` ("s" "ms" "us" "ns") since 1970-01-01T00:00:00Z, offsets applied, a fraction cut
-        to the unit.  Not valid, value 0: a string that is no timestamp (or, in "ns", one outside 1677-09-21 .. 2262-04-11),
-        a value that is no string, a missing key, a document with a verdict code.  ``cast`` and ``number_column``; only the
-        call's 48-byte result comes to the host."""
-        records, _ = self.cast(path_or_index, "timestamp", unit)
-        return number_column(records, torch.int64)
-
-    def parsed_numbers(self, path_or_index, dtype=torch.float64, keep_numbers=True):
-        """The numbers of one path that are written as strings -- "price":"12.50", "id":"9007199254740993" -- as a column ON
-        THE DEVICE: (values dtype[D], valid bool[D]) as ``number_column`` gives them, over the cast records: an integer stays
-        an exact int64.  keep_numbers: a value that already is a number counts as well."""
-        records, _ = self.cast(path_or_index, "number", keep_numbers=keep_numbers)
-        return number_column(records, dtype)
+        return self._cast_column(path_or_index, kind, unit, keep_numbers)
 
     def where(self, specs, any=False, cast=None):
         """The documents that pass predicates on their selected fields ON THE DEVICE (``msj_filter_rows_device``,
@@ -978,54 +950,18 @@ class Window:
         (``msj_cast_strings_device``), so that ``[("/ts", ">=", t0), ("/ts", "<", t1)]`` is two exact int64 compares; a
         ``datetime.datetime`` operand -- aware, or naive, which means UTC -- becomes the column's unit by integer arithmetic
         (``datetime_units``).  The records the selection carries stay the originals."""
-        if self.d_fields is None:
-            raise ValueError("no fields: the stream was not created with select=[...]")
-        specs = _column_specs(specs, self.paths.index)
-        d_fields = self.d_fields
-        if cast:
-            specs, d_fields = _cast_for_filter(self, specs, cast, self.paths.index, self.d_fields, self.d_select, self.n_documents, "the documents")
-        keep, kept, d_kept_select, _ = _filter(self, specs, any, d_fields, self.d_select, self.n_documents, "the documents")
-        fields, d_fsel = _take(self, kept, d_kept_select, kept.shape[0], self.d_fields, self.d_select, "the documents")
+        keep, kept, d_kept_select, _ = self._filtered(specs, any, cast)
+        fields, d_fsel = self._taken(kept, d_kept_select, kept.shape[0])
         return RowSelection(self, keep, kept, fields, d_fsel)
-
-    def stats(self, paths, by=None, cast=None):
-        """Count, sum, min and max of paths per group ON THE DEVICE (``msj_aggregate_device``) -> ``GroupStats``:
-        ``win.stats(["/latency_ms"], by="/status")`` is how many lines, what total, smallest and largest latency per status.
-        by: a path whose strings are dictionary-encoded first (``categories``): group g is the g-th distinct value, a row
-        without a string is in no group; None: the window is one group.  An int64 stays an int64 -- the sum of integers is
-        the exact integer while it fits -- and a sum with doubles is rounded once: the same bits from run to run and for every
-        order of the lines.  cast: ``{"/ts": ("timestamp", "ms"), "/price": "number"}`` as in ``where``, so that a timestamp
-        has a minimum and a maximum and a quoted number a sum.  The call's 48-byte result comes to the host."""
-        if self.d_fields is None:
-            raise ValueError("no fields: the stream was not created with select=[...]")
-        columns = [self.paths.index(p) for p in paths]
-        keys = self.categories(by) if by is not None else None
-        return _stats(self, self.d_fields, self.d_select, self.n_documents, columns, [self.paths.pointers[c] for c in columns],
-                      {self.paths.index(k): v for k, v in (cast or {}).items()}, keys, keys.codes if keys is not None else None,
-                      keys.n_distinct if keys is not None else 1, "the documents")
 
     def take(self, rows):
         """The documents with the given numbers ON THE DEVICE (``msj_take_rows_device``) -> ``RowSelection``.  rows: an int32
         device tensor, any order, repeats allowed -- ``categories(path).first`` gives one document per distinct value; a
         number at or past n_documents gives a row of missing values."""
-        if self.d_fields is None:
-            raise ValueError("no fields: the stream was not created with select=[...]")
-        rows = rows.to(device=self.d_fields.device, dtype=torch.int32).contiguous()
+        rows = rows.to(device=self._records.device, dtype=torch.int32).contiguous()
         n = rows.shape[0]
-        d_take = rows if n else torch.zeros(1, dtype=torch.int32, device=rows.device)
-        fields, d_fsel = _take(self, d_take, _select_word(rows.device, n), n, self.d_fields, self.d_select, "the documents")
+        fields, d_fsel = self._taken(_or_blank(rows, n), _select_word(rows.device, n), n)
         return RowSelection(self, None, rows, fields, d_fsel)
-
-    def number_column(self, path_or_index, dtype=torch.float64):
-        """The numbers of one path as a column ON THE DEVICE, from the records alone (torch operations, no call): (values
-        dtype[D], valid bool[D]).  torch.int64: valid where the value is an integer (tag 'l'); torch.float64: the doubles
-        (tag 'd') as they are and the integers converted.  A number without bits (MSJ_FIELD_NO_BITS), a value of another
-        kind and a record with a code are not valid; their value is 0."""
-        if self.d_fields is None:
-            raise ValueError("no fields: the stream was not created with select=[...]")
-        if dtype not in (torch.int64, torch.float64):
-            raise ValueError("dtype must be torch.int64 or torch.float64")
-        return number_column(self.d_fields[self.paths.index(path_or_index)], dtype)
 
     def documents(self):
         """A ``Document`` per complete document, None for one with a verdict code (its code: ``d_doc_tapes`` / ``d_verdicts``).

@@ -523,3 +523,80 @@ def test_document_stream_where(dev):
     assert windows >= 4 and seen == len(docs) and kept_in_all > 40
     assert docs[47] is None and passes(json.loads(lines[47].replace(b"[tru]", b"[]")))
     assert any(passes(d) and b"\\u006f" in t for d, t in zip(docs, lines))
+
+
+def test_record_views_agree(dev):
+    """The same records through different views give the same columns: 300 generated lines (the rows cross one block of 256)
+    in windows of 16 KiB (about 95 documents each; the arrays are reused) and again as one window (the rows cross the block).
+    Per window: the RowSelection that takes every document in order against
+    the Window, method by method; the ElementFields that selects "" -- each element itself -- against its ListColumn; the
+    values of a map column as a ListColumn, whose text is what json.dumps makes of the entries' values; and the
+    RowSelection that takes no document: columns of length 0, one group without a value, no group when grouped by a path."""
+    import torch
+    from mojo_simdjson_amd.document_stream import DocumentStream, ListColumn
+
+    lines, docs, _ = log_lines(300)
+    data = b"\n".join(lines) + b"\n"
+    paths = ["", "/status", "/latency", "/tags", "/attrs", "/items"]
+    host = lambda t: t.cpu().tolist()
+    pair = lambda c: (host(c[0]), host(c[1]))                                      # values, valid
+    column = lambda c: (host(c[0]), c[1].cpu().numpy().tobytes(), host(c[2]))      # offsets, bytes, valid
+    coded = lambda c: (host(c.codes), c.values(), host(c.first), host(c.valid))
+    per_path = [lambda v, p: v.values(p), lambda v, p: column(v.strings(p)), lambda v, p: column(v.raw(p)),
+                lambda v, p: column(v.raw(p, compact=True)), lambda v, p: coded(v.categories(p)), lambda v, p: pair(v.timestamps(p)),
+                lambda v, p: pair(v.timestamps(p, unit="s")), lambda v, p: pair(v.parsed_numbers(p)),
+                lambda v, p: pair(v.parsed_numbers(p, dtype=torch.int64, keep_numbers=False))]
+    d_data = tvd.upload(dev, data)
+    stream = lambda window: DocumentStream(dev, d_data, len(data), window=window, select=paths)
+    seen = windows = 0
+    for win in (w for window in (16384, 1 << 20) for w in stream(window)):   # (lazily: a window's arrays are the next one's)
+        D = win.n_documents
+        sel = win.take(torch.arange(D, dtype=torch.int32))
+        assert sel.n_rows == D and sel.fields.shape == win.d_fields.shape
+        for p in paths:
+            for f in per_path:
+                assert f(sel, p) == f(win, p), (windows, p)
+            for dtype in (torch.int64, torch.float64):
+                assert pair(sel.number_column(p, dtype)) == pair(win.number_column(p, dtype)), (windows, p)
+        grouped = win.stats(["/latency"], by="/status").to_python()
+        assert sel.stats(["/latency"], by="/status").to_python() == grouped and len(grouped) >= 5
+        assert sel.stats(["/latency", "/status"]).to_python() == win.stats(["/latency", "/status"]).to_python()
+        tags, attrs = win.elements("/tags"), win.entries("/attrs")
+        assert sel.elements("/tags").to_python() == tags.to_python() and sel.entries("/attrs").to_python() == attrs.to_python()
+        assert tags.n_elements > D // 2 and attrs.n_entries > D
+        # each element itself as the one field of the elements
+        ef = tags.select([""])
+        assert ef.n_elements == tags.n_elements and ef.values("") == [x for row in tags.to_python() if row for x in row]
+        for dtype in (torch.int64, torch.float64):
+            assert pair(ef.numbers("", dtype)) == pair(tags.numbers(dtype))
+        assert column(ef.strings("")) == column(tags.strings()) and coded(ef.categories("")) == coded(tags.categories())
+        assert column(ef.raw("")) == column(tags.raw()) and column(ef.raw("", compact=True)) == column(tags.raw(compact=True))
+        assert pair(ef.timestamps("")) == pair(tags.timestamps()) and pair(ef.parsed_numbers("")) == pair(tags.parsed_numbers())
+        assert ef.stats([""]).to_python() == tags.stats().to_python()
+        assert ef.stats([""], per_row=True).to_python() == tags.stats(per_row=True).to_python()
+        # a map column's values as a list column
+        values = attrs.values()
+        assert isinstance(values, ListColumn) and values.parent is attrs and values.n_elements == attrs.n_entries
+        offsets, text, valid = column(values.raw())
+        want = [json.dumps(x, ensure_ascii=False).encode() for row in attrs.to_python() if row is not None for x in row.values()]
+        assert [text[offsets[j]:offsets[j + 1]] for j in range(attrs.n_entries)] == want and valid == [True] * len(want)
+        mine = docs[seen % len(docs):seen % len(docs) + D]
+        assert attrs.to_python() == [d["attrs"] if d is not None and isinstance(d["attrs"], dict) else None for d in mine]
+        # no row at all
+        empty = win.take(torch.zeros(0, dtype=torch.int32))
+        assert empty.n_rows == 0 and empty.fields.shape == (len(paths), 0, 2)
+        for p in paths:
+            assert empty.values(p) == [] and empty.column(p).shape == (0,)
+            for f in per_path[1:4]:
+                assert f(empty, p) == ([0], b"", [])
+            assert coded(empty.categories(p)) == ([], [], [], [])
+            for f in per_path[5:]:
+                assert f(empty, p) == ([], [])
+            assert pair(empty.number_column(p)) == pair(empty.number_column(p, torch.int64)) == ([], [])
+        assert empty.elements("/tags").to_python() == [] and empty.entries("/attrs").to_python() == []
+        alone = empty.stats(["/latency"])
+        assert alone.n_groups == 1 and host(alone.n_values) == [[0]] and host(alone.n_rows) == [0]
+        assert empty.stats(["/latency"], by="/status").to_python() == []
+        seen += D
+        windows += 1
+    assert windows >= 4 and seen == 2 * len(docs) and D == len(docs) > 256
