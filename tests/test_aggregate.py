@@ -58,35 +58,64 @@ def struct_to_device(dev, s):
     return torch.from_numpy(np.frombuffer(bytes(s), dtype=np.uint8).copy()).to(dev.device)
 
 
-def device_aggregate(dev, columns, R, codes, G, capacity, sel_code=0, by_pointer=False, limit=LIMIT):
-    """One call on hand-made records -> (the record tensor's bytes with the canary, the result's bytes)"""
+class Held:
+    """A call's tensors on the device -- the records, the codes, d_n_groups, the record tensor with its canary and the result,
+    the two outputs filled with FILL -- for a caller that keeps them from one call to the next"""
+
+    def __init__(self, dev, columns, codes, capacity):
+        import torch
+
+        columns = tam.as_columns(columns)
+        n_columns, stride = columns.shape
+        self.d_fields = ttd.to_device(dev, columns.reshape(-1)).view(torch.int64).view(n_columns, stride, 2)
+        self.d_codes = None if codes is None else torch.from_numpy(np.ascontiguousarray(codes, dtype=np.int32)).to(dev.device)
+        self.t_groups = torch.empty((n_columns * capacity * 48 + CANARY,), dtype=torch.uint8, device=dev.device)
+        self.t_res = torch.empty((48,), dtype=torch.uint8, device=dev.device)
+        self.d_n = torch.zeros((1,), dtype=torch.int64, device=dev.device)
+        self.refill()
+
+    def refill(self):
+        self.t_groups.fill_(FILL), self.t_res.fill_(FILL)
+
+    def write_rows(self, columns, codes):
+        """The first rows of every column and their codes; what lies behind them stays"""
+        import torch
+
+        columns = tam.as_columns(columns)
+        n = columns.shape[1]
+        self.d_fields[:, :n].copy_(torch.from_numpy(columns.view(np.int64).reshape(columns.shape[0], n, 2).copy()))
+        self.d_codes[:n].copy_(torch.from_numpy(np.ascontiguousarray(codes[:n], dtype=np.int32)))
+
+
+def device_aggregate(dev, columns, R, codes, G, capacity, sel_code=0, by_pointer=False, limit=LIMIT, held=None):
+    """One call on hand-made records -> (the record tensor's bytes with the canary, the result's bytes).  held: the call runs
+    on these tensors as they are, whatever an earlier call left in them, and not on an upload of `columns` and `codes`"""
     import torch
 
-    columns = tam.as_columns(columns)
-    n_columns, stride = columns.shape
-    d_fields = ttd.to_device(dev, columns.reshape(-1)).view(torch.int64).view(n_columns, stride, 2)
-    d_codes = None if codes is None else torch.from_numpy(np.ascontiguousarray(codes, dtype=np.int32)).to(dev.device)
+    h = Held(dev, columns, codes, capacity) if held is None else held
     t_sel = struct_to_device(dev, tcm.select_result(R, sel_code))
-    t_groups = torch.full((n_columns * capacity * 48 + CANARY,), FILL, dtype=torch.uint8, device=dev.device)
-    t_res = torch.full((48,), FILL, dtype=torch.uint8, device=dev.device)
-    d_n = torch.tensor([G], dtype=torch.int64, device=dev.device) if by_pointer else None
+    if by_pointer:
+        h.d_n.fill_(G)
     dev.set_aggregate_limits(limit)
-    res, _ = dev.aggregate(d_fields, t_sel, d_codes, n_groups=0x7777 if by_pointer else G, d_n_groups=d_n, d_groups=t_groups,
-                           groups_capacity=capacity, d_result=t_res, sync=False)
-    assert res is t_res
+    res, _ = dev.aggregate(h.d_fields, t_sel, h.d_codes, n_groups=0x7777 if by_pointer else G, d_n_groups=h.d_n if by_pointer else None,
+                           d_groups=h.t_groups, groups_capacity=capacity, d_result=h.t_res, sync=False)
+    assert res is h.t_res
     torch.cuda.synchronize()
-    return t_groups.cpu().numpy(), t_res.cpu().numpy()
+    return h.t_groups.cpu().numpy(), h.t_res.cpu().numpy()
 
 
-def run_aggregate(dev, atw, columns, R, codes, G, capacity=None, sel_code=0, by_pointer=False, where=None, limits=(LIMIT, 0)):
+def run_aggregate(dev, atw, columns, R, codes, G, capacity=None, sel_code=0, by_pointer=False, where=None, limits=(LIMIT, 0), held=None):
     """The device, with the switch at LIMIT groups and with the LDS path off, against the twin over the whole of the record
-    tensor -> the twin's tam.Agg"""
+    tensor -> the twin's tam.Agg.  held: a Held of these columns and codes, uploaded once for all the limits; its outputs
+    are filled again before every call"""
     capacity = G + 2 if capacity is None else capacity
     want = tam.twin_aggregate(atw, columns, R, codes, G, capacity=capacity, sel_code=sel_code)
     assert want.rc == 0
     want_res = np.frombuffer(bytes(want.res), dtype=np.uint8)
     for limit in limits:
-        groups, res = device_aggregate(dev, columns, R, codes, G, capacity, sel_code, by_pointer, limit)
+        if held is not None:
+            held.refill()
+        groups, res = device_aggregate(dev, columns, R, codes, G, capacity, sel_code, by_pointer, limit, held)
         assert (groups[len(want.groups):] == FILL).all(), (where, limit, "the canary")
         got = _lib.MsjAggregateResult.from_buffer_copy(res.tobytes())
         assert np.array_equal(res, want_res), (where, limit, [(n, getattr(got, n), getattr(want.res, n)) for n, _ in got._fields_])
