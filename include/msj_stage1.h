@@ -1519,7 +1519,7 @@ uint64_t msj_dictionary_workspace_bytes(uint64_t rows);
  * d_fields, d_result == a select result, d_out_select == d_take_select or d_rows_select; alignment (d_fields, d_out 16-byte,
  * d_take 4-byte, the results 8-byte): MSJ_ERR_BAD_ARGUMENT.  Asynchronous on `stream`, safe on ANY arrays.
  * Out of scope: contains / suffix / regex, predicates on dictionary codes, nested boolean expressions (a second call over
- * the taken rows is AND), sorting.
+ * the taken rows is AND).  (Order: msj_sort_rows_device, which takes d_kept as it is.)
  */
 #define MSJ_PRED_FOUND 0u
 #define MSJ_PRED_TYPE 1u
@@ -1753,6 +1753,72 @@ int32_t msj_aggregate_device(msj_ctx *ctx,
 uint64_t msj_aggregate_workspace_bytes(uint64_t capacity, uint64_t groups_capacity, uint32_t n_columns);
 /* TEST AID: the most groups the LDS path takes (0: none; more than 256: MSJ_ERR_BAD_ARGUMENT).  Both paths write the same bytes. */
 int32_t msj_debug_set_aggregate_limits(msj_ctx *ctx, uint32_t lds_groups);
+
+/*
+ * msj_sort_rows_device answers "the ten slowest lines" and "these lines in time order" on the device: the row numbers of
+ * ONE column of msj_field records in the exact numeric order of their values, stable, optionally only the first `limit`.
+ * What it writes is a selection vector -- msj_take_rows_device gathers any columns by it -- so no column, no count and no
+ * key reaches the host.  A cast to double would order 9007199254740993 and 9007199254740992.0 as equal and an int64 above
+ * 2^53 wrongly; this call compares as real numbers.
+ * d_fields: the column (column c of a set of records: d_fields + c * stride); stride: its room; R = d_rows_select->
+ * n_documents, read on the device.  d_rows_in == NULL: the input sequence is the rows 0 .. R-1, N = R.  Otherwise (both
+ * d_rows_in pointers given) it is d_rows_in[0 .. N), N = d_rows_in_select->n_documents read on the device, repeats and any
+ * order allowed -- a filter's d_kept, an earlier call's d_order; an entry at or past R is a row without a value, counted in
+ * n_out_of_range.  A sort by two keys is two calls, the minor key first: the second takes the first's d_order as d_rows_in.
+ * Number value: msj_aggregate_device's rule -- code == 0, type 'l' or 'd', MSJ_FIELD_NO_BITS not set, a 'd' finite.  Every
+ * other record is a row without a value; one with code == 0 and type 'l' / 'd' but no usable bits is counted in n_skipped.
+ * Order: the rows with a value first, ascending by value AS REAL NUMBERS, an int64 against a double exactly (the compare of
+ * MSJ_PRED_NUM_*): 9007199254740993 lies between 9007199254740992.0 and 9007199254740994.0; -0.0, +0.0 and the int64 0 are
+ * equal, 3 and 3.0 are equal.  Equal values keep the order of the input sequence (stable).  MSJ_SORT_DESCENDING reverses
+ * the order of the values only: equal values still keep input order and the rows without a value still come last, in input
+ * order; with MSJ_SORT_VALUES_ONLY they are left out.  The answer is unique, and every output is the same bytes from run
+ * to run.
+ * Outputs: M = n_values with MSJ_SORT_VALUES_ONLY, else N; K = M for limit == 0, else min(limit, M).  d_order[0 .. K): the
+ * first K row numbers of the order (entries of the input sequence, not positions in it); nothing at or past K is written.
+ * d_order_select: NULL, or it receives code = this call's, n_documents = n_found = K, n_paths = 1, n_no_bits = 0 -- what
+ * msj_take_rows_device reads as d_take_select.  capacity: the most input rows the call orders; d_order has room for
+ * capacity entries, or for min(capacity, limit) with limit > 0.
+ * d_result: a code in d_rows_in_select (it wins) or d_rows_select: a zero result with that code, d_order_select the same,
+ * nothing else written.  R > stride, N > capacity or N >= 2^31: MSJ_CAPACITY with n_rows = N (and the flags), nothing else
+ * written.  N == 0: a zero result with the flags.
+ * Arguments, checked in this order: NULL ctx / d_result / d_rows_select; one of d_rows_in / d_rows_in_select without the
+ * other; NULL d_fields with stride > 0, NULL d_order with capacity > 0; an unknown flag: MSJ_ERR_BAD_ARGUMENT.  A stride or
+ * capacity of 2^40 or more: MSJ_CAPACITY.  Then d_result == a select result; d_order_select == one of the two input select
+ * results; d_order overlapping d_rows_in; alignment -- d_fields 16-byte, d_order / d_rows_in 4-byte, the results 8-byte:
+ * MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of them.  Asynchronous on `stream`, no host round trip, workspace in
+ * the context (about 33 bytes per row of capacity).  Safe on ANY arrays: a record is read only at a row below R <= stride,
+ * d_rows_in only below N <= capacity, d_order is written only below K.
+ * Two paths, chosen on the device, the same bytes from both.  The full sort: a least-significant-digit radix sort over a
+ * 75-bit order-preserving key and the null bit (eleven digits; a pass whose digit is the same in every row is skipped, so a
+ * plain int or double column takes at most eight).  The selection, where limit > 0, N >= 16 384 and limit <= N / 8: most-
+ * significant-digit histograms find the key of the K-th row, the rows below it and the first rows that equal it are
+ * compacted in input order and only they are sorted.  msj_debug_set_sort_mode forces either so that tests compare them on
+ * small inputs.
+ * Out of scope: string keys (sort a dictionary's codes, or cast); nulls first; sorting msj_aggregate records; top-k per
+ * group; merging sorted windows.
+ */
+#define MSJ_SORT_DESCENDING  1u
+#define MSJ_SORT_VALUES_ONLY 2u   /* rows without a number value are left out instead of placed last */
+typedef struct msj_sort_rows_result {   /* 48 bytes */
+    int32_t  code;            /* 0; MSJ_CAPACITY; or the code of d_rows_in_select (it wins) / d_rows_select */
+    uint32_t flags;           /* the call's flags */
+    uint64_t n_rows;          /* N, the rows that were ordered */
+    uint64_t n_values;        /* of them, rows whose record is a number value */
+    uint64_t n_written;       /* K, the entries of d_order */
+    uint64_t n_skipped;       /* 'l' / 'd' records without usable bits (MSJ_FIELD_NO_BITS, NaN, infinity) */
+    uint64_t n_out_of_range;  /* entries of d_rows_in at or past R */
+} msj_sort_rows_result;
+int32_t msj_sort_rows_device(msj_ctx *ctx,
+        const msj_field *d_fields, uint64_t stride, const msj_select_documents_result *d_rows_select,
+        const uint32_t *d_rows_in, const msj_select_documents_result *d_rows_in_select,
+        uint32_t flags, uint64_t limit,
+        uint32_t *d_order, uint64_t capacity,
+        msj_sort_rows_result *d_result, msj_select_documents_result *d_order_select, void *stream);
+/* Device workspace of one msj_sort_rows_device call (the context keeps it). */
+uint64_t msj_sort_rows_workspace_bytes(uint64_t capacity);
+/* TEST AID: 0 the path chosen on the device, 1 always the full sort, 2 always the selection, carried to the key's last digit
+ * (more than 2: MSJ_ERR_BAD_ARGUMENT).  Both paths write the same bytes. */
+int32_t msj_debug_set_sort_mode(msj_ctx *ctx, uint32_t mode);
 
 /*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors

@@ -205,6 +205,17 @@ class MsjAggregateResult(ctypes.Structure):
 AGG_INT_OVERFLOW, AGG_INFINITE = 1, 2
 AGG_MAX_LDS_GROUPS = 256
 
+class MsjSortRowsResult(ctypes.Structure):
+    """``msj_sort_rows_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_values", ctypes.c_uint64),
+                ("n_written", ctypes.c_uint64), ("n_skipped", ctypes.c_uint64), ("n_out_of_range", ctypes.c_uint64)]
+
+
+# msj_sort_rows_device: flags; msj_debug_set_sort_mode
+SORT_DESCENDING, SORT_VALUES_ONLY = 1, 2
+SORT_MODE_AUTO, SORT_MODE_FULL, SORT_MODE_SELECT = 0, 1, 2
+
 # msj_cast_strings_device: kind, unit, flags; msj_debug_set_cast_fetch
 CAST_TIMESTAMP, CAST_NUMBER = 1, 2
 CAST_KINDS = {"timestamp": CAST_TIMESTAMP, "number": CAST_NUMBER}
@@ -453,6 +464,14 @@ def load():
     lib.msj_aggregate_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
     lib.msj_debug_set_aggregate_limits.restype = ctypes.c_int32
     lib.msj_debug_set_aggregate_limits.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    lib.msj_sort_rows_device.restype = ctypes.c_int32
+    lib.msj_sort_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]
+    lib.msj_sort_rows_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_sort_rows_workspace_bytes.argtypes = [ctypes.c_uint64]
+    lib.msj_debug_set_sort_mode.restype = ctypes.c_int32
+    lib.msj_debug_set_sort_mode.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

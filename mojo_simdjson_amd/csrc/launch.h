@@ -1,7 +1,7 @@
 // launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 /
 // f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
 // validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
-// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip.  Every launcher and every internal workspace size is declared
+// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip.  Every launcher and every internal workspace size is declared
 // here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
 // compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
 // (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.
@@ -203,3 +203,11 @@ constexpr uint32_t kAggregateMaxLdsGroups = 256;
 extern "C" int msj_launch_aggregate(const msj_field *d_fields, uint64_t stride, uint32_t n_columns, const msj_select_documents_result *d_rows_select,
                                     const int32_t *d_codes, uint64_t n_groups, const uint64_t *d_n_groups, msj_aggregate *d_groups,
                                     uint64_t groups_capacity, uint32_t lds_groups, msj_aggregate_result *d_result, void *d_ws, void *stream);
+
+// ---- sort_rows_kernel.hip ----
+// d_fields: ONE column, `stride` its room; d_rows_in / d_rows_in_select: both or neither; flags: checked by the caller;
+// mode: 0 the path chosen on the device, 1 always the full sort, 2 always the selection (msj_debug_set_sort_mode)
+extern "C" int msj_launch_sort_rows(const msj_field *d_fields, uint64_t stride, const msj_select_documents_result *d_rows_select,
+                                    const uint32_t *d_rows_in, const msj_select_documents_result *d_rows_in_select, uint32_t flags, uint64_t limit,
+                                    uint32_t mode, uint32_t *d_order, uint64_t capacity, msj_sort_rows_result *d_result,
+                                    msj_select_documents_result *d_order_select, void *d_ws, void *stream);

@@ -658,6 +658,37 @@ int32_t msj_debug_set_aggregate_limits(msj_ctx *ctx, uint32_t lds_groups) {
     return MSJ_SUCCESS;
 }
 
+int32_t msj_sort_rows_device(msj_ctx *ctx, const msj_field *d_fields, uint64_t stride, const msj_select_documents_result *d_rows_select,
+                             const uint32_t *d_rows_in, const msj_select_documents_result *d_rows_in_select, uint32_t flags, uint64_t limit,
+                             uint32_t *d_order, uint64_t capacity, msj_sort_rows_result *d_result, msj_select_documents_result *d_order_select,
+                             void *stream) {
+    if (!ctx || !d_result || !d_rows_select) return MSJ_ERR_BAD_ARGUMENT;
+    if ((d_rows_in == nullptr) != (d_rows_in_select == nullptr)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((stride > 0 && !d_fields) || (capacity > 0 && !d_order)) return MSJ_ERR_BAD_ARGUMENT;
+    if (flags & ~(MSJ_SORT_DESCENDING | MSJ_SORT_VALUES_ONLY)) return MSJ_ERR_BAD_ARGUMENT;
+    if (stride >= (1ull << 40) || capacity >= (1ull << 40)) return MSJ_CAPACITY;  // (the extents below: no overflow)
+    if ((const void *)d_result == (const void *)d_rows_select || (const void *)d_result == (const void *)d_rows_in_select ||
+        (const void *)d_result == (const void *)d_order_select)
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (d_order_select && (d_order_select == d_rows_select || d_order_select == d_rows_in_select)) return MSJ_ERR_BAD_ARGUMENT;
+    if (d_order && d_rows_in) {  // the order may not be written over the rows it is read from
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_rows_in), b = reinterpret_cast<uintptr_t>(d_order);
+        const uint64_t b_rows = limit > 0 && limit < capacity ? limit : capacity;
+        if (a < b + 4 * b_rows && b < a + 4 * capacity) return MSJ_ERR_BAD_ARGUMENT;
+    }
+    if (!aligned(d_fields, 16) || !all_aligned(4, d_order, d_rows_in) || !all_aligned(8, d_rows_select, d_rows_in_select, d_result, d_order_select))
+        return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->sort_ws, msj_sort_rows_workspace_bytes(capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_sort_rows(d_fields, stride, d_rows_select, d_rows_in, d_rows_in_select, flags, limit, ctx->sort_mode, d_order, capacity,
+                                         d_result, d_order_select, ctx->sort_ws.p, stream));
+}
+int32_t msj_debug_set_sort_mode(msj_ctx *ctx, uint32_t mode) {
+    if (!ctx || mode > 2u) return MSJ_ERR_BAD_ARGUMENT;
+    ctx->sort_mode = mode;
+    return MSJ_SUCCESS;
+}
+
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {
     if (!ctx) return MSJ_ERR_BAD_ARGUMENT;
     ctx->tok_opts.lds_limit = lds_limit_bytes;

@@ -879,6 +879,51 @@ class Stage1Device:
         if self.lib.msj_debug_set_aggregate_limits(self.ctx, int(lds_groups)) != 0:
             raise ValueError(f"lds_groups lies in 0..{_lib.AGG_MAX_LDS_GROUPS}: {lds_groups!r}")
 
+    def sort_rows(self, d_fields, d_rows_select, d_rows_in=None, d_rows_in_select=None, descending=False, values_only=False, limit=0,
+                  capacity=None, d_order=None, d_result=None, d_order_select=None, sync=True):
+        """Row numbers in the exact numeric order of one column's values (``msj_sort_rows_device``), stable, all on the
+        device.  d_fields: int64 of shape (rows, 2), ONE column of ``msj_field`` records -- a path of ``select_documents``,
+        cast strings, taken rows; d_rows_select: the device ``msj_select_documents_result`` that counts its rows, read on
+        the device.  d_rows_in / d_rows_in_select: an int32 tensor of row numbers to order instead of all the rows, in any
+        order, repeats allowed, with the device select result that counts them -- ``filter_rows``' d_kept and
+        d_kept_select, or an earlier call's d_order and d_order_select for the major key of a two-key sort (the sort is
+        stable).  An int64 is compared with a double as real numbers; equal values keep the input order; rows without a
+        number value come last in input order, or are left out with values_only.  descending reverses the values' order
+        only.  limit: only the first so many row numbers are written (0: all).  capacity: the most input rows (default:
+        the entries of d_rows_in, or the rows of d_fields).  d_order: int32 tensor of capacity entries -- min(capacity,
+        limit) with a limit -- (default: a new one); d_order_select: uint8[48] that receives the
+        ``msj_select_documents_result`` counting the entries written (default: a new one): the pair is what ``take_rows``
+        takes as d_take / d_take_select.  Returns (``MsjSortRowsResult``, d_order, d_order_select) -- blocking for the
+        48-byte result; with sync=False the device tensor that holds it, nothing waited for."""
+        _check_records(d_fields, "the records")
+        if (d_rows_in is None) != (d_rows_in_select is None):
+            raise ValueError("d_rows_in and d_rows_in_select come together")
+        if d_rows_in is not None and (d_rows_in.dtype != torch.int32 or d_rows_in.stride(-1) != 1):
+            raise ValueError("d_rows_in is a contiguous int32 tensor")
+        stride = d_fields.shape[0]
+        if capacity is None:
+            capacity = d_rows_in.numel() if d_rows_in is not None else stride
+        capacity, limit = int(capacity), int(limit)
+        room = min(capacity, limit) if limit > 0 else capacity
+        if d_order is None:
+            d_order = torch.empty((max(room, 1),), dtype=torch.int32, device=self.device)
+        if d_order.dtype != torch.int32 or d_order.numel() < room or (d_rows_in is not None and d_rows_in.numel() < capacity):
+            raise ValueError("d_order is an int32 tensor with room for the rows written, d_rows_in has capacity entries")
+        d_result, d_order_select = self._result(d_result), self._result(d_order_select)
+        flags = (_lib.SORT_DESCENDING if descending else 0) | (_lib.SORT_VALUES_ONLY if values_only else 0)
+        rc = self.lib.msj_sort_rows_device(self.ctx, _ptr(d_fields), stride, _ptr(d_rows_select), _opt(d_rows_in), _opt(d_rows_in_select), flags,
+                                           limit, _ptr(d_order), capacity, _ptr(d_result), _ptr(d_order_select), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_sort_rows_device failed: {rc}")
+        res = _lib.MsjSortRowsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_order, d_order_select
+
+    def set_sort_mode(self, mode=_lib.SORT_MODE_AUTO):
+        """Test hook: the path ``sort_rows`` takes -- 0 chosen on the device, 1 always the full sort, 2 always the
+        selection.  The order does not change."""
+        if self.lib.msj_debug_set_sort_mode(self.ctx, int(mode)) != 0:
+            raise ValueError(f"mode is 0, 1 or 2: {mode!r}")
+
     def array_column(self, d_idx, n, d_type, d_depth, d_match, d_end, d_flags, d_doc_first, d_docs, d_fields, p, d_select_result,
                      d_numbers=None, numbers_capacity=0, d_numbers_result=None, d_offsets=None, d_valid=None, d_elements=None,
                      capacity=None, elements_capacity=None, elements=True, d_result=None, d_elements_select=None, sync=True):

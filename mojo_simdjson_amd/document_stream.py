@@ -397,6 +397,44 @@ def _stats(window, d_fields, d_select, rows, columns, pointers, cast, keys, d_co
     return GroupStats(keys, pointers, records, res)
 
 
+def _sort_keys(keys, index, descending=False):
+    """A path or index, (path, "asc" | "desc"), or a list of them, major key first -> [(column number, descending)]"""
+    def one(key):
+        if isinstance(key, tuple):
+            if len(key) != 2 or key[1] not in ("asc", "desc"):
+                raise ValueError(f'a sort key is a path or (path, "asc" | "desc"): {key!r}')
+            return index(key[0]), key[1] == "desc"
+        return index(key), bool(descending)
+
+    out = [one(k) for k in keys] if isinstance(keys, list) else [one(keys)]
+    if not out:
+        raise ValueError("an order by no key")
+    return out
+
+
+def _order(window, d_fields, d_select, rows, keys, limit, values_only, cast, what):
+    """``sort_rows`` over `rows` records per column of d_fields (int64[n_columns, rows, 2]), one call per key, the minor key
+    first and each call's order the next one's d_rows_in (the sort is stable); the last call gets the limit and values_only.
+    keys: [(column number, descending)], major first; cast: {column number: spec}.  -> (order int32[K], the uint8[48] select
+    result that counts it).  A code of an earlier call reaches the last one through that select result: only the last
+    call's 48-byte result comes to the host."""
+    w = window
+    if limit is not None and int(limit) <= 0:
+        raise ValueError(f"limit is None or at least 1: {limit!r}")
+    d_in = d_in_select = None
+    for j, (c, descending) in enumerate(reversed(keys)):
+        last = j == len(keys) - 1
+        column = d_fields[c]
+        if c in cast and rows:
+            kind, unit = _cast_spec(cast[c])
+            column = _cast(w, column, d_select, rows, kind, unit, kind == "number", what)[0]
+        res, d_in, d_in_select = w.dev.sort_rows(_or_blank(column, rows).contiguous(), d_select, d_in, d_in_select, descending=descending,
+                                                 values_only=values_only and last, limit=int(limit or 0) if last else 0, capacity=rows, sync=last)
+    if res.code != 0 or res.n_rows != rows:
+        raise DocumentStreamError(int(res.code), f"window at {w.base}: {what} could not be ordered")
+    return d_in[:int(res.n_written)], d_in_select
+
+
 def _rows_of_elements(offsets, n_elements):
     """The row of every element of a list column, int32[n_elements], from its offsets (torch)"""
     at = torch.arange(n_elements, dtype=torch.int64, device=offsets.device)
@@ -556,6 +594,19 @@ class _Records:
     def _taken(self, d_take, d_take_select, n_take):
         """``_take`` of these records by n_take row numbers"""
         return _take(self._window, self._records, self.d_select, d_take, d_take_select, n_take, self._rows_are)
+
+    def order(self, keys, limit=None, cast=None, values_only=False, descending=False):
+        """The row numbers in the exact numeric order of one or more paths ON THE DEVICE (``msj_sort_rows_device``) ->
+        (order int32[K], the uint8[48] ``msj_select_documents_result`` that counts it): what ``take_rows`` takes as d_take
+        and d_take_select.  keys: a path or index, (path, "desc"), or a list of them, the major key first; descending: the
+        direction of the keys that name none.  An int64 is compared with a double as real numbers -- 9007199254740993 lies
+        between 9007199254740992.0 and 9007199254740994.0 --, equal values keep their order, rows without a number value
+        come last (values_only: are left out).  limit: only the first so many.  cast: ``{"/ts": ("timestamp", "ns")}`` as
+        in ``where``, so that ``order("/ts", cast={"/ts": ("timestamp", "ns")})`` is time order.  Only the last call's
+        48-byte result comes to the host."""
+        fields, index = self._records, self.paths.index
+        return _order(self._window, fields, self.d_select, fields.shape[1], _sort_keys(keys, index, descending), limit, values_only,
+                      {index(k): v for k, v in (cast or {}).items()}, self._rows_are)
 
 
 class _Unnamed:
@@ -819,9 +870,10 @@ class ElementFields(_Records):
 
 
 class RowSelection(_Records):
-    """Rows of a window chosen by predicate or by number ON THE DEVICE (``Window.where``, ``Window.take``): the rows are the
-    chosen documents.  keep bool[D]: the mask over the window's documents (None for ``Window.take``); rows int32[n_rows]: the
-    chosen documents' numbers -- ascending from ``where``; fields int64[n_paths, n_rows, 2]: their records, each path a
+    """Rows of a window chosen by predicate, by number or by order ON THE DEVICE (``Window.where``, ``Window.take``,
+    ``order_by``): the rows are the chosen documents.  keep bool[D]: the mask over the window's documents (None for
+    ``Window.take`` and ``order_by``); rows int32[n_rows]: the chosen documents' numbers -- ascending from ``where``, in the
+    order asked for from ``order_by``; fields int64[n_paths, n_rows, 2]: their records, each path a
     column; d_select uint8[48], the ``msj_select_documents_result`` that goes with them.  The methods mean what they mean on
     ``Window``, over the chosen rows: ``raw("", compact=True)`` is the chosen documents as minified NDJSON lines, and
     ``elements`` and ``entries`` give a row per chosen row.  Like every array a Window carries, the window's own arrays are
@@ -840,6 +892,13 @@ class RowSelection(_Records):
         """The numbers of one path as ``Window.number_column`` gives them: (values dtype[n_rows], valid bool[n_rows])."""
         return self._number_column(path_or_index, dtype)
 
+    def order_by(self, keys, descending=False, limit=None, cast=None, values_only=False):
+        """The chosen rows in the order of one or more paths ON THE DEVICE, as ``Window.order_by`` -> ``RowSelection`` whose
+        rows are the window's document numbers in that order; keep is None."""
+        order, d_order_select = self.order(keys, limit, cast, values_only, descending)
+        fields, d_fsel = self._taken(_or_blank(order, order.shape[0]), d_order_select, order.shape[0])
+        return RowSelection(self.window, None, self.rows[order.to(torch.int64)], fields, d_fsel)
+
 
 def _skip_flag(n):
     return (n & 15) << 24
@@ -855,8 +914,8 @@ class DocumentStreamError(RuntimeError):
 class Window(_Records):
     """One window of complete documents, as ``DocumentStream`` yields it.  With select=[...] it is a record view whose rows are
     the window's D = n_documents complete documents: ``column``, ``values``, ``number_column``, ``strings``, ``categories``,
-    ``raw``, ``timestamps``, ``parsed_numbers``, ``elements``, ``entries`` and ``stats`` by path, and ``cast``, ``where`` and
-    ``take``.  Every array a Window carries is reused by the next window."""
+    ``raw``, ``timestamps``, ``parsed_numbers``, ``elements``, ``entries``, ``stats`` and ``order`` by path, and ``cast``,
+    ``where``, ``order_by`` and ``take``.  Every array a Window carries is reused by the next window."""
     base: int           # byte offset of the window in the stream (16-byte aligned)
     length: int         # bytes indexed from there
     consumed: int       # bytes that belong to this window's complete documents (the next window starts at base + consumed)
@@ -953,6 +1012,16 @@ class Window(_Records):
         keep, kept, d_kept_select, _ = self._filtered(specs, any, cast)
         fields, d_fsel = self._taken(kept, d_kept_select, kept.shape[0])
         return RowSelection(self, keep, kept, fields, d_fsel)
+
+    def order_by(self, keys, descending=False, limit=None, cast=None, values_only=False):
+        """The documents in the exact numeric order of one or more paths ON THE DEVICE (``msj_sort_rows_device``,
+        ``msj_take_rows_device``) -> ``RowSelection`` with keep None and rows the documents' numbers in that order:
+        ``win.order_by("/latency_ms", descending=True, limit=10).raw("", compact=True)`` is the ten slowest lines as
+        NDJSON, and ``win.order_by("/ts", cast={"/ts": ("timestamp", "ns")})`` the lines in time order, without the window,
+        the column or a count reaching the host.  keys, descending, limit, cast, values_only: as for ``order``."""
+        order, d_order_select = self.order(keys, limit, cast, values_only, descending)
+        fields, d_fsel = self._taken(_or_blank(order, order.shape[0]), d_order_select, order.shape[0])
+        return RowSelection(self, None, order, fields, d_fsel)
 
     def take(self, rows):
         """The documents with the given numbers ON THE DEVICE (``msj_take_rows_device``) -> ``RowSelection``.  rows: an int32
