@@ -66,12 +66,11 @@ struct Call {
     uint32_t lds_groups;
 };
 
-static inline uint64_t workspace_bytes(uint64_t groups_capacity, uint32_t n_columns) {
-    return sizeof(State) + sizeof(Acc) * groups_capacity * n_columns + 64;
-}
-static inline Work layout(void *ws) {
-    uint8_t *p = static_cast<uint8_t *>(ws);
-    return Work{reinterpret_cast<State *>(p), reinterpret_cast<Acc *>(p + sizeof(State))};
+static inline Work layout(msj_carver &c, uint64_t groups_capacity, uint32_t n_columns) {
+    Work w;
+    w.st = c.take<State>(1);
+    w.acc = c.take<Acc>(groups_capacity * n_columns);
+    return w;
 }
 
 // what every kernel reads of the call: R rows in `blocks` blocks, G groups.  stop: nothing but the result is written
@@ -299,7 +298,7 @@ __global__ void ag_result(const Call call, const Work w, msj_aggregate_result *_
 
 extern "C" uint64_t msj_aggregate_workspace_bytes(uint64_t capacity, uint64_t groups_capacity, uint32_t n_columns) {
     (void)capacity;  // (nothing is kept per row)
-    return msj_agg::workspace_bytes(groups_capacity, n_columns);
+    return msj_measure(msj_agg::layout, groups_capacity, n_columns) + 64;
 }
 
 extern "C" int msj_launch_aggregate(const msj_field *d_fields, uint64_t stride, uint32_t n_columns, const msj_select_documents_result *d_rows_select,
@@ -308,7 +307,7 @@ extern "C" int msj_launch_aggregate(const msj_field *d_fields, uint64_t stride, 
     using namespace msj_agg;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Call call{d_fields, stride, d_rows_select, d_codes, n_groups, d_n_groups, groups_capacity, lds_groups < kMaxLdsGroups ? lds_groups : kMaxLdsGroups};
-    const Work w = layout(d_ws);
+    const Work w = msj_place(layout, d_ws, groups_capacity, n_columns);
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(State), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint64_t most = most_rows(stride), nb = (most + kRows - 1) / kRows;

@@ -50,12 +50,11 @@ struct ColWork {
 };
 
 __host__ __device__ inline uint64_t most_rows(uint64_t n, uint64_t capacity) { return n < capacity ? n : capacity; }
-static inline ColWork col_layout(void *ws, uint64_t n, uint64_t capacity) {
-    uint8_t *p = static_cast<uint8_t *>(ws);
+static inline ColWork col_layout(msj_carver &c, uint64_t n, uint64_t capacity) {
     ColWork w;
-    w.st = reinterpret_cast<ColState *>(p);
-    w.desc = reinterpret_cast<Desc *>(p + sizeof(ColState));
-    w.bsum = reinterpret_cast<uint32_t *>(p + sizeof(ColState) + sizeof(Desc) * most_rows(n, capacity));
+    w.st = c.take<ColState>(1);
+    w.desc = c.take<Desc>(most_rows(n, capacity));
+    w.bsum = c.take<uint32_t>(token_blocks(n));
     return w;
 }
 
@@ -206,10 +205,7 @@ __global__ __launch_bounds__(kThreads) void ac_emit(const uint32_t *__restrict__
 
 }  // namespace msj_acol
 
-extern "C" uint64_t msj_array_column_workspace_bytes(uint64_t n, uint64_t capacity) {
-    using namespace msj_acol;
-    return sizeof(ColState) + sizeof(Desc) * most_rows(n, capacity) + up16(4 * token_blocks(n)) + 64;
-}
+extern "C" uint64_t msj_array_column_workspace_bytes(uint64_t n, uint64_t capacity) { return msj_measure(msj_acol::col_layout, n, capacity) + 64; }
 
 extern "C" int msj_launch_array_column(const msj_token_view &t, const msj_split_view &sp, const msj_number_view &nv, const msj_field *d_column,
                                        const msj_select_documents_result *d_select, uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity,
@@ -218,7 +214,7 @@ extern "C" int msj_launch_array_column(const msj_token_view &t, const msj_split_
     using namespace msj_acol;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t n = t.n;
-    const ColWork w = col_layout(d_ws, n, capacity);
+    const ColWork w = msj_place(col_layout, d_ws, n, capacity);
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(ColState), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint32_t rb = row_grid_blocks(most_rows(n, capacity)), nb = (uint32_t)token_blocks(n);

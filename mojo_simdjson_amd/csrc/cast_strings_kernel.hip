@@ -37,7 +37,7 @@ using namespace msj::wave;
 using msj::val::ByteReader;
 using msj_bytes::Head, msj_bytes::load_head;
 using msj_bytes::kGridBlocks, msj_bytes::kRows, msj_bytes::most_rows;
-using msj_tape::kThreads, msj_tape::kWaves, msj_tape::up16;
+using msj_tape::kThreads, msj_tape::kWaves;
 using msj_tdocs::load_field, msj_tdocs::store_field;
 
 static_assert(sizeof(msj_cast_strings_result) == 48 && sizeof(msj_field) == 16, "ABI");
@@ -61,10 +61,11 @@ struct Call {
     uint32_t kind, unit, flags;
 };
 
-static inline uint64_t workspace_bytes(uint64_t capacity) { return sizeof(State) + up16(4 * most_rows(capacity)) + 64; }
-static inline Work layout(void *ws) {
-    uint8_t *p = static_cast<uint8_t *>(ws);
-    return Work{reinterpret_cast<State *>(p), reinterpret_cast<uint32_t *>(p + sizeof(State))};
+static inline Work layout(msj_carver &c, uint64_t capacity) {
+    Work w;
+    w.st = c.take<State>(1);
+    w.list = c.take<uint32_t>(most_rows(capacity));
+    return w;
 }
 
 constexpr uint32_t kWin = 64;              // bytes of a body's window in LDS, from its 16-byte line on: 15 + 35 fit
@@ -233,7 +234,7 @@ static inline void launch_cast(bool window, dim3 grid, hipStream_t s, const uint
 
 }  // namespace msj_cast
 
-extern "C" uint64_t msj_cast_strings_workspace_bytes(uint64_t capacity) { return msj_cast::workspace_bytes(capacity); }
+extern "C" uint64_t msj_cast_strings_workspace_bytes(uint64_t capacity) { return msj_measure(msj_cast::layout, capacity) + 64; }
 
 extern "C" int msj_launch_cast_strings(const uint8_t *d_buf, uint64_t len, const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
                                        uint32_t kind, uint32_t unit, uint32_t flags, uint32_t fetch, msj_field *d_out, uint64_t capacity,
@@ -242,7 +243,7 @@ extern "C" int msj_launch_cast_strings(const uint8_t *d_buf, uint64_t len, const
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Rows rows{d_rows, d_rows_select, capacity};
     const Call call{kind, unit, flags};
-    const Work w = layout(d_ws);
+    const Work w = msj_place(layout, d_ws, capacity);
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(State), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint64_t most = most_rows(capacity), nb = (most + kRows - 1) / kRows;

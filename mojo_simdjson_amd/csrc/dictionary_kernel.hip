@@ -49,7 +49,7 @@ namespace msj_dict {
 using namespace msj::dict;
 using namespace msj::wave;
 using msj_bytes::kGridBlocks, msj_bytes::kRows, msj_bytes::most_rows;
-using msj_tape::block_scan, msj_tape::kThreads, msj_tape::kWaves, msj_tape::up16;
+using msj_tape::block_scan, msj_tape::kThreads, msj_tape::kWaves;
 
 constexpr uint64_t kLongRow = 512;    // a row of more bytes than this is hashed and compared by a wave, not by a lane
 constexpr uint32_t kLongCap = 1024;   // entries of the list of long rows
@@ -93,21 +93,16 @@ struct Dict {
     uint64_t bytes_capacity;
 };
 
-static inline uint64_t workspace_bytes(uint64_t rows_in) {
+static inline Work layout(msj_carver &c, uint64_t rows_in) {
     const uint64_t rows = most_rows(rows_in);
-    return sizeof(State) + up16(8 * rows) + up16(4 * rows) + up16(4 * table_slots(rows)) + 2 * up16(8 * (rows / kRows + 1)) + up16(4 * kLongCap) + 64;
-}
-static inline Work layout(void *ws, uint64_t rows_in) {
-    const uint64_t rows = most_rows(rows_in);
-    uint8_t *p = static_cast<uint8_t *>(ws);
     Work w;
-    w.st = reinterpret_cast<State *>(p), p += sizeof(State);
-    w.hash = reinterpret_cast<uint64_t *>(p), p += up16(8 * rows);
-    w.slot = reinterpret_cast<uint32_t *>(p), p += up16(4 * rows);
-    w.table = reinterpret_cast<uint32_t *>(p), p += up16(4 * table_slots(rows));
-    w.bcnt = reinterpret_cast<uint64_t *>(p), p += up16(8 * (rows / kRows + 1));
-    w.blen = reinterpret_cast<uint64_t *>(p), p += up16(8 * (rows / kRows + 1));
-    w.list = reinterpret_cast<uint32_t *>(p);
+    w.st = c.take<State>(1);
+    w.hash = c.take<uint64_t>(rows);
+    w.slot = c.take<uint32_t>(rows);
+    w.table = c.take<uint32_t>(table_slots(rows));
+    w.bcnt = c.take<uint64_t>(rows / kRows + 1);
+    w.blen = c.take<uint64_t>(rows / kRows + 1);
+    w.list = c.take<uint32_t>(kLongCap);
     return w;
 }
 
@@ -411,7 +406,7 @@ __global__ __launch_bounds__(kThreads) void dc_copy(const Col c, const Work w, c
 
 }  // namespace msj_dict
 
-extern "C" uint64_t msj_dictionary_workspace_bytes(uint64_t rows) { return msj_dict::workspace_bytes(rows); }
+extern "C" uint64_t msj_dictionary_workspace_bytes(uint64_t rows) { return msj_measure(msj_dict::layout, rows) + 64; }
 
 extern "C" int msj_launch_dictionary(const uint64_t *d_offsets, const uint8_t *d_valid, uint64_t rows, const uint64_t *d_n_rows,
                                      const uint8_t *d_bytes, uint64_t bytes_len, int32_t *d_codes, uint64_t *d_dict_offsets,
@@ -421,7 +416,7 @@ extern "C" int msj_launch_dictionary(const uint64_t *d_offsets, const uint8_t *d
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Col c{d_offsets, d_valid, rows, d_n_rows, d_bytes, bytes_len, flags};
     const Dict d{d_dict_offsets, d_dict_first, dict_capacity, d_dict_bytes, dict_bytes_capacity};
-    const Work w = layout(d_ws, rows);
+    const Work w = msj_place(layout, d_ws, rows);
     hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(State), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint64_t nb = (most_rows(rows) + kRows - 1) / kRows;  // (R < 2^31 whatever `rows` says)

@@ -247,13 +247,23 @@ __global__ __launch_bounds__(kThreads) void doc_write(const uint8_t *__restrict_
     }
 }
 
+struct Work {
+    uint4 *agg, *super_agg;      // per block, per run of kSuper blocks
+    uint32_t *off, *super_off;
+};
+static inline Work layout(msj_carver &c, uint64_t n) {
+    const uint64_t nb = (n + kBlock - 1) / kBlock, ns = (nb + kSuper - 1) / kSuper;
+    Work w;
+    w.agg = c.take<uint4>(nb ? nb : 1);
+    w.super_agg = c.take<uint4>(ns ? ns : 1);
+    w.off = c.take<uint32_t>(nb ? nb : 1, 4);
+    w.super_off = c.take<uint32_t>(ns ? ns : 1, 4);
+    return w;
+}
+
 }  // namespace msj_docs
 
-extern "C" uint64_t msj_documents_workspace_bytes(uint64_t n) {
-    const uint64_t nb = (n + msj_docs::kBlock - 1) / msj_docs::kBlock;
-    const uint64_t ns = (nb + msj_docs::kSuper - 1) / msj_docs::kSuper;
-    return ((nb ? nb : 1) + (ns ? ns : 1)) * (sizeof(uint4) + sizeof(uint32_t)) + 64;
-}
+extern "C" uint64_t msj_documents_workspace_bytes(uint64_t n) { return msj_measure(msj_docs::layout, n) + 64; }
 
 extern "C" int msj_launch_documents(const uint8_t *d_buf, uint64_t len, int is_final, const uint32_t *d_idx, uint64_t n,
                                     const uint8_t *d_type, const int32_t *d_depth, const msj_carry *d_carry, uint32_t *d_doc_first, uint64_t capacity,
@@ -264,14 +274,12 @@ extern "C" int msj_launch_documents(const uint8_t *d_buf, uint64_t len, int is_f
     if (nb64 > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
     const uint32_t nb = (uint32_t)nb64;
     const uint32_t ns = (nb + kSuper - 1u) / kSuper;
-    // per block; d_block_agg: already written by the token pre-pass for exactly these arrays
-    const uint4 *agg = d_block_agg ? static_cast<const uint4 *>(d_block_agg) : static_cast<const uint4 *>(d_ws);
-    uint4 *super_agg = static_cast<uint4 *>(d_ws) + (nb ? nb : 1);  // per run of kSuper blocks
-    uint32_t *off = reinterpret_cast<uint32_t *>(super_agg + (ns ? ns : 1));
-    uint32_t *super_off = off + (nb ? nb : 1);
-    if (nb && !d_block_agg) hipLaunchKernelGGL(doc_count, dim3(nb), dim3(kThreads), 0, s, d_type, d_depth, n, static_cast<uint4 *>(d_ws));
-    if (nb) hipLaunchKernelGGL(doc_scan_super, dim3(ns), dim3(256), 0, s, agg, nb, off, super_agg);
-    hipLaunchKernelGGL(doc_scan, dim3(1), dim3(1024), 0, s, super_agg, ns, super_off, d_type, d_idx, n, d_buf, len, is_final, d_carry, d_result);
-    if (nb) hipLaunchKernelGGL(doc_write, dim3(nb), dim3(kThreads), 0, s, d_type, d_depth, n, off, super_off, d_doc_first, capacity);
+    const Work w = msj_place(layout, d_ws, n);
+    // d_block_agg: already written by the token pre-pass for exactly these arrays
+    const uint4 *agg = d_block_agg ? static_cast<const uint4 *>(d_block_agg) : w.agg;
+    if (nb && !d_block_agg) hipLaunchKernelGGL(doc_count, dim3(nb), dim3(kThreads), 0, s, d_type, d_depth, n, w.agg);
+    if (nb) hipLaunchKernelGGL(doc_scan_super, dim3(ns), dim3(256), 0, s, agg, nb, w.off, w.super_agg);
+    hipLaunchKernelGGL(doc_scan, dim3(1), dim3(1024), 0, s, w.super_agg, ns, w.super_off, d_type, d_idx, n, d_buf, len, is_final, d_carry, d_result);
+    if (nb) hipLaunchKernelGGL(doc_write, dim3(nb), dim3(kThreads), 0, s, d_type, d_depth, n, w.off, w.super_off, d_doc_first, capacity);
     return (int)hipGetLastError();
 }

@@ -36,7 +36,7 @@ using namespace msj::frows;
 using namespace msj::wave;
 using msj::val::ByteReader;
 using msj_bytes::kGridBlocks, msj_bytes::kRows, msj_bytes::most_rows;
-using msj_tape::kThreads, msj_tape::kWaves, msj_tape::up16;
+using msj_tape::kThreads, msj_tape::kWaves;
 using msj_tdocs::load_field, msj_tdocs::store_field;
 
 static_assert(sizeof(msj_filter_rows_result) == 48 && sizeof(msj_take_rows_result) == 48 && sizeof(msj_field) == 16, "ABI");
@@ -68,17 +68,12 @@ struct List {
     uint64_t *out;
 };
 
-static inline uint64_t workspace_bytes(uint64_t capacity) {
+static inline Work layout(msj_carver &c, uint64_t capacity) {
     const uint64_t rows = most_rows(capacity);
-    return sizeof(State) + up16(8 * (rows / kRows + 1)) + up16(4 * rows) + 64;
-}
-static inline Work layout(void *ws, uint64_t capacity) {
-    const uint64_t rows = most_rows(capacity);
-    uint8_t *p = static_cast<uint8_t *>(ws);
     Work w;
-    w.st = reinterpret_cast<State *>(p), p += sizeof(State);
-    w.bcnt = reinterpret_cast<uint64_t *>(p), p += up16(8 * (rows / kRows + 1));
-    w.rank = reinterpret_cast<uint32_t *>(p);
+    w.st = c.take<State>(1);
+    w.bcnt = c.take<uint64_t>(rows / kRows + 1);
+    w.rank = c.take<uint32_t>(rows);
     return w;
 }
 
@@ -259,7 +254,7 @@ static inline dim3 grid_over(uint64_t items) {
 
 }  // namespace msj_frows
 
-extern "C" uint64_t msj_filter_rows_workspace_bytes(uint64_t capacity) { return msj_frows::workspace_bytes(capacity); }
+extern "C" uint64_t msj_filter_rows_workspace_bytes(uint64_t capacity) { return msj_measure(msj_frows::layout, capacity) + 64; }
 
 extern "C" int msj_launch_filter_rows(const void *d_predicates, const uint8_t *d_buf, uint64_t len, const msj_field *d_fields, uint64_t stride,
                                       const msj_select_documents_result *d_rows_select, uint8_t *d_keep, uint32_t *d_kept, uint64_t capacity,
@@ -271,7 +266,7 @@ extern "C" int msj_launch_filter_rows(const void *d_predicates, const uint8_t *d
     const Predicates *preds = static_cast<const Predicates *>(d_predicates);
     const Rows rows{d_fields, stride, d_rows_select, capacity};
     const List list{d_list_offsets, list_rows, d_list_n_rows, d_list_offsets_out};
-    const Work w = layout(d_ws, capacity);
+    const Work w = msj_place(layout, d_ws, capacity);
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(State), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint64_t most = most_rows(capacity);
@@ -291,7 +286,7 @@ extern "C" int msj_launch_take_rows(const uint32_t *d_take, const msj_select_doc
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Take t{d_take, d_take_select, d_out, out_stride, out_capacity, n_columns};
     const Rows rows{d_fields, stride, d_rows_select, stride};
-    const Work w = layout(d_ws, 0);  // (the counters alone)
+    const Work w = msj_place(layout, d_ws, 0);  // (the counters alone)
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(State), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint64_t most = most_rows(out_capacity);

@@ -11,6 +11,36 @@
 
 #include "../../include/msj_stage1.h"
 
+// ---- how every call behind stage 1 carves its one device workspace (host only) ----
+// A call has ONE function that takes its arrays from a carver, in order.  The launcher runs it over the workspace and gets
+// the pointers; the exported msj_*_workspace_bytes runs it over no base at all and gets the size, to which it adds the
+// call's tail slack.  So a size cannot disagree with the layout it reserves room for ("A call's size is its
+// layout, measured").  The offset is an integer: measuring forms no pointer.
+struct msj_carver {
+    uint8_t *base;       // null: measure only
+    uint64_t bytes = 0;  // carved so far
+    explicit msj_carver(void *ws) : base(static_cast<uint8_t *>(ws)) {}
+    // `count` elements of T from here on; what comes next starts at the next multiple of `round` bytes (a power of two)
+    template <class T>
+    T *take(uint64_t count, uint64_t round = 16) {
+        const uint64_t at = bytes;
+        bytes = (at + count * sizeof(T) + round - 1) & ~(round - 1);
+        return base ? reinterpret_cast<T *>(base + at) : nullptr;
+    }
+};
+// a layout function over a workspace: what it returns; and over none: the bytes it carves
+template <class Layout, class... Args>
+auto msj_place(Layout layout, void *ws, Args... args) {
+    msj_carver c(ws);
+    return layout(c, args...);
+}
+template <class Layout, class... Args>
+uint64_t msj_measure(Layout layout, Args... args) {
+    msj_carver c(nullptr);
+    layout(c, args...);
+    return c.bytes;
+}
+
 // What a token call takes besides its arrays.  The first three are TEST HOOKS kept per context
 // (msj_debug_set_span_limits / msj_debug_set_span_mode; 0xFFFFFFFF / 0 = the built-in behaviour): a hook left set by
 // one test or tool cannot change the data path of another context.

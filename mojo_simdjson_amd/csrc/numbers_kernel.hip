@@ -301,34 +301,44 @@ __global__ __launch_bounds__(kThreads) void num_long(const uint8_t *__restrict__
 extern "C" uint32_t msj_number_fallback_capacity(uint64_t n) { return (uint32_t)(n / 16 + 4096); }
 extern "C" uint32_t msj_number_long_capacity(uint64_t len) { return (uint32_t)(len / 1025 + 1); }
 
-extern "C" uint64_t msj_number_values_workspace_bytes(uint64_t n, uint64_t len) {
-    const uint64_t nb = (n + msj_nums::kBlock - 1) / msj_nums::kBlock;
-    return sizeof(msj_nums::Counters) + 2 * 4 * (nb ? nb : 1) + 8 * (uint64_t)msj_number_fallback_capacity(n) +
-           8 * (uint64_t)msj_number_long_capacity(len) + 64;
+namespace msj_nums {
+struct Work {
+    Counters *counters;
+    uint32_t *block_cnt, *block_off;  // per block
+    uint2 *fb_list, *long_list;
+};
+static inline Work layout(msj_carver &c, uint64_t n, uint64_t len) {
+    const uint64_t nb = (n + kBlock - 1) / kBlock;
+    Work w;
+    w.counters = c.take<Counters>(1, 4);
+    w.block_cnt = c.take<uint32_t>(nb ? nb : 1, 4);
+    w.block_off = c.take<uint32_t>(nb ? nb : 1, 4);
+    w.fb_list = c.take<uint2>(msj_number_fallback_capacity(n), 8);  // 16 + 8 * nb bytes in: 8-byte aligned
+    w.long_list = c.take<uint2>(msj_number_long_capacity(len), 8);
+    return w;
 }
+}  // namespace msj_nums
+
+extern "C" uint64_t msj_number_values_workspace_bytes(uint64_t n, uint64_t len) { return msj_measure(msj_nums::layout, n, len) + 64; }
 
 extern "C" int msj_launch_number_values(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, const uint8_t *d_flags,
                                         msj_number *d_numbers, uint64_t capacity, msj_numbers_result *d_result, void *d_ws, void *stream) {
     using namespace msj_nums;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint32_t nb = (uint32_t)((n + kBlock - 1) / kBlock);
-    Counters *counters = static_cast<Counters *>(d_ws);
-    uint32_t *block_cnt = reinterpret_cast<uint32_t *>(counters + 1);
-    uint32_t *block_off = block_cnt + (nb ? nb : 1);
-    uint2 *fb_list = reinterpret_cast<uint2 *>(block_off + (nb ? nb : 1));  // 16 + 8 * nb bytes in: 8-byte aligned
+    const Work w = msj_place(layout, d_ws, n, len);
     const uint32_t fb_cap = msj_number_fallback_capacity(n), long_cap = msj_number_long_capacity(len);
-    uint2 *long_list = fb_list + fb_cap;
-    if (nb) hipLaunchKernelGGL(num_count, dim3(nb), dim3(kThreads), 0, s, d_flags, n, block_cnt);
-    hipLaunchKernelGGL(num_scan, dim3(1), dim3(kScanThreads), 0, s, block_cnt, nb, block_off, d_result, counters);
+    if (nb) hipLaunchKernelGGL(num_count, dim3(nb), dim3(kThreads), 0, s, d_flags, n, w.block_cnt);
+    hipLaunchKernelGGL(num_scan, dim3(1), dim3(kScanThreads), 0, s, w.block_cnt, nb, w.block_off, d_result, w.counters);
     if (nb) {
-        hipLaunchKernelGGL(num_convert<false>, dim3(nb), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_flags, block_off, d_numbers, capacity,
-                           d_result, counters, fb_list, fb_cap, long_list, long_cap);
-        hipLaunchKernelGGL(num_long, dim3(kListBlocks / 4), dim3(kThreads), 0, s, d_buf, len, d_idx, d_numbers, capacity, d_result, counters,
-                           long_list, long_cap);
-        hipLaunchKernelGGL(num_fallback, dim3(kListBlocks), dim3(kThreads), 0, s, d_buf, len, d_idx, d_numbers, capacity, d_result, counters,
-                           fb_list, fb_cap);
-        hipLaunchKernelGGL(num_convert<true>, dim3(nb), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_flags, block_off, d_numbers, capacity,
-                           d_result, counters, fb_list, fb_cap, long_list, long_cap);
+        hipLaunchKernelGGL(num_convert<false>, dim3(nb), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_flags, w.block_off, d_numbers, capacity,
+                           d_result, w.counters, w.fb_list, fb_cap, w.long_list, long_cap);
+        hipLaunchKernelGGL(num_long, dim3(kListBlocks / 4), dim3(kThreads), 0, s, d_buf, len, d_idx, d_numbers, capacity, d_result, w.counters,
+                           w.long_list, long_cap);
+        hipLaunchKernelGGL(num_fallback, dim3(kListBlocks), dim3(kThreads), 0, s, d_buf, len, d_idx, d_numbers, capacity, d_result, w.counters,
+                           w.fb_list, fb_cap);
+        hipLaunchKernelGGL(num_convert<true>, dim3(nb), dim3(kThreads), 0, s, d_buf, len, d_idx, n, d_flags, w.block_off, d_numbers, capacity,
+                           d_result, w.counters, w.fb_list, fb_cap, w.long_list, long_cap);
     }
     return (int)hipGetLastError();
 }

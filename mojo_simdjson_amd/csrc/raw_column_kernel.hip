@@ -45,7 +45,7 @@ namespace msj_rcol {
 using namespace msj::rcol;
 using namespace msj::wave;
 using namespace msj_bytes;
-using msj_tape::block_scan, msj_tape::kThreads, msj_tape::kWaves, msj_tape::up16;
+using msj_tape::block_scan, msj_tape::kThreads, msj_tape::kWaves;
 using msj_tdocs::load_field;
 
 constexpr uint32_t kTokPer = 4;           // tokens per lane of rc_tokens
@@ -81,22 +81,16 @@ struct PSum {
 };
 
 __host__ __device__ inline uint64_t token_blocks(uint64_t n) { return n / kTokBlock + 1; }  // tokens 0 .. n: P has n + 1 entries
-static inline uint64_t workspace_bytes(uint64_t n, uint64_t capacity, bool compact) {
+// (the two compact arrays have room in the compact form only: no kernel of the verbatim form reads their pointers)
+static inline Work layout(msj_carver &c, uint64_t n, uint64_t capacity, bool compact) {
     const uint64_t rows = most_rows(capacity);
-    uint64_t b = sizeof(State) + up16(8 * (rows / kRows + 1)) + up16(8 * rows) + up16(4 * kLongCap);
-    if (compact) b += up16(8 * token_blocks(n)) + up16(8 * (n + 1));
-    return b + 64;
-}
-static inline Work layout(void *ws, uint64_t n, uint64_t capacity) {
-    const uint64_t rows = most_rows(capacity);
-    uint8_t *p = static_cast<uint8_t *>(ws);
     Work w;
-    w.st = reinterpret_cast<State *>(p), p += sizeof(State);
-    w.bsum = reinterpret_cast<uint64_t *>(p), p += up16(8 * (rows / kRows + 1));
-    w.lens = reinterpret_cast<uint64_t *>(p), p += up16(8 * rows);
-    w.list = reinterpret_cast<uint32_t *>(p), p += up16(4 * kLongCap);
-    w.tbase = reinterpret_cast<uint64_t *>(p), p += up16(8 * token_blocks(n));
-    w.tloc = reinterpret_cast<uint64_t *>(p);
+    w.st = c.take<State>(1);
+    w.bsum = c.take<uint64_t>(rows / kRows + 1);
+    w.lens = c.take<uint64_t>(rows);
+    w.list = c.take<uint32_t>(kLongCap);
+    w.tbase = c.take<uint64_t>(compact ? token_blocks(n) : 0);
+    w.tloc = c.take<uint64_t>(compact ? n + 1 : 0);
     return w;
 }
 
@@ -336,7 +330,7 @@ __global__ __launch_bounds__(kThreads) void rc_long(const Tokens t, const msj_fi
 }  // namespace msj_rcol
 
 extern "C" uint64_t msj_raw_column_workspace_bytes(uint64_t n, uint64_t capacity, uint32_t flags) {
-    return msj_rcol::workspace_bytes(n, capacity, (flags & MSJ_RAW_COMPACT) != 0);
+    return msj_measure(msj_rcol::layout, n, capacity, (flags & MSJ_RAW_COMPACT) != 0) + 64;
 }
 
 extern "C" int msj_launch_raw_column(const msj_token_view &tv, const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
@@ -346,7 +340,7 @@ extern "C" int msj_launch_raw_column(const msj_token_view &tv, const msj_field *
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool compact = (flags & MSJ_RAW_COMPACT) != 0;
     const Tokens t{tv.d_buf, tv.len, tv.d_idx, tv.n, tv.d_type, tv.d_end, tv.d_flags};
-    const Work w = layout(d_ws, tv.n, capacity);
+    const Work w = msj_place(layout, d_ws, tv.n, capacity, compact);
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(State), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint64_t nb = (most_rows(capacity) + kRows - 1) / kRows;

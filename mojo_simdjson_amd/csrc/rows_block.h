@@ -53,28 +53,21 @@ struct RowsWork {
 };
 
 __host__ __device__ inline uint64_t row_blocks(uint64_t rows) { return (rows + kRowBlock - 1) / kRowBlock; }
-static inline uint64_t work_bytes(uint64_t n, uint64_t capacity) {
-    return sizeof(RowsState) + up16(8 * row_blocks(capacity)) + 2 * up16(4 * capacity) + (sizeof(Desc) + 8) * dense_rows(n, capacity) +
-           up16(4 * token_blocks(n)) + 64;
-}
-static inline RowsWork work_layout(void *ws, uint64_t n, uint64_t capacity) {
-    uint8_t *p = static_cast<uint8_t *>(ws);
-    auto take = [&](uint64_t bytes) {
-        uint8_t *q = p;
-        p += up16(bytes);
-        return q;
-    };
+static inline RowsWork work_layout(msj_carver &c, uint64_t n, uint64_t capacity) {
     RowsWork w;
     w.dense = dense_rows(n, capacity);
-    w.st = reinterpret_cast<RowsState *>(take(sizeof(RowsState)));
-    w.desc = reinterpret_cast<Desc *>(take(sizeof(Desc) * w.dense));
-    w.doff = reinterpret_cast<uint64_t *>(take(8 * w.dense));
-    w.rsum = reinterpret_cast<uint64_t *>(take(8 * row_blocks(capacity)));
-    w.rank = reinterpret_cast<uint32_t *>(take(4 * capacity));
-    w.start = reinterpret_cast<uint32_t *>(take(4 * capacity));
-    w.bsum = reinterpret_cast<uint32_t *>(take(4 * token_blocks(n)));
+    w.st = c.take<RowsState>(1);
+    w.desc = c.take<Desc>(w.dense);
+    w.doff = c.take<uint64_t>(w.dense);
+    w.rsum = c.take<uint64_t>(row_blocks(capacity));
+    w.rank = c.take<uint32_t>(capacity);
+    w.start = c.take<uint32_t>(capacity);
+    w.bsum = c.take<uint32_t>(token_blocks(n));
     return w;
 }
+// The size of both calls.  The sizes callers budget with have always counted doff unrounded: with an odd number of dense rows
+// its 8 bytes of rounding come out of the slack
+static inline uint64_t work_bytes(uint64_t n, uint64_t capacity) { return msj_measure(work_layout, n, capacity) + 64 - 8 * (dense_rows(n, capacity) & 1); }
 
 // what every kernel reads of d_rows_select.  stop: nothing but the results is written
 struct Head {
@@ -345,7 +338,7 @@ int launch_items(const msj_token_view &t, const msj_number_view &nv, const msj_f
                  uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity, const typename P::Out &out, void *d_ws, void *stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t n = t.n;
-    const RowsWork w = work_layout(d_ws, n, capacity);
+    const RowsWork w = msj_place(work_layout, d_ws, n, capacity);
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(RowsState), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint32_t rb = row_grid_blocks(capacity), nb = (uint32_t)token_blocks(n);

@@ -159,10 +159,18 @@ __global__ __launch_bounds__(kThreads) void se_finish(const Paths *__restrict__ 
     });
 }
 
+static inline Words words_layout(msj_carver &c, uint64_t n, uint64_t capacity, uint32_t n_paths) {
+    Words ws;
+    ws.stride = state_rows(n, capacity);
+    for (int b = 0; b < 2; b++) ws.word[b] = c.take<uint32_t>((uint64_t)n_paths * ws.stride, 4);
+    ws.start = c.take<uint32_t>(ws.stride, 4);
+    return ws;
+}
+
 }  // namespace msj_selem
 
 extern "C" uint64_t msj_select_elements_workspace_bytes(uint64_t n, uint64_t capacity, uint32_t n_paths) {
-    return (2ull * 4ull * n_paths + 4ull) * msj::selem::state_rows(n, capacity) + 64;
+    return msj_measure(msj_selem::words_layout, n, capacity, n_paths) + 64;
 }
 
 extern "C" int msj_launch_select_elements(const void *d_paths, uint32_t n_paths, uint32_t max_levels, const msj_token_view &t,
@@ -174,13 +182,8 @@ extern "C" int msj_launch_select_elements(const void *d_paths, uint32_t n_paths,
     const Paths *paths = static_cast<const Paths *>(d_paths);
     const hipError_t cleared = hipMemsetAsync(d_result, 0, sizeof(msj_select_documents_result), s);
     if (cleared != hipSuccess) return (int)cleared;
-    const uint64_t most = state_rows(t.n, capacity);
-    Words ws;
-    ws.word[0] = static_cast<uint32_t *>(d_ws);
-    ws.word[1] = ws.word[0] + (uint64_t)n_paths * most;
-    ws.start = ws.word[1] + (uint64_t)n_paths * most;
-    ws.stride = most;
-    const dim3 row_grid(row_grid_blocks(most), n_paths);  // (the kernels over rows loop: rows past n need no larger grid)
+    const Words ws = msj_place(words_layout, d_ws, t.n, capacity, n_paths);
+    const dim3 row_grid(row_grid_blocks(ws.stride), n_paths);  // (the kernels over rows loop: rows past n need no larger grid)
     hipLaunchKernelGGL(se_init, row_grid, dim3(kThreads), 0, s, paths, t.d_type, t.d_match, t.n, d_rows, d_rows_select, capacity, ws, d_result);
     const uint32_t nb = (uint32_t)((t.n + kBlock - 1) / kBlock);
     for (uint32_t l = 0; l < max_levels; l++) {

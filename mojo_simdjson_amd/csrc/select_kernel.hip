@@ -132,11 +132,18 @@ __global__ __launch_bounds__(kThreads) void sel_finish(const Paths *__restrict__
                 [&](uint64_t k) { return word[k]; });
 }
 
+static inline Words words_layout(msj_carver &c, uint64_t n, uint64_t capacity, uint32_t n_paths) {
+    Words ws;
+    ws.stride = most_documents(n, capacity);
+    for (int b = 0; b < 2; b++) ws.word[b] = c.take<uint32_t>((uint64_t)n_paths * ws.stride, 4);
+    return ws;
+}
+
 }  // namespace msj_sel
 
 extern "C" uint64_t msj_select_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity, uint32_t n_paths) {
     (void)len;
-    return 2ull * 4ull * n_paths * msj_tdocs::most_documents(n, capacity) + 64;
+    return msj_measure(msj_sel::words_layout, n, capacity, n_paths) + 64;
 }
 
 extern "C" int msj_launch_select_documents(const void *d_paths, uint32_t n_paths, uint32_t max_levels, const msj_token_view &t,
@@ -146,12 +153,8 @@ extern "C" int msj_launch_select_documents(const void *d_paths, uint32_t n_paths
     using namespace msj_sel;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Paths *paths = static_cast<const Paths *>(d_paths);
-    const uint64_t most = most_documents(t.n, capacity);
-    Words ws;
-    ws.word[0] = static_cast<uint32_t *>(d_ws);
-    ws.word[1] = ws.word[0] + (uint64_t)n_paths * most;
-    ws.stride = most;
-    const dim3 doc_grid(row_grid_blocks(most), n_paths);
+    const Words ws = msj_place(words_layout, d_ws, t.n, capacity, n_paths);
+    const dim3 doc_grid(row_grid_blocks(ws.stride), n_paths);
     hipLaunchKernelGGL(sel_init, doc_grid, dim3(kThreads), 0, s, paths, t.d_type, t.d_match, t.n, sp.d_doc_first, sp.d_docs, capacity, d_verdicts, ws,
                        d_result);
     if (t.n == 0) return (int)hipGetLastError();  // no document: the zero result is all there is

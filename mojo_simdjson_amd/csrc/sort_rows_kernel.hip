@@ -46,7 +46,7 @@ namespace msj_srows {
 using namespace msj::srows;
 using namespace msj::wave;
 using msj_bytes::kRows, msj_bytes::most_rows;
-using msj_tape::kThreads, msj_tape::kWaves, msj_tape::up16;
+using msj_tape::kThreads, msj_tape::kWaves;
 using msj_tdocs::load_field;
 
 static_assert(sizeof(msj_sort_rows_result) == 48 && sizeof(msj_field) == 16, "ABI");
@@ -97,23 +97,13 @@ struct Call {
 };
 
 static inline uint64_t tiles_of(uint64_t rows) { return (rows + kTile - 1) / kTile; }
-static inline uint64_t workspace_bytes(uint64_t capacity) {
+static inline Work layout(msj_carver &c, uint64_t capacity) {
     const uint64_t rows = most_rows(capacity);
-    return up16(sizeof(State)) + 4 * up16(8 * rows) + up16(4 * kBuckets * tiles_of(rows)) + up16(8 * (rows / kRows + 1)) + 64;
-}
-static inline Work layout(void *ws, uint64_t capacity) {
-    const uint64_t rows = most_rows(capacity);
-    uint8_t *p = static_cast<uint8_t *>(ws);
-    auto take = [&](uint64_t bytes) {
-        uint8_t *q = p;
-        p += up16(bytes);
-        return q;
-    };
     Work w;
-    w.st = reinterpret_cast<State *>(take(sizeof(State)));
-    for (int b = 0; b < 2; b++) w.hi[b] = reinterpret_cast<uint64_t *>(take(8 * rows)), w.aux[b] = reinterpret_cast<uint64_t *>(take(8 * rows));
-    w.cnt = reinterpret_cast<uint32_t *>(take(4 * kBuckets * tiles_of(rows)));
-    w.bcnt = reinterpret_cast<uint64_t *>(take(8 * (rows / kRows + 1)));
+    w.st = c.take<State>(1);
+    for (int b = 0; b < 2; b++) w.hi[b] = c.take<uint64_t>(rows), w.aux[b] = c.take<uint64_t>(rows);
+    w.cnt = c.take<uint32_t>(kBuckets * tiles_of(rows));
+    w.bcnt = c.take<uint64_t>(rows / kRows + 1);
     return w;
 }
 
@@ -458,7 +448,7 @@ __global__ __launch_bounds__(kThreads) void sr_finish(const Call call, const Wor
 
 }  // namespace msj_srows
 
-extern "C" uint64_t msj_sort_rows_workspace_bytes(uint64_t capacity) { return msj_srows::workspace_bytes(capacity); }
+extern "C" uint64_t msj_sort_rows_workspace_bytes(uint64_t capacity) { return msj_measure(msj_srows::layout, capacity) + 64; }
 
 extern "C" int msj_launch_sort_rows(const msj_field *d_fields, uint64_t stride, const msj_select_documents_result *d_rows_select,
                                     const uint32_t *d_rows_in, const msj_select_documents_result *d_rows_in_select, uint32_t flags, uint64_t limit,
@@ -467,7 +457,7 @@ extern "C" int msj_launch_sort_rows(const msj_field *d_fields, uint64_t stride, 
     using namespace msj_srows;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Call call{d_fields, stride, d_rows_select, d_rows_in, d_rows_in_select, flags, mode, limit, capacity};
-    const Work w = layout(d_ws, capacity);
+    const Work w = msj_place(layout, d_ws, capacity);
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(State), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint64_t most = most_rows(capacity), nb = (most + kRows - 1) / kRows, nt = tiles_of(most);

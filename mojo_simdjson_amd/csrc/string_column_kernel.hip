@@ -38,7 +38,7 @@ using namespace msj::scol;
 using namespace msj::wave;
 using namespace msj_bytes;
 using msj::val::ByteReader;
-using msj_tape::block_scan, msj_tape::BufWriter, msj_tape::kLaneBody, msj_tape::kThreads, msj_tape::kWaves, msj_tape::up16, msj_tape::wave_unescape;
+using msj_tape::block_scan, msj_tape::BufWriter, msj_tape::kLaneBody, msj_tape::kThreads, msj_tape::kWaves, msj_tape::wave_unescape;
 using msj_tdocs::load_field;
 
 static_assert(sizeof(msj_string_column_result) == 48 && sizeof(msj_field) == 16, "ABI");
@@ -53,13 +53,12 @@ struct Work {
     uint32_t *lens;  // per row: its length in the output
 };
 
-static inline Work layout(void *ws, uint64_t capacity) {
-    const uint64_t rows = most_rows(capacity), nb = rows / kRows + 1;
-    uint8_t *p = static_cast<uint8_t *>(ws);
+static inline Work layout(msj_carver &c, uint64_t capacity) {
+    const uint64_t rows = most_rows(capacity);
     Work w;
-    w.st = reinterpret_cast<State *>(p);
-    w.bsum = reinterpret_cast<uint64_t *>(p + sizeof(State));
-    w.lens = reinterpret_cast<uint32_t *>(p + sizeof(State) + up16(8 * nb));
+    w.st = c.take<State>(1);
+    w.bsum = c.take<uint64_t>(rows / kRows + 1);
+    w.lens = c.take<uint32_t>(rows);
     return w;
 }
 
@@ -150,18 +149,14 @@ __global__ __launch_bounds__(kThreads) void sc_copy(const uint8_t *__restrict__ 
 
 }  // namespace msj_scol
 
-extern "C" uint64_t msj_string_column_workspace_bytes(uint64_t capacity) {
-    using namespace msj_scol;
-    const uint64_t rows = most_rows(capacity);
-    return sizeof(State) + up16(8 * (rows / kRows + 1)) + up16(4 * rows) + 64;
-}
+extern "C" uint64_t msj_string_column_workspace_bytes(uint64_t capacity) { return msj_measure(msj_scol::layout, capacity) + 64; }
 
 extern "C" int msj_launch_string_column(const uint8_t *d_buf, uint64_t len, const msj_field *d_column, const msj_select_documents_result *d_select,
                                         uint64_t *d_offsets, uint8_t *d_valid, uint64_t capacity, uint8_t *d_bytes, uint64_t bytes_capacity,
                                         msj_string_column_result *d_result, void *d_ws, void *stream) {
     using namespace msj_scol;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Work w = layout(d_ws, capacity);
+    const Work w = msj_place(layout, d_ws, capacity);
     const hipError_t cleared = hipMemsetAsync(w.st, 0, sizeof(State), s);
     if (cleared != hipSuccess) return (int)cleared;
     const uint64_t nb = (most_rows(capacity) + kRows - 1) / kRows;

@@ -3,13 +3,14 @@
 // over the blocks, a string token's body (the checked writer and the wave's walk over a long body are wave_unescape.h, which
 // string_column_kernel.hip shares), the 8-ary min tree of a
 // block's depths with its two searches, and the bodies of the kernels that are the same in both calls (positions and
-// element counts, the block minima, the pending counts, the long bodies' bytes).  Device code only; the per-token
-// arithmetic is tape_math.h.
+// element counts, the block minima, the pending counts, the long bodies' bytes).  Device code but for the workspace's
+// layout, which is also its size (launch.h: msj_carver); the per-token arithmetic is tape_math.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
+#include "launch.h"
 #include "tape_math.h"
 #include "wave_ops.h"
 #include "wave_unescape.h"
@@ -49,7 +50,6 @@ struct Work {  // the workspace, carved by layout()
 };
 
 __host__ __device__ inline uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-__host__ __device__ inline uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
 
 // exclusive sum over the workgroup (s_w: kWaves words of LDS, free again after the call); total receives the sum
 template <class T>
@@ -362,35 +362,29 @@ __device__ __forceinline__ void long_out_body(const uint8_t *__restrict__ buf, u
 }
 
 // n_docs: the window call's documents at most (0: the one-document call)
-static inline Work layout(void *ws, uint64_t n, uint64_t len, uint64_t n_docs = 0) {
+static inline Work layout(msj_carver &c, uint64_t n, uint64_t len, uint64_t n_docs) {
     Work w;
     const uint64_t nb = (n + kBlock - 1) / kBlock, lcap = len / kLaneBody + 1;
-    uint8_t *p = static_cast<uint8_t *>(ws);
-    auto take = [&](uint64_t bytes) {
-        uint8_t *q = p;
-        p += up16(bytes);
-        return q;
-    };
     // (the first three are cleared by one memset per call)
-    w.st = reinterpret_cast<State *>(take(sizeof(State)));
-    w.b_sbytes = reinterpret_cast<uint64_t *>(take(8 * nb));
-    w.cnt = reinterpret_cast<uint32_t *>(take(4 * n));
-    w.pos = reinterpret_cast<uint32_t *>(take(4 * n));
-    w.b_words = reinterpret_cast<uint32_t *>(take(4 * nb));
-    w.b_nums = reinterpret_cast<uint32_t *>(take(4 * nb));
-    w.b_nstr = reinterpret_cast<uint32_t *>(take(4 * nb));
-    w.b_min = reinterpret_cast<int32_t *>(take(4 * nb));
-    w.b_min64 = reinterpret_cast<int32_t *>(take(4 * ((nb + 63) / 64)));
-    w.b_min4096 = reinterpret_cast<int32_t *>(take(4 * ((nb + 4095) / 4096)));
-    w.b_span = reinterpret_cast<uint32_t *>(take(4 * nb));
-    w.long_list = reinterpret_cast<uint32_t *>(take(4 * lcap));
-    w.long_ulen = reinterpret_cast<uint32_t *>(take(4 * lcap));
-    w.long_soff = reinterpret_cast<uint64_t *>(take(8 * lcap));
-    w.doc_sbase = reinterpret_cast<uint64_t *>(take(8 * n_docs));
-    w.b_built = reinterpret_cast<uint32_t *>(take(n_docs ? 4 * nb : 0));
+    w.st = c.take<State>(1);
+    w.b_sbytes = c.take<uint64_t>(nb);
+    w.cnt = c.take<uint32_t>(n);
+    w.pos = c.take<uint32_t>(n);
+    w.b_words = c.take<uint32_t>(nb);
+    w.b_nums = c.take<uint32_t>(nb);
+    w.b_nstr = c.take<uint32_t>(nb);
+    w.b_min = c.take<int32_t>(nb);
+    w.b_min64 = c.take<int32_t>((nb + 63) / 64);
+    w.b_min4096 = c.take<int32_t>((nb + 4095) / 4096);
+    w.b_span = c.take<uint32_t>(nb);
+    w.long_list = c.take<uint32_t>(lcap);
+    w.long_ulen = c.take<uint32_t>(lcap);
+    w.long_soff = c.take<uint64_t>(lcap);
+    w.doc_sbase = c.take<uint64_t>(n_docs);
+    w.b_built = c.take<uint32_t>(n_docs ? nb : 0);
     w.long_cap = (uint32_t)lcap;
     w.nb = (uint32_t)nb;
-    w.bytes = (uint64_t)(p - static_cast<uint8_t *>(ws));
+    w.bytes = c.bytes;
     return w;
 }
 

@@ -384,7 +384,7 @@ __global__ __launch_bounds__(kThreads) void td_long_out(const uint8_t *__restric
 }  // namespace msj_tdocs
 
 extern "C" uint64_t msj_tape_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity) {
-    return msj_tape::layout(nullptr, n, len, msj_tdocs::most_documents(n, capacity)).bytes + 64;
+    return msj_measure(msj_tape::layout, n, len, msj_tdocs::most_documents(n, capacity)) + 64;
 }
 
 extern "C" int msj_launch_tape_documents(const msj_token_view &t, const msj_split_view &sp, const msj_number_view &nv,
@@ -393,7 +393,7 @@ extern "C" int msj_launch_tape_documents(const msj_token_view &t, const msj_spli
                                          msj_tape_documents_result *d_result, void *d_ws, void *stream) {
     using namespace msj_tdocs;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Work w = layout(d_ws, t.n, t.len, most_documents(t.n, capacity));
+    const Work w = msj_place(layout, d_ws, t.n, t.len, most_documents(t.n, capacity));
     const uint32_t nb = w.nb, nb64 = (nb + 63) / 64, nb4096 = (nb64 + 63) / 64;
     if (hipMemsetAsync(w.st, 0, (size_t)(reinterpret_cast<uint8_t *>(w.pos) - reinterpret_cast<uint8_t *>(w.st)), s) != hipSuccess)
         return (int)hipGetLastError();

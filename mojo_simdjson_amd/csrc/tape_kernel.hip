@@ -257,7 +257,7 @@ __global__ __launch_bounds__(kThreads) void tape_long_out(const uint8_t *__restr
 }  // namespace msj_tape
 
 extern "C" uint64_t msj_tape_workspace_bytes(uint64_t n, uint64_t len) {
-    return msj_tape::layout(nullptr, n, len).bytes + 64;
+    return msj_measure(msj_tape::layout, n, len, 0) + 64;
 }
 
 extern "C" int msj_launch_tape(const msj_token_view &t, const msj_number_view &nv, const msj_validate_result *d_verdict, uint64_t *d_tape,
@@ -265,7 +265,7 @@ extern "C" int msj_launch_tape(const msj_token_view &t, const msj_number_view &n
                                void *d_ws, void *stream) {
     using namespace msj_tape;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Work w = layout(d_ws, t.n, t.len);
+    const Work w = msj_place(layout, d_ws, t.n, t.len, 0);
     const uint32_t nb = w.nb, nb64 = (nb + 63) / 64, nb4096 = (nb64 + 63) / 64;
     if (hipMemsetAsync(w.st, 0, (size_t)(reinterpret_cast<uint8_t *>(w.pos) - reinterpret_cast<uint8_t *>(w.st)), s) != hipSuccess)
         return (int)hipGetLastError();

@@ -1328,110 +1328,78 @@ __global__ __launch_bounds__(1024) void build_upper_levels_compact(const MinTree
 
 }  // namespace msj_tokens
 
-// workspace: 4 int32 per block (aggregates) + start depth + start slot in the list of opening
-// brackets per block, then (matching only) the min tree and that list (one uint32 per token at most)
-static uint64_t tree_words(uint64_t n) {  // every level padded to a multiple of 8 entries
-    uint64_t w = 0, c = n;
-    while (c > 8) {
-        c = (c + 7) / 8;
-        w += (c + 7) & ~7ull;
-    }
-    return w;
-}
-static uint64_t super_count(uint64_t n) {
-    const uint64_t nb = (n + msj_tokens::kBlock - 1) / msj_tokens::kBlock;
-    return nb ? (nb + msj_tokens::kSuper - 1) / msj_tokens::kSuper : 1;
-}
-// per block: 4 words (depth aggregate) + 4 (document aggregate, for msj_documents_device) + relative start
-// depth + relative start slot
-static uint64_t block_words(uint64_t n) {
-    const uint64_t nb = (n + msj_tokens::kBlock - 1) / msj_tokens::kBlock;
-    return (10 * (nb ? nb : 1) + 7u) & ~7ull;
-}
-static_assert(msj_tokens::kBlock == 2048, "documents_kernel.hip reads these aggregates with its own block size");
-extern "C" void *msj_tokens_doc_aggregates(int32_t *d_ws, uint64_t n) {
-    const uint64_t nb = (n + msj_tokens::kBlock - 1) / msj_tokens::kBlock;
-    return d_ws + 4 * (nb ? nb : 1);
-}
-static uint64_t head_words(uint64_t n) {  // ... + the same six words per run of kSuper blocks
-    return block_words(n) + ((6 * super_count(n) + 7u) & ~7ull);
-}
-// with_match: 0 = depths only, 1 = + match[] (the min tree over depth[], 64 scratch words, the lists of opening brackets
-// left to the tree and their counters), 2 = + pairs[] (round 5: the same over the call's brackets as a compact list -- a
-// token word and a depth word each, n of them at most -- which comes on top)
-static uint64_t compact_words(uint64_t n) { return (n + 7u) & ~7ull; }
-extern "C" uint64_t msj_tokens_workspace_bytes(uint64_t n, int with_match) {
-    const uint64_t nb = (n + msj_tokens::kBlock - 1) / msj_tokens::kBlock;
-    uint64_t w = head_words(n);
-    if (with_match) w += tree_words(n) + 64 + (uint64_t)msj_tokens::kSurvivorShards * msj_tokens::kSurvivorStride;
-    if (with_match) w += msj_tokens::kSurvivorShards * msj_tokens::survivor_capacity(nb);
-    if (with_match == 2) w += 2 * compact_words(n);
-    return w * sizeof(int32_t);
-}
+// ---- the workspace of the token, span and prep calls: every region of it, from (n, len, with_match) by token_layout (below,
+// behind the geometry of the fused kernels) and from nowhere else ----
+// with_match: 0 = depths only, 1 = + match[] (the min tree over depth[], its scratch, the lists of opening brackets left to
+// the tree and their counters), 2 = + pairs[] (round 5: the same over the call's brackets as a compact list, which comes on
+// top).  A region a call does not have is null.
+struct TokenWork {
+    // per block of kBlock tokens (one block at least); every group of regions is padded to a multiple of 8 words
+    int32_t *agg;          // 4 words: the depth aggregate
+    uint4 *doc_agg;        // the document aggregate, for msj_documents_device (msj_tokens_doc_aggregates)
+    int32_t *start;        // relative start depth
+    uint32_t *open_start;  // relative start slot in the list of opening brackets
+    // the same six words per run of kSuper blocks
+    int32_t *super_agg, *super_start;
+    uint32_t *super_open;
+    // with_match: levels 1 .. nlev - 1 of the min tree over n entries, every level padded to a multiple of 8 entries, then
+    // 64 scratch words: apply_depth writes levels 1 .. 3 unconditionally, also those a short input lacks
+    int32_t *level[msj_tokens::kMaxLevels];
+    uint32_t count[msj_tokens::kMaxLevels];
+    int nlev;
+    int32_t *scratch;
+    uint32_t *brk_tok;     // with_match == 2: the compact bracket list, a token and a depth word each, n of them at most
+    int32_t *brk_depth;
+    uint32_t *opens, *survivors;  // with_match: kSurvivorShards lists, then their counters (zeroed by scan_blocks)
+    uint64_t token_bytes;  // msj_tokens_workspace_bytes: the token pre-pass's own regions end here
+    int4 *sub;             // per chunk of kChunk tokens (16-byte aligned): the fused kernels' depth aggregates
+    uint32_t *table;       // the group table of token_tiles
+};
+static_assert(msj_tokens::kBlock == 2048, "documents_kernel.hip reads doc_agg with its own block size");
 
 // scan of the block aggregates (already in d_ws), depth of every token, bracket partners
 static int launch_depth_passes(const uint32_t *d_idx, uint64_t n, uint8_t *d_type, int32_t *d_depth, uint32_t *d_match,
-                               msj_tokens_result *d_result, int32_t *d_ws, hipStream_t s, const msj_token_opts &o) {
+                               msj_tokens_result *d_result, const TokenWork &w, hipStream_t s, const msj_token_opts &o) {
     using namespace msj_tokens;
     (void)d_idx;
     const uint32_t nb = (uint32_t)((n + kBlock - 1) / kBlock);
-    const uint64_t nbs = nb ? nb : 1;
-    int32_t *agg = d_ws, *start = d_ws + 8 * nbs;
-    uint32_t *open_start = reinterpret_cast<uint32_t *>(d_ws + 9 * nbs);
-    uint4 *doc_agg = reinterpret_cast<uint4 *>(d_ws + 4 * nbs);
-    int32_t *tree = d_ws + head_words(n);  // 32-byte aligned inside the workspace
     uint2 *d_pairs = reinterpret_cast<uint2 *>(o.d_pairs);
+    // (a call without a token hands no kernel a matching region, whatever it was laid out for)
     const bool want_match = (d_match != nullptr || d_pairs != nullptr) && n > 0;
     const bool compact = want_match && d_pairs != nullptr;
-    // the workspace behind the tree (msj_tokens_workspace_bytes): [compact: the bracket list, a token and a depth word
-    // each,] kSurvivorShards lists, then their counters (zeroed by scan_blocks)
-    uint32_t *behind = want_match ? reinterpret_cast<uint32_t *>(tree + tree_words(n) + 64) : nullptr;
-    uint32_t *brk_tok = compact ? behind : nullptr;
-    int32_t *brk_depth = compact ? reinterpret_cast<int32_t *>(behind + compact_words(n)) : nullptr;
-    uint32_t *opens = compact ? behind + 2 * compact_words(n) : behind;
-    uint32_t *survivors = want_match ? opens + kSurvivorShards * survivor_capacity(nb) : nullptr;
-    const uint32_t nsuper = (uint32_t)super_count(n);
-    int32_t *super_agg = d_ws + block_words(n), *super_start = super_agg + 4 * (uint64_t)nsuper;
-    uint32_t *super_open = reinterpret_cast<uint32_t *>(super_start + nsuper);
-    if (nb) hipLaunchKernelGGL(scan_super, dim3(nsuper), dim3(256), 0, s, agg, nb, start, open_start, super_agg);
+    uint32_t *brk_tok = compact ? w.brk_tok : nullptr;
+    int32_t *brk_depth = compact ? w.brk_depth : nullptr;
+    uint32_t *opens = want_match ? w.opens : nullptr;
+    uint32_t *survivors = want_match ? w.survivors : nullptr;
+    const uint32_t nsuper = nb ? (nb + kSuper - 1u) / kSuper : 1u;
+    if (nb) hipLaunchKernelGGL(scan_super, dim3(nsuper), dim3(256), 0, s, w.agg, nb, w.start, w.open_start, w.super_agg);
     uint32_t *resid = (want_match && !d_pairs) ? o.d_resid : nullptr;
-    hipLaunchKernelGGL(scan_blocks, dim3(1), dim3(1024), 0, s, super_agg, nb ? nsuper : 0u, super_start, super_open, d_result, n, o.d_prev,
+    hipLaunchKernelGGL(scan_blocks, dim3(1), dim3(1024), 0, s, w.super_agg, nb ? nsuper : 0u, w.super_start, w.super_open, d_result, n, o.d_prev,
                        survivors, resid);
     // levels of the min tree (over depth[]; compact: over the bracket list's depth words, laid out for n brackets, the
     // counts of a call known on the device only): 1..3 come out of apply_depth / match_compact, the rest from build_level
     MinTree t;
     t.lv[0] = compact ? brk_depth : d_depth;
     t.cnt[0] = (uint32_t)n;
-    t.nlev = 1;
-    int32_t *lvl[kMaxLevels] = {nullptr};
-    for (int k = 1; k < kMaxLevels; k++) t.lv[k] = nullptr, t.cnt[k] = 0;
-    if (want_match) {
-        int32_t *p = tree;
-        while (t.cnt[t.nlev - 1] > 8 && t.nlev < kMaxLevels) {
-            const uint32_t c_out = (t.cnt[t.nlev - 1] + 7u) / 8u;
-            lvl[t.nlev] = p;
-            t.lv[t.nlev] = p;
-            t.cnt[t.nlev] = c_out;
-            p += (c_out + 7u) & ~7u;
-            t.nlev++;
-        }
-    }
-    // apply_depth writes levels 1..3 unconditionally when asked to: give it scratch for the ones a short input lacks
-    int32_t *l1 = want_match ? (t.nlev > 1 ? lvl[1] : tree) : nullptr;
-    int32_t *l2 = want_match ? (t.nlev > 2 ? lvl[2] : tree + tree_words(n) + 8) : nullptr;
-    int32_t *l3 = want_match ? (t.nlev > 3 ? lvl[3] : tree + tree_words(n) + 40) : nullptr;
+    t.nlev = w.nlev;
+    int32_t *const *lvl = w.level;
+    for (int k = 1; k < kMaxLevels; k++) t.lv[k] = w.level[k], t.cnt[k] = w.count[k];
+    // apply_depth writes levels 1..3 unconditionally when asked to: the scratch words for the ones a short input lacks
+    int32_t *l1 = want_match ? (t.nlev > 1 ? lvl[1] : w.scratch) : nullptr;
+    int32_t *l2 = want_match ? (t.nlev > 2 ? lvl[2] : w.scratch + 8) : nullptr;
+    int32_t *l3 = want_match ? (t.nlev > 3 ? lvl[3] : w.scratch + 40) : nullptr;
     int32_t *const no_level = nullptr;
     uint32_t *const no_brk = nullptr;
     if (nb && compact)
-        hipLaunchKernelGGL(depth_rows<true>, dim3((nb + kRowsWaves - 1u) / kRowsWaves), dim3(kThreads), 0, s, d_type, n, nb, start, super_start, super_open,
-                           open_start, d_depth, doc_agg, agg, o.d_prev, brk_tok, brk_depth);
+        hipLaunchKernelGGL(depth_rows<true>, dim3((nb + kRowsWaves - 1u) / kRowsWaves), dim3(kThreads), 0, s, d_type, n, nb, w.start, w.super_start, w.super_open,
+                           w.open_start, d_depth, w.doc_agg, w.agg, o.d_prev, brk_tok, brk_depth);
     else if (nb && want_match)
-        hipLaunchKernelGGL(apply_depth, dim3(nb), dim3(kThreads), 0, s, d_type, n, start, super_start, d_depth, l1, l2, l3, opens, doc_agg, agg, o.d_prev,
+        hipLaunchKernelGGL(apply_depth, dim3(nb), dim3(kThreads), 0, s, d_type, n, w.start, w.super_start, d_depth, l1, l2, l3, opens, w.doc_agg, w.agg, o.d_prev,
                            d_match, survivors, o.match_bias, resid ? 1u : 0u);
     else if (nb)
-        hipLaunchKernelGGL(depth_rows<false>, dim3((nb + kRowsWaves - 1u) / kRowsWaves), dim3(kThreads), 0, s, d_type, n, nb, start, super_start, super_open,
-                           open_start, d_depth, doc_agg, agg, o.d_prev, no_brk, no_level);
-    if (nb) hipLaunchKernelGGL(min_max_depth, dim3(nb < kMinMaxGroups * 256u ? (nb + 255u) / 256u : kMinMaxGroups), dim3(256), 0, s, agg, nb, d_result, resid);
+        hipLaunchKernelGGL(depth_rows<false>, dim3((nb + kRowsWaves - 1u) / kRowsWaves), dim3(kThreads), 0, s, d_type, n, nb, w.start, w.super_start, w.super_open,
+                           w.open_start, d_depth, w.doc_agg, w.agg, o.d_prev, no_brk, no_level);
+    if (nb) hipLaunchKernelGGL(min_max_depth, dim3(nb < kMinMaxGroups * 256u ? (nb + 255u) / 256u : kMinMaxGroups), dim3(256), 0, s, w.agg, nb, d_result, resid);
     const uint32_t lists = nb < kSurvivorShards ? nb : kSurvivorShards;
     const uint32_t per_list = nb / kSurvivorShards / 8u + 1u;  // ~2 survivors per block, 16 brackets per workgroup and round
     if (compact) {
@@ -2720,19 +2688,47 @@ extern "C" int msj_debug_set_tile_stamps(void *d_stamps) {
 // the work list of span_fixup: zeroed once by the owner (the kernels leave it zeroed)
 extern "C" uint64_t msj_span_fix_bytes(void) { return (msj_tokens::kFixWords + msj_tokens::kLngWords) * sizeof(uint32_t); }  // + the long-string list
 
-// ---- workspace of the span / prep calls: the token pre-pass's own words, then (16-byte aligned) one int4 per chunk
-// of kChunk tokens (the fused kernels' depth aggregates), then the group table of token_tiles
+// ---- TokenWork (above) carved: the token pre-pass's own regions, then one int4 per chunk of kChunk tokens, then the group
+// table of token_tiles.  Every region in front of the chunk aggregates is whole runs of 8 words: they start 16-byte aligned
 static uint64_t chunk_count(uint64_t n) { return n ? (n + msj_tokens::kChunk - 1) / msj_tokens::kChunk : 1; }
 static uint64_t group_count(uint64_t len) { return (len + msj_tokens::kTgBytes - 1) / msj_tokens::kTgBytes; }
-static uint64_t sub_offset_bytes(uint64_t n, int with_match) { return (msj_tokens_workspace_bytes(n, with_match) + 15u) & ~15ull; }
+static TokenWork token_layout(msj_carver &c, uint64_t n, uint64_t len, int with_match) {
+    using namespace msj_tokens;
+    const uint64_t nb = (n + kBlock - 1) / kBlock, nbs = nb ? nb : 1, nsuper = (nbs + kSuper - 1) / kSuper;
+    TokenWork w = {};
+    w.agg = c.take<int32_t>(4 * nbs, 4);
+    w.doc_agg = c.take<uint4>(nbs, 4);
+    w.start = c.take<int32_t>(nbs, 4);
+    w.open_start = c.take<uint32_t>(nbs, 32);
+    w.super_agg = c.take<int32_t>(4 * nsuper, 4);
+    w.super_start = c.take<int32_t>(nsuper, 4);
+    w.super_open = c.take<uint32_t>(nsuper, 32);
+    w.nlev = 1;
+    if (with_match) {
+        for (uint64_t cnt = n; cnt > 8;) {  // (a level past kMaxLevels has its room and no pointer: n >= 2^33, no call's)
+            cnt = (cnt + 7) / 8;
+            int32_t *level = c.take<int32_t>(cnt, 32);
+            if (w.nlev < kMaxLevels) w.level[w.nlev] = level, w.count[w.nlev] = (uint32_t)cnt, w.nlev++;
+        }
+        w.scratch = c.take<int32_t>(64, 32);
+        if (with_match == 2) w.brk_tok = c.take<uint32_t>(n, 32), w.brk_depth = c.take<int32_t>(n, 32);
+        w.opens = c.take<uint32_t>(kSurvivorShards * survivor_capacity(nb), 32);
+        w.survivors = c.take<uint32_t>((uint64_t)kSurvivorShards * kSurvivorStride, 32);
+    }
+    w.token_bytes = c.bytes;
+    w.sub = c.take<int4>(chunk_count(n));
+    w.table = c.take<uint32_t>(group_count(len) + 2, 4);
+    return w;
+}
+static int match_form(const uint32_t *d_match, const msj_token_opts &o) { return o.d_pairs ? 2 : (d_match != nullptr ? 1 : 0); }
+extern "C" uint64_t msj_tokens_workspace_bytes(uint64_t n, int with_match) {
+    return msj_place(token_layout, nullptr, n, 0, with_match).token_bytes;
+}
 extern "C" uint64_t msj_stage2_prep_workspace_bytes(uint64_t n, uint64_t len, int with_match) {
-    return sub_offset_bytes(n, with_match) + chunk_count(n) * sizeof(int4) + (group_count(len) + 2) * sizeof(uint32_t);
+    return msj_measure(token_layout, n, len, with_match);
 }
-static int4 *sub_of(int32_t *d_ws, uint64_t n, int with_match) {
-    return reinterpret_cast<int4 *>(reinterpret_cast<uint8_t *>(d_ws) + sub_offset_bytes(n, with_match));
-}
-static uint32_t *table_of(int32_t *d_ws, uint64_t n, int with_match) {
-    return reinterpret_cast<uint32_t *>(sub_of(d_ws, n, with_match) + chunk_count(n));
+extern "C" void *msj_tokens_doc_aggregates(int32_t *d_ws, uint64_t n) {
+    return msj_place(token_layout, d_ws, n, 0, 0).doc_agg;
 }
 
 // the tile-organised kernel with its table in front of it and the fix-up pass behind it
@@ -2750,6 +2746,28 @@ static void launch_token_tiles(const uint8_t *d_buf, uint64_t len, const uint32_
     }
 }
 
+// The first pass of the token and prep calls: every token's type byte and the chunks' depth aggregates -- kSpans: its end
+// and flags as well, with the fix-up passes --, by tiles or by tokens, then the chunks folded into the blocks' aggregates
+template <bool kSpans>
+static void launch_first_pass(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, uint8_t *d_type, uint32_t *d_end,
+                              uint8_t *d_flags, const TokenWork &w, uint32_t *d_fix, hipStream_t s, const msj_token_opts &o) {
+    using namespace msj_tokens;
+    if (n == 0) return;
+    const uint32_t nb = (uint32_t)((n + kBlock - 1) / kBlock);
+    if (by_tiles(o, n, len)) {
+        launch_token_tiles<true, kSpans>(d_buf, len, d_idx, n, d_end, d_flags, d_type, w.sub, w.table, d_fix, s, o);
+    } else {
+        const uint32_t nsub = (uint32_t)((n + kSpanTokens - 1) / kSpanTokens);
+        hipLaunchKernelGGL((token_spans<true, kSpans>), dim3(nsub), dim3(kSpanThreads), 0, s, d_buf, len, d_idx, n, d_end, d_flags,
+                           kSpans ? span_lds_limit(o) : kSpanLds, d_type, w.sub, d_fix, kSpans ? fix_cap(o) : 0u);
+        if (kSpans) {
+            hipLaunchKernelGGL(span_fixup, dim3(kFixGroups), dim3(256), 0, s, d_buf, len, d_idx, n, d_end, d_flags, d_fix, fix_cap(o));
+            hipLaunchKernelGGL(long_strings_big, dim3(kBigGroups), dim3(256), 0, s, d_buf, d_idx, d_end, d_flags, d_fix);
+        }
+    }
+    hipLaunchKernelGGL(merge_chunk_counts, dim3((nb * 16u + 255u) / 256u), dim3(256), 0, s, w.sub, (uint32_t)chunk_count(n), w.agg, nb);
+}
+
 int msj_launch_token_spans(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, uint32_t *d_end, uint8_t *d_flags,
                            int32_t *d_ws, uint32_t *d_fix, void *stream, const msj_token_opts &o) {
     using namespace msj_tokens;
@@ -2759,7 +2777,8 @@ int msj_launch_token_spans(const uint8_t *d_buf, uint64_t len, const uint32_t *d
     // against 0.49, pretty-printed 0.48 against 0.45: without the type bytes and bracket counts the fused call gets for
     // nothing, the tile kernel's per-byte work pays off later) -- from one structural per 7 bytes on
     if ((o.span_mode == 2u || (o.span_mode == 0u && n * 7u >= len)) && (reinterpret_cast<uintptr_t>(d_idx) & 7u) == 0) {
-        launch_token_tiles<false, true>(d_buf, len, d_idx, n, d_end, d_flags, nullptr, nullptr, table_of(d_ws, n, 0), d_fix, s, o);
+        uint32_t *table = msj_place(token_layout, d_ws, n, len, 0).table;  // (its place in the layout without partners)
+        launch_token_tiles<false, true>(d_buf, len, d_idx, n, d_end, d_flags, nullptr, nullptr, table, d_fix, s, o);
         return (int)hipGetLastError();
     }
     const uint32_t lds_limit = span_lds_limit(o);  // stretches over this many bytes take the global-memory path
@@ -2778,24 +2797,10 @@ int msj_launch_stage2_prep(const uint8_t *d_buf, uint64_t len, const uint32_t *d
                            uint32_t *d_fix, void *stream, const msj_token_opts &o) {
     using namespace msj_tokens;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t nb64 = (n + kBlock - 1) / kBlock;
-    if (nb64 > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-    const uint32_t nb = (uint32_t)nb64;
-    // the fused kernel's aggregates live behind the token pre-pass's own workspace (16-byte aligned)
-    const int wm = o.d_pairs ? 2 : (d_match != nullptr ? 1 : 0);
-    int4 *sub = sub_of(d_ws, n, wm);
-    if (n && by_tiles(o, n, len)) {
-        launch_token_tiles<true, true>(d_buf, len, d_idx, n, d_end, d_flags, d_type, sub, table_of(d_ws, n, wm), d_fix, s, o);
-        hipLaunchKernelGGL(merge_chunk_counts, dim3((nb * 16u + 255u) / 256u), dim3(256), 0, s, sub, (uint32_t)chunk_count(n), d_ws, nb);
-    } else if (n) {
-        const uint32_t nsub = (uint32_t)((n + kSpanTokens - 1) / kSpanTokens);
-        const uint32_t lds_limit = span_lds_limit(o);
-        hipLaunchKernelGGL(token_spans<true>, dim3(nsub), dim3(kSpanThreads), 0, s, d_buf, len, d_idx, n, d_end, d_flags, lds_limit, d_type, sub, d_fix, fix_cap(o));
-        hipLaunchKernelGGL(span_fixup, dim3(kFixGroups), dim3(256), 0, s, d_buf, len, d_idx, n, d_end, d_flags, d_fix, fix_cap(o));
-        hipLaunchKernelGGL(long_strings_big, dim3(kBigGroups), dim3(256), 0, s, d_buf, d_idx, d_end, d_flags, d_fix);
-        hipLaunchKernelGGL(merge_chunk_counts, dim3((nb * 16u + 255u) / 256u), dim3(256), 0, s, sub, (uint32_t)chunk_count(n), d_ws, nb);
-    }
-    return launch_depth_passes(d_idx, n, d_type, d_depth, d_match, d_result, d_ws, s, o);
+    if ((n + kBlock - 1) / kBlock > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    const TokenWork w = msj_place(token_layout, d_ws, n, len, match_form(d_match, o));
+    launch_first_pass<true>(d_buf, len, d_idx, n, d_type, d_end, d_flags, w, d_fix, s, o);
+    return launch_depth_passes(d_idx, n, d_type, d_depth, d_match, d_result, w, s, o);
 }
 
 // ---- PROTOTYPE (round 5): depth (and partners) from type bytes that stage 1 wrote itself
@@ -2847,29 +2852,19 @@ extern "C" int msj_launch_depth_from_types(const uint8_t *d_type, uint64_t n, in
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t nb64 = (n + kBlock - 1) / kBlock;
     if (nb64 > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-    if (n) hipLaunchKernelGGL(count_brackets, dim3((uint32_t)((nb64 * 128u + 255u) / 256u)), dim3(256), 0, s, d_type, (uint32_t)n, d_ws);
-    return launch_depth_passes(nullptr, n, const_cast<uint8_t *>(d_type), d_depth, d_match, d_result, d_ws, s, o);
+    const TokenWork w = msj_place(token_layout, d_ws, n, 0, match_form(d_match, o));
+    if (n) hipLaunchKernelGGL(count_brackets, dim3((uint32_t)((nb64 * 128u + 255u) / 256u)), dim3(256), 0, s, d_type, (uint32_t)n, w.agg);
+    return launch_depth_passes(nullptr, n, const_cast<uint8_t *>(d_type), d_depth, d_match, d_result, w, s, o);
 }
 
 int msj_launch_tokens(const uint8_t *d_buf, uint64_t len, const uint32_t *d_idx, uint64_t n, uint8_t *d_type, int32_t *d_depth,
                       uint32_t *d_match, msj_tokens_result *d_result, int32_t *d_ws, void *stream, const msj_token_opts &o) {
     using namespace msj_tokens;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t nb64 = (n + kBlock - 1) / kBlock;
-    if (nb64 > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
-    const uint32_t nb = (uint32_t)nb64;
-    const int wm = o.d_pairs ? 2 : (d_match != nullptr ? 1 : 0);
-    int4 *sub = sub_of(d_ws, n, wm);
-    if (n && by_tiles(o, n, len)) {
-        launch_token_tiles<true, false>(d_buf, len, d_idx, n, nullptr, nullptr, d_type, sub, table_of(d_ws, n, wm), nullptr, s, o);
-        hipLaunchKernelGGL(merge_chunk_counts, dim3((nb * 16u + 255u) / 256u), dim3(256), 0, s, sub, (uint32_t)chunk_count(n), d_ws, nb);
-    } else if (n) {
-        const uint32_t nsub = (uint32_t)((n + kSpanTokens - 1) / kSpanTokens);
-        hipLaunchKernelGGL((token_spans<true, false>), dim3(nsub), dim3(kSpanThreads), 0, s, d_buf, len, d_idx, n, static_cast<uint32_t *>(nullptr),
-                           static_cast<uint8_t *>(nullptr), kSpanLds, d_type, sub, static_cast<uint32_t *>(nullptr), 0u);
-        hipLaunchKernelGGL(merge_chunk_counts, dim3((nb * 16u + 255u) / 256u), dim3(256), 0, s, sub, (uint32_t)chunk_count(n), d_ws, nb);
-    }
-    return launch_depth_passes(d_idx, n, d_type, d_depth, d_match, d_result, d_ws, s, o);
+    if ((n + kBlock - 1) / kBlock > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
+    const TokenWork w = msj_place(token_layout, d_ws, n, len, match_form(d_match, o));
+    launch_first_pass<false>(d_buf, len, d_idx, n, d_type, nullptr, nullptr, w, nullptr, s, o);
+    return launch_depth_passes(d_idx, n, d_type, d_depth, d_match, d_result, w, s, o);
 }
 
 int msj_launch_stitch_partners(const msj_stitch_args &a, uint32_t *d_match, msj_tokens_result *d_results, const msj_tokens_result *d_prev,

@@ -1,11 +1,13 @@
 // validate_block.h -- the device pieces that validate_kernel.hip (one document) and validate_docs_kernel.hip (every
 // document of a window) share: the geometry of the token pass, the block's neighbourhood in LDS as the rule's accessor,
-// and the wave's walk over a long escaped body.  Device code only; the rule itself is validate_math.h.
+// the wave's walk over a long escaped body, and the calls' state and workspace.  Device code but for the workspace's layout;
+// the rule itself is validate_math.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/msj_stage1.h"
+#include "launch.h"
 #include "validate_math.h"
 #include "wave_ops.h"
 
@@ -136,6 +138,24 @@ __device__ __forceinline__ void count_listed_commas(const uint8_t *__restrict__ 
         commas = wave_sum(commas);
         if ((threadIdx.x & 63) == 0 && commas) atomicAdd(&st->big_commas[c], commas);
     }
+}
+
+// the workspace of both calls (host): the state, the two lists of escaped bodies -- a body over kLaneBody (kWaveBody) bytes
+// takes that many bytes, so they are never full -- and one count per block of the token pass, which judges token n too
+struct Work {
+    State *st;
+    uint32_t *long_list, *huge_list, *block_esc;
+    uint32_t long_cap, huge_cap, nb;
+};
+static inline Work layout(msj_carver &c, uint64_t n, uint64_t len) {
+    Work w;
+    w.long_cap = (uint32_t)(len / kLaneBody + 1), w.huge_cap = (uint32_t)(len / kWaveBody + 1);
+    w.nb = (uint32_t)((n + 1 + kBlock - 1) / kBlock);
+    w.st = c.take<State>(1, 4);
+    w.long_list = c.take<uint32_t>(w.long_cap, 4);
+    w.huge_list = c.take<uint32_t>(w.huge_cap, 4);
+    w.block_esc = c.take<uint32_t>(w.nb, 4);
+    return w;
 }
 
 }  // namespace msj_val

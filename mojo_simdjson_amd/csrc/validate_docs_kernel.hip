@@ -352,15 +352,10 @@ __global__ __launch_bounds__(kThreads) void vd_finish(const msj_documents_result
 
 }  // namespace msj_vdocs
 
-// entries of the two lists of escaped bodies: a body over kLaneBody (kWaveBody) bytes takes that many bytes: never full
-static uint32_t vd_long_capacity(uint64_t len) { return (uint32_t)(len / msj_val::kLaneBody + 1); }
-static uint32_t vd_huge_capacity(uint64_t len) { return (uint32_t)(len / msj_val::kWaveBody + 1); }
-
 // (capacity: the documents' error words live in d_verdicts, so nothing here grows with it)
 extern "C" uint64_t msj_validate_documents_workspace_bytes(uint64_t n, uint64_t len, uint64_t capacity) {
     (void)capacity;
-    const uint64_t nb = (n + 1 + msj_val::kBlock - 1) / msj_val::kBlock;
-    return sizeof(msj_val::State) + 4ull * vd_long_capacity(len) + 4ull * vd_huge_capacity(len) + 4ull * nb + 64;
+    return msj_measure(msj_val::layout, n, len) + 64;
 }
 
 extern "C" int msj_launch_validate_documents(const msj_token_view &t, const msj_split_view &sp, const msj_number_view &nv, uint32_t max_depth,
@@ -368,26 +363,21 @@ extern "C" int msj_launch_validate_documents(const msj_token_view &t, const msj_
                                              void *d_ws, void *stream) {
     using namespace msj_vdocs;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    State *st = static_cast<State *>(d_ws);
-    const uint32_t long_cap = vd_long_capacity(t.len), huge_cap = vd_huge_capacity(t.len);
-    uint32_t *long_list = reinterpret_cast<uint32_t *>(st + 1);
-    uint32_t *huge_list = long_list + long_cap;
-    uint32_t *block_esc = huge_list + huge_cap;  // one count per block of vd_tokens
-    const uint32_t nb = (uint32_t)((t.n + 1 + kBlock - 1) / kBlock);  // token T <= n, the last document's end of stream, is judged too
+    const msj_val::Work w = msj_place(msj_val::layout, d_ws, t.n, t.len);  // (token T <= n, the last document's end of stream, is judged too)
     // the grid-stride kernels over the documents: there are at most min(n, capacity) of them
     const uint64_t most = t.n < capacity ? t.n : capacity;
     const uint32_t gb = (uint32_t)((most + (uint64_t)kThreads * 4 - 1) / ((uint64_t)kThreads * 4));
     const uint32_t doc_blocks = gb < 1 ? 1u : (gb > (uint32_t)kGridBlocks ? (uint32_t)kGridBlocks : gb);
     hipLaunchKernelGGL(vd_init, dim3(doc_blocks), dim3(kThreads), 0, s, sp.d_docs, t.n, capacity, nv.d_numbers_result, nv.d_numbers,
-                       nv.numbers_capacity, st, d_verdicts, d_result);
+                       nv.numbers_capacity, w.st, d_verdicts, d_result);
     if (t.n == 0) return (int)hipGetLastError();  // no document: the zero result is all there is
-    hipLaunchKernelGGL(vd_tokens, dim3(nb), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_depth, t.d_match, t.d_end, t.d_flags,
-                       sp.d_doc_first, sp.d_docs, capacity, max_depth, st, d_verdicts, long_list, long_cap, huge_list, huge_cap, block_esc);
+    hipLaunchKernelGGL(vd_tokens, dim3(w.nb), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_depth, t.d_match, t.d_end, t.d_flags,
+                       sp.d_doc_first, sp.d_docs, capacity, max_depth, w.st, d_verdicts, w.long_list, w.long_cap, w.huge_list, w.huge_cap, w.block_esc);
     hipLaunchKernelGGL(vd_strings, dim3(kListBlocks), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_end, sp.d_doc_first, sp.d_docs,
-                       capacity, st, d_verdicts, long_list, long_cap, huge_list, huge_cap);
-    hipLaunchKernelGGL(vd_count, dim3(kListBlocks * 4), dim3(kThreads), 0, s, t.d_type, t.d_depth, t.n, sp.d_docs, st);
+                       capacity, w.st, d_verdicts, w.long_list, w.long_cap, w.huge_list, w.huge_cap);
+    hipLaunchKernelGGL(vd_count, dim3(kListBlocks * 4), dim3(kThreads), 0, s, t.d_type, t.d_depth, t.n, sp.d_docs, w.st);
     hipLaunchKernelGGL(vd_records, dim3(kListBlocks), dim3(kThreads), 0, s, sp.d_doc_first, sp.d_docs, t.n, capacity, nv.d_numbers_result,
-                       nv.d_numbers, nv.numbers_capacity, st, d_verdicts, d_result);
-    hipLaunchKernelGGL(vd_finish, dim3(doc_blocks), dim3(kThreads), 0, s, sp.d_docs, t.n, capacity, block_esc, nb, d_verdicts, d_result);
+                       nv.d_numbers, nv.numbers_capacity, w.st, d_verdicts, d_result);
+    hipLaunchKernelGGL(vd_finish, dim3(doc_blocks), dim3(kThreads), 0, s, sp.d_docs, t.n, capacity, w.block_esc, w.nb, d_verdicts, d_result);
     return (int)hipGetLastError();
 }

@@ -208,31 +208,19 @@ __global__ __launch_bounds__(kThreads) void val_finish(const State *__restrict__
 
 }  // namespace msj_val
 
-// entries of the two lists of escaped bodies: a body over kLaneBody (kWaveBody) bytes takes that many bytes: never full
-static uint32_t msj_validate_long_capacity(uint64_t len) { return (uint32_t)(len / msj_val::kLaneBody + 1); }
-static uint32_t msj_validate_huge_capacity(uint64_t len) { return (uint32_t)(len / msj_val::kWaveBody + 1); }
-
-extern "C" uint64_t msj_validate_workspace_bytes(uint64_t n, uint64_t len) {
-    const uint64_t nb = (n + 1 + msj_val::kBlock - 1) / msj_val::kBlock;
-    return sizeof(msj_val::State) + 4ull * msj_validate_long_capacity(len) + 4ull * msj_validate_huge_capacity(len) + 4ull * nb + 64;
-}
+extern "C" uint64_t msj_validate_workspace_bytes(uint64_t n, uint64_t len) { return msj_measure(msj_val::layout, n, len) + 64; }
 
 extern "C" int msj_launch_validate(const msj_token_view &t, const msj_number_view &nv, uint32_t max_depth, msj_validate_result *d_result,
                                    void *d_ws, void *stream) {
     using namespace msj_val;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    State *st = static_cast<State *>(d_ws);
-    const uint32_t long_cap = msj_validate_long_capacity(t.len), huge_cap = msj_validate_huge_capacity(t.len);
-    uint32_t *long_list = reinterpret_cast<uint32_t *>(st + 1);
-    uint32_t *huge_list = long_list + long_cap;
-    uint32_t *block_esc = huge_list + huge_cap;  // one count per block of val_tokens
-    const uint32_t nb = (uint32_t)((t.n + 1 + kBlock - 1) / kBlock);  // token n, the end of the stream, is judged too
-    hipLaunchKernelGGL(val_init, dim3(1), dim3(1), 0, s, st);
-    hipLaunchKernelGGL(val_tokens, dim3(nb), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_depth, t.d_match, t.d_end, t.d_flags,
-                       max_depth, st, long_list, long_cap, huge_list, huge_cap, block_esc);
-    hipLaunchKernelGGL(val_strings, dim3(kListBlocks), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.d_end, st, long_list, long_cap, huge_list,
-                       huge_cap);
-    hipLaunchKernelGGL(val_count, dim3(kListBlocks * 4), dim3(kThreads), 0, s, t.d_type, t.d_depth, t.n, st);
-    hipLaunchKernelGGL(val_finish, dim3(1), dim3(kThreads), 0, s, st, t.d_idx, t.n, t.len, nv.d_numbers_result, block_esc, nb, d_result);
+    const Work w = msj_place(layout, d_ws, t.n, t.len);
+    hipLaunchKernelGGL(val_init, dim3(1), dim3(1), 0, s, w.st);
+    hipLaunchKernelGGL(val_tokens, dim3(w.nb), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.n, t.d_type, t.d_depth, t.d_match, t.d_end, t.d_flags,
+                       max_depth, w.st, w.long_list, w.long_cap, w.huge_list, w.huge_cap, w.block_esc);
+    hipLaunchKernelGGL(val_strings, dim3(kListBlocks), dim3(kThreads), 0, s, t.d_buf, t.len, t.d_idx, t.d_end, w.st, w.long_list, w.long_cap, w.huge_list,
+                       w.huge_cap);
+    hipLaunchKernelGGL(val_count, dim3(kListBlocks * 4), dim3(kThreads), 0, s, t.d_type, t.d_depth, t.n, w.st);
+    hipLaunchKernelGGL(val_finish, dim3(1), dim3(kThreads), 0, s, w.st, t.d_idx, t.n, t.len, nv.d_numbers_result, w.block_esc, w.nb, d_result);
     return (int)hipGetLastError();
 }
