@@ -1411,8 +1411,8 @@ uint64_t msj_raw_column_workspace_bytes(uint64_t n, uint64_t capacity, uint32_t 
  * d_result 8-byte; d_codes, d_dict_first 4-byte; d_bytes, d_valid, d_dict_bytes any: MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of them.  Asynchronous on `stream`, no host round trip, workspace in the
  * context.  Safe on ANY arrays: d_bytes is read only inside [0, bytes_len), every store to the dictionary arrays is checked
  * against its capacity, nothing at or past R is touched.
- * Out of scope: counts per value (bincount of the codes; the Python layer does that), a dictionary shared across windows,
- * ordering the dictionary by value, case or Unicode folding.
+ * Out of scope: counts per value (bincount of the codes; the Python layer does that), ordering the dictionary by value,
+ * case or Unicode folding.  One dictionary across windows is msj_dictionary_extend_device, below.
  */
 #define MSJ_DICTIONARY_WEAK_HASH 1u   /* msj_dictionary_device flags: TEST AID, every chain in the table's last four slots */
 typedef struct msj_dictionary_result {   /* 48 bytes */
@@ -1435,6 +1435,75 @@ int32_t msj_dictionary_device(msj_ctx *ctx,
 /* Device workspace of one msj_dictionary_device call (the context keeps it): 8 + 4 bytes per row (hash, slot), 4 bytes per
  * table slot (the power of two >= 2 * rows, at least 1 024), 16 per 256 rows (block sums), a list of 1 024 long rows. */
 uint64_t msj_dictionary_workspace_bytes(uint64_t rows);
+
+/*
+ * ---- one dictionary across windows (DERIVED) -----------------------------------------------------------
+ * msj_dictionary_extend_device -- msj_dictionary_device against the P entries the dictionary arrays hold already: a value
+ * keeps its code from window to window, so counts per code add, msj_aggregate_device's group g is the same value in every
+ * window, and a filter or a sort by code means the same everywhere.  With MSJ_DICTIONARY_FROZEN it encodes against a FIXED
+ * vocabulary -- a reference table's codes, a model's categories, an IN-list: the semi-join on the device.
+ * The column, R, the row test (checked, never believed) and equality byte for byte are msj_dictionary_device's.
+ * The prior dictionary: P = d_n_prior ? *d_n_prior : n_prior, read on the device (&previous_result->n_distinct chains window
+ * after window without a host wait).  It is d_dict_offsets[0 .. P] and the bytes below base = d_dict_offsets[P], as an earlier
+ * call of either dictionary call wrote them into these arrays; with P = 0 the call writes d_dict_offsets[0] = 0 itself and
+ * base = 0.  Prior entry c < P has a value iff d_dict_offsets[c] <= d_dict_offsets[c + 1] <= dict_bytes_capacity -- checked
+ * on the array; an entry without a value equals no row and stays where it is.
+ *   d_codes      with d = {entry c's bytes: c} over the prior entries in ascending c (the lowest c wins among equal
+ *                entries), what `for v in rows: d.setdefault(v, len(d))` gives: a row with a prior value gets that entry's
+ *                code, a new value P plus the number of new values whose first row lies in front of its own first row, a
+ *                null row -1
+ *   appended     the new values in code order: d_dict_offsets[c + 1] for c >= P, d_dict_first[c] the row of THIS column
+ *                that first holds the value, the bytes behind base
+ * NOTHING OF THE PRIOR DICTIONARY IS WRITTEN: no entry of d_dict_offsets at or below P (but [0] when P = 0), no
+ * d_dict_first[c] for c < P, no byte below base -- the first piece of the byte copy starts at base itself, whatever its
+ * alignment.  Clipping is msj_dictionary_device's rule: the codes are complete, n_distinct (= P + new values) and dict_bytes
+ * (= base + new bytes) exact, what does not fit is not written, and the code is MSJ_CAPACITY.  Because nothing below P / base
+ * is ever written, a caller who gets MSJ_CAPACITY copies the prior part into larger arrays and REPEATS THE CALL WITH THE SAME
+ * P for the complete answer; repeating any call with the same P gives the same bytes.
+ * All three dictionary arrays NULL with both capacities 0 is the layout-only form, legal only with P = 0: codes and counts.
+ * R > rows, P > dict_capacity, base > dict_bytes_capacity or P + R >= 2^31: MSJ_CAPACITY, and nothing but code, flags,
+ * n_rows and n_prior is written (the other members are 0) -- so a clipped previous call chained through d_n_prior stops
+ * the chain by itself.
+ * MSJ_DICTIONARY_FROZEN: the three dictionary arrays are read only; a row whose value is no prior entry's gets code -2;
+ * n_distinct = P, dict_bytes = base; the code is 0 unless one of the four conditions above holds.
+ * MSJ_DICTIONARY_WEAK_HASH keeps its meaning as a test aid, for prior entries and rows alike.
+ * Every output but max_probe is a pure function of the input, bit-identical from run to run.
+ * Arguments, checked in this order: NULL ctx / d_result; NULL d_offsets / d_valid / d_codes with rows > 0; NULL d_bytes with
+ * bytes_len > 0; NULL d_dict_offsets / d_dict_first with dict_capacity > 0; NULL d_dict_bytes with dict_bytes_capacity > 0;
+ * n_prior > 0 or d_n_prior != NULL with all three dictionary arrays NULL; a flag other than the two; MSJ_DICTIONARY_FROZEN
+ * with all three dictionary arrays NULL: MSJ_ERR_BAD_ARGUMENT.  Then alignment as in msj_dictionary_device, and d_n_prior
+ * 8-byte: MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of them.  Asynchronous on `stream`, no host round trip, workspace
+ * in the context.  Safe on ANY arrays: prior offsets are used only after the entry test, nothing at or past a capacity is
+ * written, nothing at or past R is touched.
+ * Out of scope: merging msj_aggregate records on the device (two 'd' sums do not merge exactly; that needs the 96-bit
+ * accumulators exposed); removing values from a dictionary; ordering it by value; a dictionary over more than 2^31 - 1
+ * items (P + R); a hash table kept between calls -- the prior entries are hashed again per call, one read of the
+ * dictionary's bytes.
+ */
+#define MSJ_DICTIONARY_FROZEN 2u   /* look up only: nothing is appended, a value that is not in the dictionary gets code -2 */
+typedef struct msj_dictionary_extend_result {   /* 64 bytes; the first 48 are msj_dictionary_result's members, in its order */
+    int32_t  code;        /* 0; MSJ_CAPACITY (one of the four conditions: nothing else written; or the dictionary clipped:
+                             codes complete, counts exact); MSJ_UNEXPECTED_ERROR: an item walked the whole table (never) */
+    uint32_t flags;       /* the call's flags */
+    uint64_t n_rows;      /* R */
+    uint64_t n_values;    /* rows that are not null */
+    uint64_t n_distinct;  /* P + the new values; frozen: P */
+    uint64_t dict_bytes;  /* base + the bytes of the new values, exact also when clipped; frozen: base */
+    uint64_t max_probe;   /* the longest probe sequence any item walked (a diagnostic; not a function of the input alone) */
+    uint64_t n_prior;     /* P */
+    uint64_t n_matched;   /* rows whose value is a prior entry's */
+} msj_dictionary_extend_result;
+int32_t msj_dictionary_extend_device(msj_ctx *ctx,
+        const uint64_t *d_offsets, const uint8_t *d_valid, uint64_t rows, const uint64_t *d_n_rows,
+        const uint8_t *d_bytes, uint64_t bytes_len,
+        uint64_t n_prior, const uint64_t *d_n_prior,
+        int32_t *d_codes,
+        uint64_t *d_dict_offsets, uint32_t *d_dict_first, uint64_t dict_capacity,
+        uint8_t *d_dict_bytes, uint64_t dict_bytes_capacity,
+        uint32_t flags, msj_dictionary_extend_result *d_result, void *stream);
+/* Device workspace of one msj_dictionary_extend_device call (the context keeps it): msj_dictionary_workspace_bytes' terms
+ * per ITEM, rows + dict_capacity of them (at most 2^31). */
+uint64_t msj_dictionary_extend_workspace_bytes(uint64_t rows, uint64_t dict_capacity);
 
 /*
  * ---- rows by predicate (DERIVED) --------------------------------------------------------------------

@@ -158,6 +158,12 @@ class MsjDictionaryResult(ctypes.Structure):
                 ("n_distinct", ctypes.c_uint64), ("dict_bytes", ctypes.c_uint64), ("max_probe", ctypes.c_uint64)]
 
 
+class MsjDictionaryExtendResult(ctypes.Structure):
+    """``msj_dictionary_extend_result`` (include/msj_stage1.h): ``msj_dictionary_result``'s members, then two more."""
+
+    _fields_ = MsjDictionaryResult._fields_ + [("n_prior", ctypes.c_uint64), ("n_matched", ctypes.c_uint64)]
+
+
 class MsjPredicate(ctypes.Structure):
     """``msj_predicate`` (include/msj_stage1.h)."""
 
@@ -232,6 +238,8 @@ MAX_PREDICATES, MAX_COLUMNS, MAX_OPERAND_BYTES = 16, 16, 255
 
 RAW_COMPACT = 1   # MSJ_RAW_COMPACT
 DICTIONARY_WEAK_HASH = 1   # MSJ_DICTIONARY_WEAK_HASH (a test aid)
+DICTIONARY_FROZEN = 2      # MSJ_DICTIONARY_FROZEN (msj_dictionary_extend_device: look up only)
+DICTIONARY_NO_ENTRY = -2   # ... the code of a row whose value the frozen dictionary does not hold
 FIELD_NO_BITS = 64
 NO_SUCH_FIELD, INCORRECT_TYPE, INVALID_JSON_POINTER = 20, 17, 22
 MAX_PATHS, MAX_PATH_SEGMENTS, MAX_SEGMENT_BYTES = 16, 8, 255
@@ -257,7 +265,7 @@ assert ctypes.sizeof(MsjDocumentTape) == 32 and ctypes.sizeof(MsjTapeDocumentsRe
 assert ctypes.sizeof(MsjField) == 16 and ctypes.sizeof(MsjSelectDocumentsResult) == 48
 assert ctypes.sizeof(MsjStringColumnResult) == 48 and ctypes.sizeof(MsjArrayColumnResult) == 48
 assert ctypes.sizeof(MsjObjectEntriesResult) == 48 and ctypes.sizeof(MsjRawColumnResult) == 48
-assert ctypes.sizeof(MsjDictionaryResult) == 48
+assert ctypes.sizeof(MsjDictionaryResult) == 48 and ctypes.sizeof(MsjDictionaryExtendResult) == 64
 
 _lib = None
 
@@ -434,6 +442,13 @@ def load():
                                           ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_dictionary_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_dictionary_workspace_bytes.argtypes = [ctypes.c_uint64]
+    lib.msj_dictionary_extend_device.restype = ctypes.c_int32
+    lib.msj_dictionary_extend_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                 ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_dictionary_extend_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_dictionary_extend_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
     lib.msj_predicates_create.restype = ctypes.c_int32
     lib.msj_predicates_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     lib.msj_predicates_destroy.restype = None

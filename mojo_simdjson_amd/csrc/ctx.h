@@ -116,6 +116,7 @@ struct msj_ctx {
     DeviceBuffer oent_ws;         // msj_object_entries_device: the same state and arrays (rows_block.h)
     DeviceBuffer rcol_ws;         // msj_raw_column_device: lengths per row, the list of long rows, P per token (compact)
     DeviceBuffer dict_ws;         // msj_dictionary_device: a hash and a slot per row, the table of rows, the block sums, the list of long rows
+    DeviceBuffer dictx_ws;        // msj_dictionary_extend_device: the same per ITEM (prior entries + rows), the table of items
     DeviceBuffer frow_ws;         // msj_filter_rows_device: the counters, a count per block of rows, a rank per row
     DeviceBuffer take_ws;         // msj_take_rows_device: the counters
     DeviceBuffer cast_ws;         // msj_cast_strings_device: the counters, the list of the rows the lane path leaves over

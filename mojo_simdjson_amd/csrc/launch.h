@@ -1,7 +1,7 @@
 // launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 /
 // f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
 // validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
-// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip.  Every launcher and every internal workspace size is declared
+// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, dictionary_extend_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip.  Every launcher and every internal workspace size is declared
 // here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
 // compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
 // (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.
@@ -202,6 +202,15 @@ extern "C" int msj_launch_dictionary(const uint64_t *d_offsets, const uint8_t *d
                                      const uint8_t *d_bytes, uint64_t bytes_len, int32_t *d_codes, uint64_t *d_dict_offsets,
                                      uint32_t *d_dict_first, uint64_t dict_capacity, uint8_t *d_dict_bytes, uint64_t dict_bytes_capacity,
                                      uint32_t flags, msj_dictionary_result *d_result, void *d_ws, void *stream);
+
+// ---- dictionary_extend_kernel.hip ----
+// the same column; n_prior / d_n_prior: P, the entries the dictionary arrays hold already (the word on the device wins); the
+// three dictionary arrays null: the layout-only form (P = 0); flags: MSJ_DICTIONARY_WEAK_HASH | MSJ_DICTIONARY_FROZEN
+extern "C" int msj_launch_dictionary_extend(const uint64_t *d_offsets, const uint8_t *d_valid, uint64_t rows, const uint64_t *d_n_rows,
+                                            const uint8_t *d_bytes, uint64_t bytes_len, uint64_t n_prior, const uint64_t *d_n_prior,
+                                            int32_t *d_codes, uint64_t *d_dict_offsets, uint32_t *d_dict_first, uint64_t dict_capacity,
+                                            uint8_t *d_dict_bytes, uint64_t dict_bytes_capacity, uint32_t flags,
+                                            msj_dictionary_extend_result *d_result, void *d_ws, void *stream);
 
 // ---- filter_rows_kernel.hip ----
 // d_predicates: the compiled predicates (filter_rows_math.h: Predicates) in device memory; d_fields: column c at c * stride;

@@ -2,7 +2,7 @@
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
 // window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
 // elements, the arrays inside list rows, an object's members as a map column, a selected value's JSON text as a column, a byte column as codes plus distinct
-// values, rows by predicate, strings cast to numbers, count / sum / min / max per group.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// values (in one window, or against a dictionary carried across windows), rows by predicate, strings cast to numbers, count / sum / min / max per group.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
 // see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
 #include <new>
 
@@ -533,6 +533,27 @@ int32_t msj_dictionary_device(msj_ctx *ctx, const uint64_t *d_offsets, const uin
     if (rc != MSJ_SUCCESS) return rc;
     return launched(msj_launch_dictionary(d_offsets, d_valid, rows, d_n_rows, d_bytes, bytes_len, d_codes, d_dict_offsets, d_dict_first,
                                           dict_capacity, d_dict_bytes, dict_bytes_capacity, flags, d_result, ctx->dict_ws.p, stream));
+}
+
+int32_t msj_dictionary_extend_device(msj_ctx *ctx, const uint64_t *d_offsets, const uint8_t *d_valid, uint64_t rows, const uint64_t *d_n_rows,
+                                     const uint8_t *d_bytes, uint64_t bytes_len, uint64_t n_prior, const uint64_t *d_n_prior, int32_t *d_codes,
+                                     uint64_t *d_dict_offsets, uint32_t *d_dict_first, uint64_t dict_capacity, uint8_t *d_dict_bytes,
+                                     uint64_t dict_bytes_capacity, uint32_t flags, msj_dictionary_extend_result *d_result, void *stream) {
+    const bool layout_only = !d_dict_offsets && !d_dict_first && !d_dict_bytes;
+    if (!ctx || !d_result) return MSJ_ERR_BAD_ARGUMENT;
+    if (rows > 0 && (!d_offsets || !d_valid || !d_codes)) return MSJ_ERR_BAD_ARGUMENT;
+    if (bytes_len > 0 && !d_bytes) return MSJ_ERR_BAD_ARGUMENT;
+    if (dict_capacity > 0 && (!d_dict_offsets || !d_dict_first)) return MSJ_ERR_BAD_ARGUMENT;
+    if (dict_bytes_capacity > 0 && !d_dict_bytes) return MSJ_ERR_BAD_ARGUMENT;
+    if ((n_prior > 0 || d_n_prior) && layout_only) return MSJ_ERR_BAD_ARGUMENT;
+    if ((flags & ~(MSJ_DICTIONARY_WEAK_HASH | MSJ_DICTIONARY_FROZEN)) != 0) return MSJ_ERR_BAD_ARGUMENT;
+    if ((flags & MSJ_DICTIONARY_FROZEN) && layout_only) return MSJ_ERR_BAD_ARGUMENT;
+    if (!all_aligned(8, d_offsets, d_n_rows, d_n_prior, d_dict_offsets, d_result) || !all_aligned(4, d_codes, d_dict_first)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->dictx_ws, msj_dictionary_extend_workspace_bytes(rows, dict_capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_dictionary_extend(d_offsets, d_valid, rows, d_n_rows, d_bytes, bytes_len, n_prior, d_n_prior, d_codes,
+                                                 d_dict_offsets, d_dict_first, dict_capacity, d_dict_bytes, dict_bytes_capacity, flags, d_result,
+                                                 ctx->dictx_ws.p, stream));
 }
 
 int32_t msj_predicates_create(msj_ctx *ctx, const msj_predicate *predicates, uint32_t n_predicates, uint32_t flags, msj_predicates **out) {

@@ -712,6 +712,46 @@ class Stage1Device:
         call(dict_capacity, dict_bytes_capacity, d_dict_offsets, d_dict_first, d_dict_bytes)
         return (read() if sync else d_result), d_codes, d_dict_offsets, d_dict_first, d_dict_bytes
 
+    def dictionary_extend(self, d_offsets, d_bytes, d_valid, d_dict_offsets=None, d_dict_first=None, d_dict_bytes=None, n_prior=0,
+                          d_n_prior=None, rows=None, d_n_rows=None, bytes_len=None, d_codes=None, dict_capacity=None,
+                          dict_bytes_capacity=None, frozen=False, weak_hash=False, d_result=None, sync=True):
+        """A byte column encoded against the entries the dictionary arrays hold already (``msj_dictionary_extend_device``): a
+        prior value keeps its code, a new one is appended behind the n_prior entries -- or, frozen=True, gets code -2 and
+        nothing is written to the three arrays.  The column, rows, d_n_rows, bytes_len and d_codes are ``dictionary``'s.
+        d_dict_offsets (int64, dict_capacity + 1), d_dict_first (int32, dict_capacity), d_dict_bytes (uint8,
+        dict_bytes_capacity): the caller's, as an earlier call of either dictionary call left them (a ``RunningDictionary``
+        of ``document_stream`` owns such three), all three or none; none is the layout-only form (codes and counts,
+        n_prior 0).  n_prior: the entries they hold; d_n_prior: an int64 device tensor whose first word is that number,
+        read on the device (the ``n_distinct`` of the previous call's result tensor: ``d_res[24:32].view(torch.int64)``), so
+        that window follows window with nothing waited for.  weak_hash: the test aid.  Returns
+        (``MsjDictionaryExtendResult``, d_codes, d_dict_offsets, d_dict_first, d_dict_bytes) -- blocking for the 64-byte
+        result; with sync=False the device tensor that holds it, nothing waited for."""
+        rows = d_offsets.numel() - 1 if rows is None else int(rows)
+        bytes_len = d_bytes.numel() if bytes_len is None else int(bytes_len)
+        if d_codes is None:
+            d_codes = torch.empty(max(rows, 1), dtype=torch.int32, device=self.device)
+        if d_result is None:
+            d_result = torch.zeros(64, dtype=torch.uint8, device=self.device)
+        mine = (d_dict_offsets, d_dict_first, d_dict_bytes)
+        if any(t is None for t in mine) != all(t is None for t in mine):
+            raise ValueError("d_dict_offsets, d_dict_first and d_dict_bytes: all three or none")
+        if d_dict_offsets is None:
+            dict_capacity = dict_bytes_capacity = 0
+        else:
+            if dict_capacity is None:
+                dict_capacity = min(d_dict_offsets.numel() - 1, d_dict_first.numel())
+            if dict_bytes_capacity is None:
+                dict_bytes_capacity = d_dict_bytes.numel()
+        flags = (_lib.DICTIONARY_WEAK_HASH if weak_hash else 0) | (_lib.DICTIONARY_FROZEN if frozen else 0)
+        rc = self.lib.msj_dictionary_extend_device(self.ctx, _ptr(d_offsets), _ptr(d_valid), rows, _opt(d_n_rows), _ptr(d_bytes), bytes_len,
+                                                   int(n_prior), _opt(d_n_prior), _ptr(d_codes), _opt(d_dict_offsets), _opt(d_dict_first),
+                                                   int(dict_capacity), _opt(d_dict_bytes), int(dict_bytes_capacity), flags,
+                                                   _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_dictionary_extend_device failed: {rc}")
+        res = _lib.MsjDictionaryExtendResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_codes, d_dict_offsets, d_dict_first, d_dict_bytes
+
     def compile_predicates(self, specs, any=False):
         """Compile 1 to 16 row predicates for ``filter_rows`` (``msj_predicates_create``).  A spec is a tuple (column, op,
         operand): ``(0, "==", "error")``, ``(0, "prefix", b"err")``, ``(1, ">", 250)``, ``(1, "<=", 0.5)``, ``(2, "type",

@@ -325,6 +325,77 @@ def _dictionary(window, column, what):
     return DictionaryColumn(codes[:rows], d_off[:n + 1], d_bytes[:int(res.dict_bytes)], d_first[:n], valid)
 
 
+class RunningDictionary:
+    """The dictionary a stream carries from window to window ON THE DEVICE (``msj_dictionary_extend_device``): it owns the
+    three dictionary tensors -- offsets int64[dict_capacity + 1], first int32[dict_capacity], bytes uint8[bytes_capacity] --
+    and knows how many entries they hold.  ``win.categories("/status", dictionary=rd)`` encodes a window's column against
+    it, so that a value has ONE code in every window: ``counts()`` add, ``stats(..., by=..., dictionary=rd)`` give records
+    that merge by position.  The tensors grow when a window's new values do not fit; a ``DictionaryColumn`` handed out
+    before keeps the tensors it was made over.  One column per RunningDictionary: values of two columns share codes only
+    when that is wanted."""
+
+    def __init__(self, dev, dict_capacity=1024, bytes_capacity=16384):
+        self.dev = dev
+        self._n = self._n_bytes = 0
+        self._allocate(max(int(dict_capacity), 1), max(int(bytes_capacity), 1))
+
+    def _allocate(self, dict_capacity, bytes_capacity):
+        """New tensors of these capacities with the entries held so far copied over on the device"""
+        device = self.dev.device
+        offsets = torch.zeros(dict_capacity + 1, dtype=torch.int64, device=device)
+        first = torch.zeros(dict_capacity, dtype=torch.int32, device=device)
+        data = torch.zeros(bytes_capacity, dtype=torch.uint8, device=device)
+        if self._n:
+            offsets[:self._n + 1] = self.offsets[:self._n + 1]
+            first[:self._n] = self.first[:self._n]
+            data[:self._n_bytes] = self.bytes[:self._n_bytes]
+        self.offsets, self.first, self.bytes = offsets, first, data
+
+    @property
+    def n_distinct(self):
+        return self._n
+
+    @property
+    def dict_capacity(self):
+        return self.first.shape[0]
+
+    @property
+    def bytes_capacity(self):
+        return self.bytes.shape[0]
+
+    def values(self):
+        """The values as str in code order: the dictionary comes to the host."""
+        off, data = self.offsets[:self._n + 1].cpu().tolist(), self.bytes[:self._n_bytes].cpu().numpy().tobytes()
+        return [data[off[c]:off[c + 1]].decode("utf-8", "surrogateescape") for c in range(self._n)]
+
+    def encode(self, column, frozen=False, what="a column"):
+        """A column (offsets int64[rows + 1], bytes uint8[total], valid bool[rows]) as the column calls return it, encoded
+        against this dictionary -> ``DictionaryColumn``: codes int32[rows] in THIS dictionary's numbering; offsets and bytes
+        are views of the running dictionary as it stands after the call; first holds -1 for the values that came from
+        earlier windows, else the row of this column; so ``counts()`` has ``n_distinct`` entries of the running dictionary.
+        New values are appended; where they do not fit (MSJ_CAPACITY from clipping) the tensors are grown -- at least
+        doubled, at least to what the result names --, the prior part copied on the device and the call repeated with the
+        same number of prior entries.  frozen=True: nothing is appended, a value the dictionary does not hold gets -2.  Any
+        other code raises ``DocumentStreamError``.  The call's 64-byte result comes to the host."""
+        offsets, data, valid = column
+        rows = valid.shape[0]
+        d_valid = _or_blank(valid.view(torch.uint8), rows)
+        while True:
+            res, codes, _, _, _ = self.dev.dictionary_extend(offsets, data, d_valid, self.offsets, self.first, self.bytes, n_prior=self._n,
+                                                             rows=rows, frozen=frozen)
+            need, need_bytes = int(res.n_distinct), int(res.dict_bytes)
+            if res.code != errors.CAPACITY or (need <= self.dict_capacity and need_bytes <= self.bytes_capacity):
+                break  # (not clipped: done, or one of the conditions under which nothing is written)
+            self._allocate(max(need, 2 * self.dict_capacity) if need > self.dict_capacity else self.dict_capacity,
+                           max(need_bytes, 2 * self.bytes_capacity) if need_bytes > self.bytes_capacity else self.bytes_capacity)
+        if res.code != 0 or res.n_rows != rows or res.n_prior != self._n:
+            raise DocumentStreamError(int(res.code), f"{what} could not be encoded against the running dictionary")
+        prior, self._n, self._n_bytes = self._n, need, need_bytes
+        first = torch.full((need,), -1, dtype=torch.int32, device=codes.device)
+        first[prior:] = self.first[prior:need]
+        return DictionaryColumn(codes[:rows], self.offsets[:need + 1], self.bytes[:need_bytes], first, valid)
+
+
 class GroupStats:
     """Count, sum, min and max per group ON THE DEVICE (``msj_aggregate_device``; ``Window.stats``, ``RowSelection.stats``,
     ``ElementFields.stats``, ``ListColumn.stats``).  keys: the ``DictionaryColumn`` of the grouping path, whose value g names
@@ -518,13 +589,20 @@ class _Records:
         w, fields, rows, p, what = self._at(path_or_index)
         return _string_column(w, fields, self.d_select, rows, p, bytes_capacity, what)
 
-    def categories(self, path_or_index, bytes_capacity=None):
+    def categories(self, path_or_index, bytes_capacity=None, dictionary=None, frozen=False):
         """The string values of one path in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over
         ``strings(path)``) -> ``DictionaryColumn``: codes int32[rows], -1 where the row has no string, else the value's
         number in the order of first appearance, and the distinct values once.  A low-cardinality column -- a status, a
-        country, a device id -- is grouped, compared and counted (``counts()``) without moving a byte to the host."""
+        country, a device id -- is grouped, compared and counted (``counts()``) without moving a byte to the host.
+        dictionary: a ``RunningDictionary``, against which the column is encoded instead (``RunningDictionary.encode``): a
+        value has the same code in every window.  frozen=True: nothing is added to it, a value it does not hold is -2."""
         column = self.strings(path_or_index, bytes_capacity)
-        return _dictionary(self._window, column, self._at(path_or_index)[-1])
+        what = self._at(path_or_index)[-1]
+        if dictionary is not None:
+            return dictionary.encode(column, frozen=frozen, what=f"window at {self._window.base}: the strings of {what}")
+        if frozen:
+            raise ValueError("frozen=True needs a dictionary")
+        return _dictionary(self._window, column, what)
 
     def raw(self, path_or_index, compact=False, bytes_capacity=None):
         """The JSON text of one path's values as a column ON THE DEVICE (``msj_raw_column_device``): (offsets int64[rows + 1],
@@ -555,23 +633,28 @@ class _Records:
         w, fields, rows, p, what = self._at(path_or_index)
         return _object_entries(w, fields[p], self.d_select, rows, entries_capacity, self._parent, what)
 
-    def stats(self, paths, by=None, cast=None):
+    def stats(self, paths, by=None, cast=None, dictionary=None, frozen=False):
         """Count, sum, min and max of paths per group ON THE DEVICE (``msj_aggregate_device``) -> ``GroupStats``:
         ``win.stats(["/latency_ms"], by="/status")`` is how many lines, what total, smallest and largest latency per status.
         by: a path whose strings are dictionary-encoded first (``categories``): group g is the g-th distinct value, a row
         without a string is in no group; None: all rows are one group.  An int64 stays an int64 -- the sum of integers is
         the exact integer while it fits -- and a sum with doubles is rounded once: the same bits from run to run and for every
         order of the lines.  cast: ``{"/ts": ("timestamp", "ms"), "/price": "number"}`` as in ``where``, so that a timestamp
-        has a minimum and a maximum and a quoted number a sum.  The call's 48-byte result comes to the host."""
-        return self._grouped(paths, by, cast)
+        has a minimum and a maximum and a quoted number a sum.  The call's 48-byte result comes to the host.
+        dictionary: a ``RunningDictionary`` for `by` (``categories``): the groups are then ITS values, n_groups its
+        n_distinct after this window, so that record g is the same value in every window and the windows' records merge
+        by position (include/msj_stage1.h, "Merging two windows' records"); frozen=True as in ``categories``."""
+        return self._grouped(paths, by, cast, dictionary=dictionary, frozen=frozen)
 
-    def _grouped(self, paths, by, cast, d_list_offsets=None):
+    def _grouped(self, paths, by, cast, d_list_offsets=None, dictionary=None, frozen=False):
         """``stats``; d_list_offsets: a list column's offsets over these rows, for a group per row of it -- the element's
         row number, computed from the offsets with torch, being its code"""
         w, fields, index = self._window, self._records, self.paths.index
         rows = fields.shape[1]
         columns = [index(p) for p in paths]
-        keys = self.categories(by) if by is not None else None
+        if by is None and (dictionary is not None or frozen):
+            raise ValueError("a dictionary groups the rows of `by`")
+        keys = self.categories(by, dictionary=dictionary, frozen=frozen) if by is not None else None
         if keys is not None:
             d_codes, n_groups = keys.codes, keys.n_distinct
         elif d_list_offsets is not None:
@@ -652,11 +735,11 @@ class MapColumn:
         (offsets int64[n_entries + 1], bytes uint8[total], valid bool[n_entries])."""
         return self._keys.strings(0, bytes_capacity)
 
-    def key_categories(self, bytes_capacity=None):
+    def key_categories(self, bytes_capacity=None, dictionary=None, frozen=False):
         """The keys in the dictionary layout ON THE DEVICE (``msj_dictionary_device`` over ``keys()``) ->
         ``DictionaryColumn`` with one code per entry: the same few names repeated millions of times become one int32 each
-        and the names once."""
-        return self._keys.categories(0, bytes_capacity)
+        and the names once.  dictionary, frozen: a ``RunningDictionary`` to encode against, as in ``Window.categories``."""
+        return self._keys.categories(0, bytes_capacity, dictionary=dictionary, frozen=frozen)
 
     def schema(self):
         """Which keys these objects have: for each distinct key in the order of first appearance (the key, how many entries
@@ -738,10 +821,11 @@ class ListColumn:
         valid bool[n_elements])."""
         return self._one.strings(0, bytes_capacity)
 
-    def categories(self, bytes_capacity=None):
+    def categories(self, bytes_capacity=None, dictionary=None, frozen=False):
         """The elements that are strings in the dictionary layout ON THE DEVICE -> ``DictionaryColumn`` with one code per
-        element, -1 where the element is no string."""
-        return self._one.categories(0, bytes_capacity)
+        element, -1 where the element is no string.  dictionary, frozen: a ``RunningDictionary`` to encode against, as in
+        ``Window.categories``."""
+        return self._one.categories(0, bytes_capacity, dictionary=dictionary, frozen=frozen)
 
     def raw(self, compact=False, bytes_capacity=None):
         """The JSON text of every element as a column on the device: (offsets int64[n_elements + 1], bytes uint8[total],
@@ -836,14 +920,14 @@ class ElementFields(_Records):
         """The numbers of one path as ``number_column`` gives them: (values dtype[n_elements], valid bool[n_elements])."""
         return self._number_column(path_or_index, dtype)
 
-    def stats(self, paths, by=None, cast=None, per_row=False):
+    def stats(self, paths, by=None, cast=None, per_row=False, dictionary=None, frozen=False):
         """Count, sum, min and max of paths of the elements ON THE DEVICE (``msj_aggregate_device``) -> ``GroupStats``, see
         ``Window.stats``.  by: a path whose strings group the elements; per_row=True instead: a group per row of the list
         column -- ``sum(items[*].qty)`` per document -- the element's row number, computed from the offsets with torch,
-        being its code."""
+        being its code.  dictionary, frozen: a ``RunningDictionary`` for `by`, as in ``Window.stats``."""
         if by is not None and per_row:
             raise ValueError("by and per_row exclude each other")
-        return self._grouped(paths, by, cast, self.list_column.offsets if per_row else None)
+        return self._grouped(paths, by, cast, self.list_column.offsets if per_row else None, dictionary=dictionary, frozen=frozen)
 
     def where(self, specs, any=False, cast=None):
         """The elements whose fields pass predicates -- ``items[*].qty > 1`` -- ON THE DEVICE (``msj_filter_rows_device`` with
