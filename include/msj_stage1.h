@@ -1890,6 +1890,77 @@ uint64_t msj_sort_rows_workspace_bytes(uint64_t capacity);
 int32_t msj_debug_set_sort_mode(msj_ctx *ctx, uint32_t mode);
 
 /*
+ * msj_join_rows_device answers "which row of the users file does this event's /user_id match" on the device: the equi-join
+ * of two int32 code columns, as row pairs.  The codes are those of ONE dictionary (msj_dictionary_extend_device over both
+ * sides: the right column encoded, the left one encoded or looked up with MSJ_DICTIONARY_FROZEN), so equal values have equal
+ * codes in both.  What it writes is a pair of selection vectors, the kind msj_sort_rows_device writes: msj_take_rows_device
+ * gathers any columns of either side by them, and no key, no count and no row number reaches the host.
+ * Row counts: L = d_n_left ? *d_n_left : left_rows, R and G (the dictionary's entries) the same way, all three read on the
+ * device -- &dictionary_result->n_rows, &extend_result->n_distinct -- so a join follows two dictionary calls without a host
+ * wait.  left_rows / right_rows are also the rooms of the key arrays.
+ * Keys: an int32 is a key iff it lies in [0, G).  Anything else equals nothing, itself included: -1 (null), -2 (a frozen
+ * miss), a code from a later window.  match(l): the right rows r < R with d_right_keys[r] == d_left_keys[l], ascending;
+ * empty for a left row without a key.  c(l) = |match(l)|; row l emits n(l) pairs:
+ *   MSJ_JOIN_INNER  n = c            (l, r) for r in match(l)
+ *   MSJ_JOIN_LEFT   n = max(c, 1)    as INNER; (l, MSJ_JOIN_NO_ROW) when c == 0
+ *   MSJ_JOIN_SEMI   n = c > 0        (l, match(l)[0])
+ *   MSJ_JOIN_ANTI   n = c == 0       (l, MSJ_JOIN_NO_ROW)
+ * Outputs: M = the sum of n(l).  d_left_rows[0 .. M) / d_right_rows[0 .. M): the pairs in ascending l and, inside a row, in
+ * ascending r.  The answer is unique and every output byte is a pure function of the input, the same from run to run.
+ * d_right_rows may be NULL (SEMI / ANTI callers) and is then not written.  d_offsets: NULL, or room for left_rows + 1
+ * words: d_offsets[l] = the sum of n(l') for l' < l, d_offsets[L] = M -- with it the result is also a list column over the
+ * left rows, a group join.  d_left_select / d_right_select: each NULL, or it receives what msj_sort_rows_device writes to
+ * d_order_select: code = this call's, n_documents = n_found = M, n_paths = 1, n_no_bits = 0 -- msj_take_rows_device takes
+ * either vector as d_take with no host wait.  MSJ_JOIN_NO_ROW is at or past any R, so the missing side of a LEFT or ANTI
+ * pair comes out of msj_take_rows_device as the record of a missing value (code 20).  Nothing at or past M is written.
+ * d_result: L > left_rows, R > right_rows, G > keys_capacity, or L or R >= 2^31: MSJ_CAPACITY with the flags and the three
+ * counts, both select results the same code with M = 0, nothing else written.  M > pairs_capacity: MSJ_CAPACITY with every
+ * counter exact and d_offsets complete; nothing is written to the pair arrays and both select results carry the code, so a
+ * take behind it gives a zero result; the caller repeats the call with n_pairs entries of room.  L == 0, R == 0 or G == 0:
+ * the same definition (M == 0, or L pairs for LEFT / ANTI).
+ * Arguments, checked in this order: NULL ctx / d_result; a NULL key array with rows > 0; NULL d_left_rows with
+ * pairs_capacity > 0; an unknown flag; d_offsets overlapping a key array or a count word: MSJ_ERR_BAD_ARGUMENT.  A room or
+ * capacity of 2^40 or more: MSJ_CAPACITY.  Then alignment -- the keys and the rows 4-byte; the offsets, the counts and the
+ * results 8-byte -- and a select result that is d_result: MSJ_ERR_BAD_ARGUMENT.  Nothing is
+ * launched on any of them.  Asynchronous on `stream`, no host round trip, workspace in the context (about 4 bytes per key of
+ * keys_capacity, 17 per row of right_rows, 12 per row of left_rows).  Safe on ANY arrays: a key is read only below L / R,
+ * nothing at or past M, pairs_capacity or d_offsets[L] is written, and keys_capacity bounds every table.
+ * How: the right rows are ordered by key with a stable least-significant-digit radix sort over the eight-bit digits that
+ * tell the keys of [0, G) apart (G <= 256: one pass; the first pass also leaves out the rows without a key, so there is
+ * always one); a scan of count[key] gives every key's run; the pairs are then written by OUTPUT position, each lane finding
+ * its left row by binary search in the offsets, so a key held by millions of rows is spread over the grid like any other.
+ * Out of scope: keys that are not dense codes; numeric equality (3 against 3.0: cast first); more than one key column
+ * (combine the codes first); right and full outer joins (swap the sides); a shortcut for unique right keys; joins across
+ * more than 2^31 - 1 rows a side; a hash table kept between calls.
+ */
+#define MSJ_JOIN_INNER 0u   /* flags & 3: the kind */
+#define MSJ_JOIN_LEFT  1u
+#define MSJ_JOIN_SEMI  2u
+#define MSJ_JOIN_ANTI  3u
+#define MSJ_JOIN_NO_ROW 0xFFFFFFFFu
+typedef struct msj_join_rows_result {   /* 64 bytes */
+    int32_t  code;            /* 0; MSJ_CAPACITY */
+    uint32_t flags;           /* the call's flags */
+    uint64_t n_left, n_right, n_keys;   /* L, R, G as read on the device */
+    uint64_t n_pairs;         /* M, exact also when the pair arrays were too small */
+    uint64_t n_left_matched;  /* left rows with at least one partner */
+    uint64_t n_left_null;     /* left rows whose key lies outside [0, G) */
+    uint64_t n_right_null;    /* right rows whose key lies outside [0, G) */
+} msj_join_rows_result;
+int32_t msj_join_rows_device(msj_ctx *ctx,
+        const int32_t *d_left_keys,  uint64_t left_rows,  const uint64_t *d_n_left,
+        const int32_t *d_right_keys, uint64_t right_rows, const uint64_t *d_n_right,
+        uint64_t n_keys, const uint64_t *d_n_keys, uint64_t keys_capacity,
+        uint32_t flags,
+        uint32_t *d_left_rows, uint32_t *d_right_rows, uint64_t pairs_capacity,
+        uint64_t *d_offsets,
+        msj_join_rows_result *d_result,
+        msj_select_documents_result *d_left_select, msj_select_documents_result *d_right_select,
+        void *stream);
+/* Device workspace of one msj_join_rows_device call (the context keeps it). */
+uint64_t msj_join_rows_workspace_bytes(uint64_t left_rows, uint64_t right_rows, uint64_t keys_capacity);
+
+/*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors
  * under include/): allocation on the context's device and blocking copies.  Plumbing, not part of the path.
  */

@@ -222,6 +222,19 @@ class MsjSortRowsResult(ctypes.Structure):
 SORT_DESCENDING, SORT_VALUES_ONLY = 1, 2
 SORT_MODE_AUTO, SORT_MODE_FULL, SORT_MODE_SELECT = 0, 1, 2
 
+class MsjJoinRowsResult(ctypes.Structure):
+    """``msj_join_rows_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_left", ctypes.c_uint64), ("n_right", ctypes.c_uint64),
+                ("n_keys", ctypes.c_uint64), ("n_pairs", ctypes.c_uint64), ("n_left_matched", ctypes.c_uint64),
+                ("n_left_null", ctypes.c_uint64), ("n_right_null", ctypes.c_uint64)]
+
+
+# msj_join_rows_device: the kind (flags & 3); the right side of a pair without one
+JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3
+JOIN_KINDS = {"inner": JOIN_INNER, "left": JOIN_LEFT, "semi": JOIN_SEMI, "anti": JOIN_ANTI}
+JOIN_NO_ROW = 0xFFFFFFFF
+
 # msj_cast_strings_device: kind, unit, flags; msj_debug_set_cast_fetch
 CAST_TIMESTAMP, CAST_NUMBER = 1, 2
 CAST_KINDS = {"timestamp": CAST_TIMESTAMP, "number": CAST_NUMBER}
@@ -487,6 +500,13 @@ def load():
     lib.msj_sort_rows_workspace_bytes.argtypes = [ctypes.c_uint64]
     lib.msj_debug_set_sort_mode.restype = ctypes.c_int32
     lib.msj_debug_set_sort_mode.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    lib.msj_join_rows_device.restype = ctypes.c_int32
+    lib.msj_join_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]
+    lib.msj_join_rows_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_join_rows_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

@@ -1,7 +1,7 @@
 // launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 /
 // f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
 // validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
-// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, dictionary_extend_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip.  Every launcher and every internal workspace size is declared
+// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, dictionary_extend_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip, join_rows_kernel.hip.  Every launcher and every internal workspace size is declared
 // here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
 // compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
 // (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.
@@ -250,3 +250,12 @@ extern "C" int msj_launch_sort_rows(const msj_field *d_fields, uint64_t stride, 
                                     const uint32_t *d_rows_in, const msj_select_documents_result *d_rows_in_select, uint32_t flags, uint64_t limit,
                                     uint32_t mode, uint32_t *d_order, uint64_t capacity, msj_sort_rows_result *d_result,
                                     msj_select_documents_result *d_order_select, void *d_ws, void *stream);
+
+// ---- join_rows_kernel.hip ----
+// the two key columns with their rooms and the counts on the device (or null for the room); n_keys / d_n_keys: G; flags:
+// MSJ_JOIN_*, checked by the caller; d_right_rows, d_offsets and the two select results: each may be null
+extern "C" int msj_launch_join_rows(const int32_t *d_left_keys, uint64_t left_rows, const uint64_t *d_n_left, const int32_t *d_right_keys,
+                                    uint64_t right_rows, const uint64_t *d_n_right, uint64_t n_keys, const uint64_t *d_n_keys,
+                                    uint64_t keys_capacity, uint32_t flags, uint32_t *d_left_rows, uint32_t *d_right_rows, uint64_t pairs_capacity,
+                                    uint64_t *d_offsets, msj_join_rows_result *d_result, msj_select_documents_result *d_left_select,
+                                    msj_select_documents_result *d_right_select, void *d_ws, void *stream);

@@ -2,7 +2,7 @@
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
 // window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
 // elements, the arrays inside list rows, an object's members as a map column, a selected value's JSON text as a column, a byte column as codes plus distinct
-// values (in one window, or against a dictionary carried across windows), rows by predicate, strings cast to numbers, count / sum / min / max per group.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// values (in one window, or against a dictionary carried across windows), rows by predicate, strings cast to numbers, count / sum / min / max per group, rows by numeric order, the equi-join of two code columns.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
 // see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
 #include <new>
 
@@ -10,6 +10,7 @@
 #include "aggregate_math.h"
 #include "cast_strings_math.h"
 #include "filter_rows_math.h"
+#include "join_rows_math.h"
 #include "select_math.h"
 
 // msj_paths_create's object: the compiled paths (select_math.h: Paths) in device memory, and what the host needs of them
@@ -708,6 +709,36 @@ int32_t msj_debug_set_sort_mode(msj_ctx *ctx, uint32_t mode) {
     if (!ctx || mode > 2u) return MSJ_ERR_BAD_ARGUMENT;
     ctx->sort_mode = mode;
     return MSJ_SUCCESS;
+}
+
+int32_t msj_join_rows_device(msj_ctx *ctx, const int32_t *d_left_keys, uint64_t left_rows, const uint64_t *d_n_left, const int32_t *d_right_keys,
+                             uint64_t right_rows, const uint64_t *d_n_right, uint64_t n_keys, const uint64_t *d_n_keys, uint64_t keys_capacity,
+                             uint32_t flags, uint32_t *d_left_rows, uint32_t *d_right_rows, uint64_t pairs_capacity, uint64_t *d_offsets,
+                             msj_join_rows_result *d_result, msj_select_documents_result *d_left_select,
+                             msj_select_documents_result *d_right_select, void *stream) {
+    if (!ctx || !d_result) return MSJ_ERR_BAD_ARGUMENT;
+    if ((left_rows > 0 && !d_left_keys) || (right_rows > 0 && !d_right_keys)) return MSJ_ERR_BAD_ARGUMENT;
+    if (pairs_capacity > 0 && !d_left_rows) return MSJ_ERR_BAD_ARGUMENT;
+    if (flags & ~msj::jrows::kKnownFlags) return MSJ_ERR_BAD_ARGUMENT;
+    if (d_offsets) {  // the offsets may not be written over what the call reads (128 bits: no room is too large to compare)
+        const auto overlaps = [&](const void *p, uint64_t count, uint64_t size) {
+            const unsigned __int128 a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(d_offsets);
+            return p && a < b + ((unsigned __int128)left_rows + 1) * 8 && b < a + (unsigned __int128)count * size;
+        };
+        if (overlaps(d_left_keys, left_rows, 4) || overlaps(d_right_keys, right_rows, 4) || overlaps(d_n_left, 1, 8) || overlaps(d_n_right, 1, 8) ||
+            overlaps(d_n_keys, 1, 8))
+            return MSJ_ERR_BAD_ARGUMENT;
+    }
+    if (left_rows >= (1ull << 40) || right_rows >= (1ull << 40) || keys_capacity >= (1ull << 40) || pairs_capacity >= (1ull << 40)) return MSJ_CAPACITY;
+    if (!all_aligned(4, d_left_keys, d_right_keys, d_left_rows, d_right_rows) ||
+        !all_aligned(8, d_offsets, d_n_left, d_n_right, d_n_keys, d_result, d_left_select, d_right_select))
+        return MSJ_ERR_BAD_ARGUMENT;
+    if ((const void *)d_result == (const void *)d_left_select || (const void *)d_result == (const void *)d_right_select) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->join_ws, msj_join_rows_workspace_bytes(left_rows, right_rows, keys_capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_join_rows(d_left_keys, left_rows, d_n_left, d_right_keys, right_rows, d_n_right, n_keys, d_n_keys, keys_capacity, flags,
+                                         d_left_rows, d_right_rows, pairs_capacity, d_offsets, d_result, d_left_select, d_right_select,
+                                         ctx->join_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

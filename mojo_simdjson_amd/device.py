@@ -958,6 +958,64 @@ class Stage1Device:
         res = _lib.MsjSortRowsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
         return res, d_order, d_order_select
 
+    def join_rows(self, d_left_keys, d_right_keys, n_keys=0, d_n_keys=None, keys_capacity=None, how="inner", left_rows=None, d_n_left=None,
+                  right_rows=None, d_n_right=None, pairs_capacity=None, d_left_rows=None, d_right_rows=None, right=True, d_offsets=None,
+                  offsets=False, d_result=None, d_left_select=None, d_right_select=None, sync=True):
+        """The equi-join of two int32 code columns as row pairs (``msj_join_rows_device``), all on the device.
+        d_left_keys / d_right_keys: contiguous int32 tensors, codes of ONE dictionary (``dictionary_extend`` over both
+        sides); left_rows / right_rows: their rows (default: their entries), which are also the rooms; d_n_left / d_n_right
+        / d_n_keys: int64 device tensors whose first word is L, R or G, read on the device -- ``d_res[8:16]`` of a
+        dictionary call's result is its n_rows, ``d_res[24:32]`` its n_distinct -- so a join follows two dictionary calls
+        with nothing waited for; n_keys: G otherwise; keys_capacity: the most G can be (default: n_keys).  A code outside
+        [0, G) -- -1, -2 -- equals nothing.  how: "inner", "left" (a left row without a partner is paired with
+        ``JOIN_NO_ROW``), "semi" (each left row with a partner once, with its first), "anti" (each left row without one).
+        Pairs come in ascending left row and, inside one, ascending right row.  pairs_capacity: the room of the pair
+        tensors (default: their entries, or the left rows); d_left_rows / d_right_rows: int32 tensors (default: new ones;
+        right=False: no right tensor, nothing written for it); d_offsets: int64 tensor of left_rows + 1 entries, or
+        offsets=True for a new one: the pairs in front of every left row, a list column over the left rows.
+        d_left_select / d_right_select: uint8[48] tensors that receive the ``msj_select_documents_result`` counting the
+        pairs -- with a pair tensor what ``take_rows`` takes as d_take / d_take_select.  A result with code 1
+        (MSJ_CAPACITY) and n_pairs above the room: nothing was written to the pair tensors; repeat with n_pairs entries.
+        Returns (``MsjJoinRowsResult``, d_left_rows, d_right_rows, d_offsets, d_left_select, d_right_select) -- blocking
+        for the 64-byte result; with sync=False the device tensor that holds it, nothing waited for."""
+        for t in (d_left_keys, d_right_keys):
+            if t.dtype != torch.int32 or t.stride(-1) != 1:
+                raise ValueError("the keys are contiguous int32 tensors")
+        if how not in _lib.JOIN_KINDS:
+            raise ValueError(f"how is one of {sorted(_lib.JOIN_KINDS)}: {how!r}")
+        left_rows = d_left_keys.numel() if left_rows is None else int(left_rows)
+        right_rows = d_right_keys.numel() if right_rows is None else int(right_rows)
+        keys_capacity = int(n_keys) if keys_capacity is None else int(keys_capacity)
+        if pairs_capacity is None:
+            pairs_capacity = d_left_rows.numel() if d_left_rows is not None else left_rows
+        pairs_capacity = int(pairs_capacity)
+        if d_left_rows is None:
+            d_left_rows = torch.empty((max(pairs_capacity, 1),), dtype=torch.int32, device=self.device)
+        if d_right_rows is None and right:
+            d_right_rows = torch.empty((max(pairs_capacity, 1),), dtype=torch.int32, device=self.device)
+        if d_offsets is None and offsets:
+            d_offsets = torch.empty((left_rows + 1,), dtype=torch.int64, device=self.device)
+        for t in (d_left_rows, d_right_rows):
+            if t is not None and (t.dtype != torch.int32 or t.numel() < pairs_capacity):
+                raise ValueError("the pair tensors are int32 with pairs_capacity entries")
+        if d_offsets is not None and (d_offsets.dtype != torch.int64 or d_offsets.numel() < left_rows + 1):
+            raise ValueError("d_offsets is an int64 tensor of left_rows + 1 entries")
+        if d_result is None:
+            d_result = torch.zeros(64, dtype=torch.uint8, device=self.device)
+        d_left_select, d_right_select = self._result(d_left_select), self._result(d_right_select)
+        rc = self.lib.msj_join_rows_device(self.ctx, _ptr(d_left_keys), left_rows, _opt(d_n_left), _ptr(d_right_keys), right_rows, _opt(d_n_right),
+                                           int(n_keys), _opt(d_n_keys), keys_capacity, _lib.JOIN_KINDS[how], _ptr(d_left_rows), _opt(d_right_rows),
+                                           pairs_capacity, _opt(d_offsets), _ptr(d_result), _ptr(d_left_select), _ptr(d_right_select),
+                                           self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_join_rows_device failed: {rc}")
+        res = _lib.MsjJoinRowsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_left_rows, d_right_rows, d_offsets, d_left_select, d_right_select
+
+    def join_rows_workspace_bytes(self, left_rows, right_rows, keys_capacity):
+        """The device workspace one ``join_rows`` call of these rooms keeps in the context (``msj_join_rows_workspace_bytes``)."""
+        return int(self.lib.msj_join_rows_workspace_bytes(int(left_rows), int(right_rows), int(keys_capacity)))
+
     def set_sort_mode(self, mode=_lib.SORT_MODE_AUTO):
         """Test hook: the path ``sort_rows`` takes -- 0 chosen on the device, 1 always the full sort, 2 always the
         selection.  The order does not change."""

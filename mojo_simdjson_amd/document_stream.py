@@ -983,6 +983,108 @@ class RowSelection(_Records):
         fields, d_fsel = self._taken(_or_blank(order, order.shape[0]), d_order_select, order.shape[0])
         return RowSelection(self.window, None, self.rows[order.to(torch.int64)], fields, d_fsel)
 
+    def join(self, other, on, right_on=None, how="inner", by="string", dictionary=None, pairs_capacity=None):
+        return _join(self, other, on, right_on, how, by, dictionary, pairs_capacity)
+
+
+class JoinedRows:
+    """The row pairs of an equi-join of two record views ON THE DEVICE (``msj_join_rows_device``; ``Window.join``,
+    ``RowSelection.join``).  left / right: a ``RowSelection`` each, over its own window, with one row per PAIR -- pair j is
+    row j of both --, so every method of a record view runs on the joined rows: ``joined.right.strings("/name")`` is the
+    user's name per event.  right is None for how="semi" / "anti"; for how="left" a left row without a partner has a right
+    row of missing values (records with code 20) and the row number -1.  left_rows / right_rows int32[n_pairs]: the pair
+    vectors as the call wrote them, row numbers of the two views joined (right_rows -1 where there is none; None for semi /
+    anti); offsets int64[L + 1]: the pairs in front of every left row -- with it the pairs are a list column over the left
+    rows, a group join; n_pairs; result: the call's ``MsjJoinRowsResult``.  Pairs come in ascending left row and, inside
+    one, ascending right row.  BOTH windows must be alive: a window's arrays are reused by its stream's next window."""
+
+    def __init__(self, left, right, left_rows, right_rows, offsets, result):
+        self.left, self.right, self.left_rows, self.right_rows, self.offsets, self.result = left, right, left_rows, right_rows, offsets, result
+
+    @property
+    def n_pairs(self):
+        return self.left_rows.shape[0]
+
+    def to_python(self, paths_left, paths_right=()):
+        """The pairs as a list of (left values, right values): a tuple of ``values(path)`` entries per side, the right one
+        None for semi / anti.  For tests: both windows come to the host."""
+        sides = [list(zip(*[self.left.values(p) for p in paths_left])) if paths_left else [()] * self.n_pairs]
+        if self.right is None:
+            return [(l, None) for l in sides[0]]
+        sides.append(list(zip(*[self.right.values(p) for p in paths_right])) if paths_right else [()] * self.n_pairs)
+        return list(zip(*sides))
+
+
+def _join_keys(view, path, by):
+    """The byte column whose equal values are equal join keys"""
+    if by == "string":
+        return view.strings(path)
+    if by == "raw":
+        return view.raw(path, compact=True)
+    raise ValueError(f'by is "string" or "raw": {by!r}')
+
+
+def _joined_side(view, d_rows, d_select, n_pairs):
+    """One side of the pairs as a ``RowSelection`` over the view's window: its records taken by the pair vector, its rows the
+    window's document numbers (-1 where the pair has no row of this side)"""
+    fields, d_fsel = view._taken(_or_blank(d_rows, n_pairs), d_select, n_pairs)
+    rows = d_rows
+    if isinstance(view, RowSelection):
+        ok = d_rows >= 0
+        at = torch.where(ok, d_rows, torch.zeros_like(d_rows)).to(torch.int64)
+        rows = torch.where(ok, _or_blank(view.rows, view.rows.shape[0])[at], torch.full_like(d_rows, -1)) if n_pairs else d_rows
+    return RowSelection(view._window, None, rows, fields, d_fsel)
+
+
+def _join(left, other, on, right_on, how, by, dictionary, pairs_capacity):
+    """``Window.join`` / ``RowSelection.join``"""
+    if not isinstance(other, (Window, RowSelection)):
+        raise TypeError("other is a Window or a RowSelection")
+    if how not in _lib.JOIN_KINDS:
+        raise ValueError(f"how is one of {sorted(_lib.JOIN_KINDS)}: {how!r}")
+    lw, rw = left._window, other._window
+    if lw.dev.device != rw.dev.device:
+        raise ValueError("the two sides lie on different devices")
+    dev = lw.dev
+    right_path = on if right_on is None else right_on
+    fresh = dictionary is None
+    rd = RunningDictionary(dev) if fresh else dictionary
+    # the right side first: with a fresh dictionary the left side only looks up, and a value it alone holds is -2, no key
+    right_keys = rd.encode(_join_keys(other, right_path, by), what=f"window at {rw.base}: the join keys of {other._rows_are}")
+    left_keys = rd.encode(_join_keys(left, on, by), frozen=fresh, what=f"window at {lw.base}: the join keys of {left._rows_are}")
+    L, R, G = left_keys.codes.shape[0], right_keys.codes.shape[0], rd.n_distinct
+    with_right = how in ("inner", "left")
+    room = max(L, 1) if pairs_capacity is None else int(pairs_capacity)
+    d_offsets = torch.empty(L + 1, dtype=torch.int64, device=dev.device)
+    for _ in range(2):
+        res, d_l, d_r, _, d_lsel, d_rsel = dev.join_rows(_or_blank(left_keys.codes, L), _or_blank(right_keys.codes, R), n_keys=G, how=how, left_rows=L,
+                                                         right_rows=R, pairs_capacity=room, right=with_right, d_offsets=d_offsets)
+        if res.code != errors.CAPACITY or res.n_pairs <= room:
+            break
+        room = int(res.n_pairs)
+    if res.code != 0:
+        raise DocumentStreamError(int(res.code), f"window at {lw.base}: {left._rows_are} could not be joined")
+    M = int(res.n_pairs)
+    d_l = d_l[:M]
+    d_r = d_r[:M] if with_right else None
+    return JoinedRows(_joined_side(left, d_l, d_lsel, M), _joined_side(other, d_r, d_rsel, M) if with_right else None, d_l, d_r, d_offsets, res)
+
+
+_JOIN_DOC = """The equi-join of these rows with `other`'s ON THE DEVICE (``msj_dictionary_extend_device`` twice, then
+        ``msj_join_rows_device`` and ``msj_take_rows_device``) -> ``JoinedRows``: ``events.join(users, "/user_id", "/id")``
+        pairs every event with the user it names.  other: a ``Window`` or ``RowSelection``, of another ``DocumentStream`` on
+        the same device or this very window (a self-join).  on / right_on: the key's path on this side and on the other
+        (default: the same).  by="string": the key is ``strings(path)``, the unescaped string; a value that is no string is
+        no key.  by="raw": the key is ``raw(path, compact=True)``, the value's compact JSON text, so numbers, booleans and
+        containers join as well -- by their TEXT: the number 7 matches 7 but neither 7.0 nor "7".  A row without a key
+        matches nothing.  how: "inner"; "left" (a row without a partner stays, its right side missing values); "semi" (each
+        row with a partner, once); "anti" (each row without one) -- for the last two ``.right`` is None.  Pairs come in the
+        order of these rows and, inside one, of the other's.  dictionary: a ``RunningDictionary`` both sides are encoded
+        into, so that the windows of a stream joined against one table share the codes; without one a fresh dictionary is
+        built from the other side and this side only looked up in it.  pairs_capacity: the first guess of the pairs' room
+        (default: these rows); the call is repeated once with what it asks for.  Only the calls' 64-byte results reach the
+        host.  BOTH windows must be alive: a window's arrays are reused by its stream's next window."""
+
 
 def _skip_flag(n):
     return (n & 15) << 24
@@ -1116,6 +1218,9 @@ class Window(_Records):
         fields, d_fsel = self._taken(_or_blank(rows, n), _select_word(rows.device, n), n)
         return RowSelection(self, None, rows, fields, d_fsel)
 
+    def join(self, other, on, right_on=None, how="inner", by="string", dictionary=None, pairs_capacity=None):
+        return _join(self, other, on, right_on, how, by, dictionary, pairs_capacity)
+
     def documents(self):
         """A ``Document`` per complete document, None for one with a verdict code (its code: ``d_doc_tapes`` / ``d_verdicts``).
         One copy of the three arrays to the host; the list is kept.  d_tape, d_string_buf and d_doc_tapes are views of
@@ -1146,6 +1251,9 @@ class Window(_Records):
         first = self.d_doc_first.cpu().numpy().astype("int64")
         idx = self.d_idx.cpu().numpy().view("uint32").astype("int64")
         return [self.base + int(idx[t]) for t in first]
+
+
+RowSelection.join.__doc__ = Window.join.__doc__ = _JOIN_DOC
 
 
 class DocumentStream:
