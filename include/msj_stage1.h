@@ -1411,7 +1411,8 @@ uint64_t msj_raw_column_workspace_bytes(uint64_t n, uint64_t capacity, uint32_t 
  * d_result 8-byte; d_codes, d_dict_first 4-byte; d_bytes, d_valid, d_dict_bytes any: MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of them.  Asynchronous on `stream`, no host round trip, workspace in the
  * context.  Safe on ANY arrays: d_bytes is read only inside [0, bytes_len), every store to the dictionary arrays is checked
  * against its capacity, nothing at or past R is touched.
- * Out of scope: counts per value (bincount of the codes; the Python layer does that), ordering the dictionary by value,
+ * Out of scope: counts per value (bincount of the codes; the Python layer does that), ordering the dictionary by value
+ * (msj_dictionary_order_device, below, orders its entries without rewriting it),
  * case or Unicode folding.  One dictionary across windows is msj_dictionary_extend_device, below.
  */
 #define MSJ_DICTIONARY_WEAK_HASH 1u   /* msj_dictionary_device flags: TEST AID, every chain in the table's last four slots */
@@ -1476,7 +1477,7 @@ uint64_t msj_dictionary_workspace_bytes(uint64_t rows);
  * in the context.  Safe on ANY arrays: prior offsets are used only after the entry test, nothing at or past a capacity is
  * written, nothing at or past R is touched.
  * Out of scope: merging msj_aggregate records on the device (two 'd' sums do not merge exactly; that needs the 96-bit
- * accumulators exposed); removing values from a dictionary; ordering it by value; a dictionary over more than 2^31 - 1
+ * accumulators exposed); removing values from a dictionary; ordering it by value (msj_dictionary_order_device); a dictionary over more than 2^31 - 1
  * items (P + R); a hash table kept between calls -- the prior entries are hashed again per call, one read of the
  * dictionary's bytes.
  */
@@ -1863,7 +1864,8 @@ int32_t msj_debug_set_aggregate_limits(msj_ctx *ctx, uint32_t lds_groups);
  * significant-digit histograms find the key of the K-th row, the rows below it and the first rows that equal it are
  * compacted in input order and only they are sorted.  msj_debug_set_sort_mode forces either so that tests compare them on
  * small inputs.
- * Out of scope: string keys (sort a dictionary's codes, or cast); nulls first; sorting msj_aggregate records; top-k per
+ * Out of scope: string keys here (msj_dictionary_order_device and msj_rank_rows_device give a string column ranks this call
+ * orders; or cast); nulls first; sorting msj_aggregate records; top-k per
  * group; merging sorted windows.
  */
 #define MSJ_SORT_DESCENDING  1u
@@ -1959,6 +1961,109 @@ int32_t msj_join_rows_device(msj_ctx *ctx,
         void *stream);
 /* Device workspace of one msj_join_rows_device call (the context keeps it). */
 uint64_t msj_join_rows_workspace_bytes(uint64_t left_rows, uint64_t right_rows, uint64_t keys_capacity);
+
+/*
+ * msj_dictionary_order_device answers "these rows by /name" and "the first ten hosts alphabetically" on the device: it
+ * orders the V distinct values of a dictionary once, so that every row's value has a rank, a number that
+ * msj_sort_rows_device, msj_filter_rows_device and msj_aggregate_device take (msj_rank_rows_device below).
+ * Entries: V = d_n_entries ? *d_n_entries : n_entries, read on the device -- &dictionary_result->n_distinct chains without
+ * a host wait.  Entry c < V has a value iff d_dict_offsets[c] <= d_dict_offsets[c + 1] <= dict_bytes_capacity (the
+ * prior-entry test of msj_dictionary_extend_device: checked, never believed); the value is those bytes, and the empty
+ * string is a value.  Arrays with equal values -- any offsets array a caller made -- are legal input.
+ * Order: values compare as unsigned bytes, lexicographically, a proper prefix first: memcmp, then length; for UTF-8 that is
+ * code-point order.  No collation, no case folding.
+ * d_sorted[V]: the entry numbers -- the entries with a value first, ascending by value, equal values by ascending entry
+ * number; then the entries without a value in entry order.  The answer is unique.  d_rank[V]: d_rank[c] = the number of
+ * entries whose value is smaller than entry c's; equal values share a rank, so for a real dictionary the ranks are a
+ * permutation of 0 .. V-1 and d_sorted[d_rank[c]] == c; an entry without a value gets MSJ_ORDER_NO_RANK.
+ * The partial order by depth B is the same definition with every value v replaced by its first B bytes, v[:B].  After a
+ * call has compared B bytes the two arrays hold exactly that.  An entry is TIED iff it shares its rank with another entry
+ * and its length is at least B: such entries agree on B bytes and may still differ behind them.  The order is complete iff
+ * no entry is tied.
+ * Rounds: a round compares the next eight bytes of the tied entries and runs only while an entry is tied.  A call runs at
+ * most max_rounds of them (1 .. 64; 0: the path's default, 64 rounds on the one-workgroup path and 4 on the grid path).
+ * Every launch is enqueued up front, sized by `capacity` (the room of d_sorted, d_rank and, plus one, d_dict_offsets); a
+ * kernel that finds nothing tied returns at once.
+ * d_result: code 0: complete, n_tied == 0.  The budget ended with entries still tied: MSJ_CAPACITY with n_tied > 0, and the
+ * arrays hold the order by the first `depth` bytes.  The caller repeats the call with MSJ_ORDER_CONTINUE: the two arrays are
+ * the state and `depth` the previous result's depth (8 x the rounds requested so far, so the host knows it without
+ * reading).  The chain gives the bytes one call with a large budget gives.  Without MSJ_ORDER_CONTINUE the arrays are
+ * written, not read, and depth must be 0.  result.depth: the argument plus 8 x the rounds that ran.  n_equal: the entries
+ * whose value an earlier entry also holds, as far as the depth shows (0 for a real dictionary).  V > capacity or V >= 2^31:
+ * MSJ_CAPACITY with n_entries = V, depth = 0, n_tied = 0, nothing else written.  V == 0: a zero result with the flags.
+ * Arguments, checked in this order: NULL ctx / d_result; NULL d_dict_offsets, d_sorted or d_rank with capacity > 0, NULL
+ * d_dict_bytes with dict_bytes_capacity > 0; an unknown flag, max_rounds > 64, a depth that is no multiple of 8, a depth
+ * without MSJ_ORDER_CONTINUE: MSJ_ERR_BAD_ARGUMENT.  A capacity of 2^40 or more: MSJ_CAPACITY.  Then alignment -- the
+ * offsets, d_n_entries and the result 8-byte, the two arrays 4-byte, the bytes any: MSJ_ERR_BAD_ARGUMENT.  Nothing is
+ * launched on any of them.  Asynchronous on `stream`, no host round trip, workspace in the context (about 49 bytes per
+ * entry of capacity; the one-workgroup path does not use it).
+ * Safe on ANY arrays: no byte outside [0, dict_bytes_capacity) is read, whatever the alignment of d_dict_bytes and of a
+ * value's end; an offset is read only at or below V.  With MSJ_ORDER_CONTINUE an entry of d_sorted at or past V is an entry
+ * without a value; garbage state gives unspecified but in-bounds output within the budget.  Nothing at or past V is
+ * written.  Every output is a pure function of the input, the same bytes from run to run.
+ * Two paths, the same bytes from both.  capacity <= 1 024: one workgroup keeps the arrays and the keys in LDS and loops
+ * over the rounds inside ONE kernel until nothing is tied or the budget ends.  Above: per round the tied entries are
+ * compacted, their words fetched, and ordered by a stable least-significant-digit radix sort over the key (rank, word,
+ * nvalid) in eight-bit digits -- a pass whose digit is the same in every tied entry is skipped, so a prefix shared inside a
+ * word costs nothing, and of the rank only the digits that tell [0, capacity) apart exist --, written back, and the new
+ * groups found by comparing neighbours and a scan.  msj_debug_set_order_mode forces either path.
+ * Out of scope: collation and case folding; string range predicates (the rank of an operand); string min / max in one
+ * call; skipping a group's common prefix beyond what constant digits give; rewriting a dictionary into sorted order; more
+ * than 2^31 - 1 entries; sharing the radix passes with msj_sort_rows_device.
+ */
+#define MSJ_ORDER_CONTINUE 1u
+#define MSJ_ORDER_NO_RANK 0xFFFFFFFFu
+typedef struct msj_dictionary_order_result {   /* 48 bytes */
+    int32_t  code;       /* 0; MSJ_CAPACITY: entries still tied (n_tied > 0), or V does not fit */
+    uint32_t flags;      /* the call's flags */
+    uint64_t n_entries;  /* V */
+    uint64_t n_values;   /* entries with a value */
+    uint64_t n_tied;     /* entries still tied at `depth` */
+    uint64_t depth;      /* bytes compared when the call ended */
+    uint64_t n_equal;    /* entries whose value an earlier entry also holds */
+} msj_dictionary_order_result;
+int32_t msj_dictionary_order_device(msj_ctx *ctx,
+        const uint64_t *d_dict_offsets, const uint8_t *d_dict_bytes, uint64_t dict_bytes_capacity,
+        uint64_t n_entries, const uint64_t *d_n_entries, uint64_t capacity,
+        uint64_t depth, uint32_t max_rounds, uint32_t flags,
+        uint32_t *d_sorted, uint32_t *d_rank,
+        msj_dictionary_order_result *d_result, void *stream);
+/* Device workspace of one msj_dictionary_order_device call (the context keeps it). */
+uint64_t msj_dictionary_order_workspace_bytes(uint64_t capacity);
+/* TEST AID: 0 the path by capacity, 1 always the grid path, 2 the one-workgroup path wherever capacity <= 1 024 (more than
+ * 2: MSJ_ERR_BAD_ARGUMENT).  Both paths write the same bytes. */
+int32_t msj_debug_set_order_mode(msj_ctx *ctx, uint32_t mode);
+
+/*
+ * msj_rank_rows_device turns a column of dictionary codes into records that order like the strings: row k with c =
+ * d_codes[k] in [0, V) and d_rank[c] != MSJ_ORDER_NO_RANK gets {bits = d_rank[c], token = 0xFFFFFFFF, type 'l', flags 0,
+ * code 0}; every other row -- a null (-1), a frozen miss (-2), a wild code -- gets the record of a missing value that
+ * msj_take_rows_device writes (code 20, token 0xFFFFFFFF, the rest 0).  R = d_n_rows ? *d_n_rows : rows and V =
+ * d_order_result->n_entries are read on the device.  d_select is written as a select result over the records
+ * (n_documents = R, n_paths = 1, n_found = n_ranked), so msj_sort_rows_device, msj_filter_rows_device,
+ * msj_aggregate_device and msj_take_rows_device run on them unchanged.
+ * A non-zero code in d_order_result -- the tied MSJ_CAPACITY included -- passes through: d_result and d_select carry it and
+ * nothing else is written, so the chain stops by itself.  R > rows, R > capacity, V > rank_capacity or R >= 2^31:
+ * MSJ_CAPACITY the same way.  Arguments, checked in this order: NULL ctx / d_result / d_select / d_order_result; NULL
+ * d_codes with rows > 0, NULL d_fields with capacity > 0, NULL d_rank with rank_capacity > 0: MSJ_ERR_BAD_ARGUMENT.  rows or
+ * capacity of 2^40 or more: MSJ_CAPACITY.  Then d_result == d_select, and alignment -- d_fields 16-byte, the codes and
+ * ranks 4-byte, d_n_rows and the three results 8-byte: MSJ_ERR_BAD_ARGUMENT.  One kernel, a lane per row; a code is read
+ * only below R, a rank only below min(V, rank_capacity), nothing at or past R is written.
+ */
+typedef struct msj_rank_rows_result {   /* 48 bytes */
+    int32_t  code;       /* 0; MSJ_CAPACITY; or the code of d_order_result */
+    uint32_t flags;      /* 0 */
+    uint64_t n_rows;     /* R */
+    uint64_t n_ranked;   /* rows that got a rank */
+    uint64_t n_null;     /* rows with code -1 */
+    uint64_t n_unknown;  /* every other row without a rank */
+    uint64_t reserved;
+} msj_rank_rows_result;
+int32_t msj_rank_rows_device(msj_ctx *ctx,
+        const int32_t *d_codes, uint64_t rows, const uint64_t *d_n_rows,
+        const uint32_t *d_rank, uint64_t rank_capacity, const msj_dictionary_order_result *d_order_result,
+        msj_field *d_fields, uint64_t capacity,
+        msj_rank_rows_result *d_result, msj_select_documents_result *d_select, void *stream);
 
 /*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors

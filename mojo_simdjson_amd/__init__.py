@@ -10,7 +10,7 @@ from .dom_parser_implementation import DomParserImplementation  # noqa: F401
 
 def __getattr__(name):
     # the columns of the document stream, without importing torch until one of them is asked for
-    if name in ("DocumentStream", "ListColumn", "ElementFields", "MapColumn", "DictionaryColumn", "RowSelection", "RunningDictionary", "JoinedRows"):
+    if name in ("DocumentStream", "ListColumn", "ElementFields", "MapColumn", "DictionaryColumn", "DictionaryOrder", "RowSelection", "RunningDictionary", "JoinedRows"):
         from . import document_stream
 
         return getattr(document_stream, name)

@@ -235,6 +235,27 @@ JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3
 JOIN_KINDS = {"inner": JOIN_INNER, "left": JOIN_LEFT, "semi": JOIN_SEMI, "anti": JOIN_ANTI}
 JOIN_NO_ROW = 0xFFFFFFFF
 
+class MsjDictionaryOrderResult(ctypes.Structure):
+    """``msj_dictionary_order_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_entries", ctypes.c_uint64), ("n_values", ctypes.c_uint64),
+                ("n_tied", ctypes.c_uint64), ("depth", ctypes.c_uint64), ("n_equal", ctypes.c_uint64)]
+
+
+class MsjRankRowsResult(ctypes.Structure):
+    """``msj_rank_rows_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_ranked", ctypes.c_uint64),
+                ("n_null", ctypes.c_uint64), ("n_unknown", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+# msj_dictionary_order_device: flags, the rank of an entry without a value, the most rounds; msj_debug_set_order_mode
+ORDER_CONTINUE = 1
+ORDER_NO_RANK = 0xFFFFFFFF
+ORDER_MAX_ROUNDS = 64
+ORDER_DEFAULT_ROUNDS_GROUP, ORDER_DEFAULT_ROUNDS_GRID, ORDER_GROUP_ENTRIES = 64, 4, 1024
+ORDER_MODE_AUTO, ORDER_MODE_GRID, ORDER_MODE_GROUP = 0, 1, 2
+
 # msj_cast_strings_device: kind, unit, flags; msj_debug_set_cast_fetch
 CAST_TIMESTAMP, CAST_NUMBER = 1, 2
 CAST_KINDS = {"timestamp": CAST_TIMESTAMP, "number": CAST_NUMBER}
@@ -507,6 +528,17 @@ def load():
                                          ctypes.c_void_p]
     lib.msj_join_rows_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_join_rows_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64]
+    lib.msj_dictionary_order_device.restype = ctypes.c_int32
+    lib.msj_dictionary_order_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_dictionary_order_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_dictionary_order_workspace_bytes.argtypes = [ctypes.c_uint64]
+    lib.msj_debug_set_order_mode.restype = ctypes.c_int32
+    lib.msj_debug_set_order_mode.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    lib.msj_rank_rows_device.restype = ctypes.c_int32
+    lib.msj_rank_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

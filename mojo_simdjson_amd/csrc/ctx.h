@@ -125,6 +125,8 @@ struct msj_ctx {
     uint32_t agg_lds_groups = kAggregateMaxLdsGroups;  // msj_debug_set_aggregate_limits: the most groups the LDS path takes
     DeviceBuffer sort_ws;         // msj_sort_rows_device: the state and the plan, two buffers of two key words per row, the tiles' bucket counts
     DeviceBuffer join_ws;         // msj_join_rows_device: the counters, count / start per key, two buffers of (key, row) per right row, a run and an offset per left row
+    DeviceBuffer order_ws;        // msj_dictionary_order_device: the counters, and per entry the tied entries' keys, entries and places twice over
+    uint32_t order_mode = 0;      // msj_debug_set_order_mode: 0 the path by capacity, 1 always the grid path, 2 the one-workgroup path wherever it fits
     uint32_t sort_mode = 0;       // msj_debug_set_sort_mode: 0 chosen on the device, 1 always the full sort, 2 always the selection
 };
 

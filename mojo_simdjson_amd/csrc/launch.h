@@ -1,7 +1,7 @@
 // launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 /
 // f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
 // validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
-// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, dictionary_extend_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip, join_rows_kernel.hip.  Every launcher and every internal workspace size is declared
+// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, dictionary_extend_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip, join_rows_kernel.hip, dictionary_order_kernel.hip.  Every launcher and every internal workspace size is declared
 // here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
 // compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
 // (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.
@@ -259,3 +259,16 @@ extern "C" int msj_launch_join_rows(const int32_t *d_left_keys, uint64_t left_ro
                                     uint64_t keys_capacity, uint32_t flags, uint32_t *d_left_rows, uint32_t *d_right_rows, uint64_t pairs_capacity,
                                     uint64_t *d_offsets, msj_join_rows_result *d_result, msj_select_documents_result *d_left_select,
                                     msj_select_documents_result *d_right_select, void *d_ws, void *stream);
+
+// ---- dictionary_order_kernel.hip ----
+// the (d_dict_offsets, d_dict_bytes) layout of a dictionary; n_entries / d_n_entries: V (the word on the device wins); depth,
+// max_rounds, flags: checked by the caller (dictionary_order_math.h: bad_numbers); mode: 0 the path by capacity, 1 always the
+// grid path, 2 the one-workgroup path wherever it fits (msj_debug_set_order_mode)
+extern "C" int msj_launch_dictionary_order(const uint64_t *d_dict_offsets, const uint8_t *d_dict_bytes, uint64_t dict_bytes_capacity,
+                                           uint64_t n_entries, const uint64_t *d_n_entries, uint64_t capacity, uint64_t depth, uint32_t max_rounds,
+                                           uint32_t flags, uint32_t mode, uint32_t *d_sorted, uint32_t *d_rank,
+                                           msj_dictionary_order_result *d_result, void *d_ws, void *stream);
+// `rows` / `capacity`: the rooms of d_codes / d_fields; the two results are cleared on the stream in front of the one kernel
+extern "C" int msj_launch_rank_rows(const int32_t *d_codes, uint64_t rows, const uint64_t *d_n_rows, const uint32_t *d_rank, uint64_t rank_capacity,
+                                    const msj_dictionary_order_result *d_order_result, msj_field *d_fields, uint64_t capacity,
+                                    msj_rank_rows_result *d_result, msj_select_documents_result *d_select, void *stream);

@@ -2,13 +2,14 @@
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
 // window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
 // elements, the arrays inside list rows, an object's members as a map column, a selected value's JSON text as a column, a byte column as codes plus distinct
-// values (in one window, or against a dictionary carried across windows), rows by predicate, strings cast to numbers, count / sum / min / max per group, rows by numeric order, the equi-join of two code columns.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// values (in one window, or against a dictionary carried across windows), rows by predicate, strings cast to numbers, count / sum / min / max per group, rows by numeric order, the equi-join of two code columns, a dictionary's values in byte order and the rank records of a code column.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
 // see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
 #include <new>
 
 #include "ctx.h"
 #include "aggregate_math.h"
 #include "cast_strings_math.h"
+#include "dictionary_order_math.h"
 #include "filter_rows_math.h"
 #include "join_rows_math.h"
 #include "select_math.h"
@@ -739,6 +740,38 @@ int32_t msj_join_rows_device(msj_ctx *ctx, const int32_t *d_left_keys, uint64_t 
     return launched(msj_launch_join_rows(d_left_keys, left_rows, d_n_left, d_right_keys, right_rows, d_n_right, n_keys, d_n_keys, keys_capacity, flags,
                                          d_left_rows, d_right_rows, pairs_capacity, d_offsets, d_result, d_left_select, d_right_select,
                                          ctx->join_ws.p, stream));
+}
+
+int32_t msj_dictionary_order_device(msj_ctx *ctx, const uint64_t *d_dict_offsets, const uint8_t *d_dict_bytes, uint64_t dict_bytes_capacity,
+                                    uint64_t n_entries, const uint64_t *d_n_entries, uint64_t capacity, uint64_t depth, uint32_t max_rounds,
+                                    uint32_t flags, uint32_t *d_sorted, uint32_t *d_rank, msj_dictionary_order_result *d_result, void *stream) {
+    if (!ctx || !d_result) return MSJ_ERR_BAD_ARGUMENT;
+    if ((capacity > 0 && (!d_dict_offsets || !d_sorted || !d_rank)) || (dict_bytes_capacity > 0 && !d_dict_bytes)) return MSJ_ERR_BAD_ARGUMENT;
+    if (msj::dord::bad_numbers(depth, max_rounds, flags)) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity >= (1ull << 40)) return MSJ_CAPACITY;  // (the workspace's size below: no overflow)
+    if (!all_aligned(8, d_dict_offsets, d_n_entries, d_result) || !all_aligned(4, d_sorted, d_rank)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->order_ws, msj_dictionary_order_workspace_bytes(capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_dictionary_order(d_dict_offsets, d_dict_bytes, dict_bytes_capacity, n_entries, d_n_entries, capacity, depth, max_rounds,
+                                                flags, ctx->order_mode, d_sorted, d_rank, d_result, ctx->order_ws.p, stream));
+}
+int32_t msj_debug_set_order_mode(msj_ctx *ctx, uint32_t mode) {
+    if (!ctx || mode > 2u) return MSJ_ERR_BAD_ARGUMENT;
+    ctx->order_mode = mode;
+    return MSJ_SUCCESS;
+}
+
+int32_t msj_rank_rows_device(msj_ctx *ctx, const int32_t *d_codes, uint64_t rows, const uint64_t *d_n_rows, const uint32_t *d_rank,
+                             uint64_t rank_capacity, const msj_dictionary_order_result *d_order_result, msj_field *d_fields, uint64_t capacity,
+                             msj_rank_rows_result *d_result, msj_select_documents_result *d_select, void *stream) {
+    if (!ctx || !d_result || !d_select || !d_order_result) return MSJ_ERR_BAD_ARGUMENT;
+    if ((rows > 0 && !d_codes) || (capacity > 0 && !d_fields) || (rank_capacity > 0 && !d_rank)) return MSJ_ERR_BAD_ARGUMENT;
+    if (rows >= (1ull << 40) || capacity >= (1ull << 40)) return MSJ_CAPACITY;
+    if ((const void *)d_result == (const void *)d_select) return MSJ_ERR_BAD_ARGUMENT;
+    if (!aligned(d_fields, 16) || !all_aligned(4, d_codes, d_rank) || !all_aligned(8, d_n_rows, d_order_result, d_result, d_select))
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (!hip_ok(hipSetDevice(ctx->device))) return MSJ_ERR_HIP;
+    return launched(msj_launch_rank_rows(d_codes, rows, d_n_rows, d_rank, rank_capacity, d_order_result, d_fields, capacity, d_result, d_select, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

@@ -1016,6 +1016,82 @@ class Stage1Device:
         """The device workspace one ``join_rows`` call of these rooms keeps in the context (``msj_join_rows_workspace_bytes``)."""
         return int(self.lib.msj_join_rows_workspace_bytes(int(left_rows), int(right_rows), int(keys_capacity)))
 
+    def dictionary_order(self, d_dict_offsets, d_dict_bytes, n_entries=0, d_n_entries=None, capacity=None, dict_bytes_capacity=None, depth=0,
+                         max_rounds=0, resume=False, d_sorted=None, d_rank=None, d_result=None, sync=True):
+        """A dictionary's entries in the byte order of their values (``msj_dictionary_order_device``), all on the device.
+        d_dict_offsets (int64, capacity + 1 entries) and d_dict_bytes (uint8): what ``dictionary`` / ``dictionary_extend``
+        wrote, or any arrays of that shape; n_entries: V; d_n_entries: an int64 device tensor whose first word is V, read on
+        the device (``d_res[24:32].view(torch.int64)`` of a dictionary call's result is its n_distinct); capacity: the room
+        of d_sorted / d_rank (default: the room of d_dict_offsets); dict_bytes_capacity: default the size of d_dict_bytes.
+        Values compare as unsigned bytes, a proper prefix first.  d_sorted / d_rank: int32 tensors of `capacity` entries
+        (default: new ones) -- the entry numbers in order, and per entry the number of smaller values (``ORDER_NO_RANK``,
+        as int32 -1, for an entry without a value).  max_rounds: the rounds of eight bytes this call may compare (0: the
+        path's default).  A result with code 1 (MSJ_CAPACITY) and n_tied > 0: entries still agree on `depth` bytes; repeat
+        with resume=True, depth=result.depth and the same two tensors.  Returns (``MsjDictionaryOrderResult``, d_sorted,
+        d_rank) -- blocking for the 48-byte result; with sync=False the device tensor that holds it, nothing waited for."""
+        if d_dict_offsets.dtype != torch.int64 or d_dict_offsets.stride(-1) != 1 or d_dict_bytes.dtype != torch.uint8:
+            raise ValueError("the dictionary is a contiguous int64 offsets tensor and a uint8 bytes tensor")
+        capacity = max(d_dict_offsets.numel() - 1, 0) if capacity is None else int(capacity)
+        if d_dict_offsets.numel() < capacity + 1 and capacity > 0:
+            raise ValueError("d_dict_offsets has capacity + 1 entries")
+        dict_bytes_capacity = d_dict_bytes.numel() if dict_bytes_capacity is None else int(dict_bytes_capacity)
+        if d_sorted is None:
+            d_sorted = torch.empty((max(capacity, 1),), dtype=torch.int32, device=self.device)
+        if d_rank is None:
+            d_rank = torch.empty((max(capacity, 1),), dtype=torch.int32, device=self.device)
+        for t in (d_sorted, d_rank):
+            if t.dtype != torch.int32 or t.numel() < capacity:
+                raise ValueError("d_sorted and d_rank are int32 tensors of capacity entries")
+        d_result = self._result(d_result)
+        rc = self.lib.msj_dictionary_order_device(self.ctx, _ptr(d_dict_offsets), _ptr(d_dict_bytes), dict_bytes_capacity, int(n_entries),
+                                                  _opt(d_n_entries), capacity, int(depth), int(max_rounds), _lib.ORDER_CONTINUE if resume else 0,
+                                                  _ptr(d_sorted), _ptr(d_rank), _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_dictionary_order_device failed: {rc}")
+        res = _lib.MsjDictionaryOrderResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_sorted, d_rank
+
+    def dictionary_order_workspace_bytes(self, capacity):
+        """The device workspace one ``dictionary_order`` call of this room keeps in the context."""
+        return int(self.lib.msj_dictionary_order_workspace_bytes(int(capacity)))
+
+    def set_order_mode(self, mode=_lib.ORDER_MODE_AUTO):
+        """Test hook: the path ``dictionary_order`` takes -- 0 by capacity, 1 always the grid path, 2 the one-workgroup path
+        wherever capacity <= 1 024.  The order does not change."""
+        if self.lib.msj_debug_set_order_mode(self.ctx, int(mode)) != 0:
+            raise ValueError(f"mode is 0, 1 or 2: {mode!r}")
+
+    def rank_rows(self, d_codes, d_rank, d_order_result, rows=None, d_n_rows=None, rank_capacity=None, d_fields=None, capacity=None,
+                  d_result=None, d_select=None, sync=True):
+        """A column of dictionary codes as records that order like the strings (``msj_rank_rows_device``): row k with a
+        code that has a rank gets the 'l' record of that rank, every other row (null -1, frozen miss -2, a wild code) the
+        record of a missing value.  d_codes: contiguous int32; d_rank and d_order_result: what ``dictionary_order`` wrote
+        (the result as the uint8[48] device tensor of its sync=False form); rows: default the entries of d_codes; d_n_rows:
+        an int64 device tensor whose first word is R; d_fields: int64 (capacity, 2) (default: a new one).  d_select
+        receives the select result over the records, so ``sort_rows``, ``filter_rows``, ``aggregate`` and ``take_rows`` run on
+        them.  A code in d_order_result -- an order with entries still tied included -- passes through and nothing is
+        written.  Returns (``MsjRankRowsResult``, d_fields, d_select) -- blocking for the 48-byte result; with sync=False
+        the device tensor that holds it."""
+        if d_codes.dtype != torch.int32 or d_codes.stride(-1) != 1 or d_rank.dtype != torch.int32:
+            raise ValueError("the codes and the ranks are contiguous int32 tensors")
+        rows = d_codes.numel() if rows is None else int(rows)
+        rank_capacity = d_rank.numel() if rank_capacity is None else int(rank_capacity)
+        if capacity is None:
+            capacity = d_fields.shape[0] if d_fields is not None else rows
+        capacity = int(capacity)
+        if d_fields is None:
+            d_fields = torch.empty((max(capacity, 1), 2), dtype=torch.int64, device=self.device)
+        _check_records(d_fields, "d_fields")
+        if d_fields.shape[0] < capacity:
+            raise ValueError("d_fields has capacity records")
+        d_result, d_select = self._result(d_result), self._result(d_select)
+        rc = self.lib.msj_rank_rows_device(self.ctx, _ptr(d_codes), rows, _opt(d_n_rows), _ptr(d_rank), rank_capacity, _ptr(d_order_result),
+                                           _ptr(d_fields), capacity, _ptr(d_result), _ptr(d_select), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_rank_rows_device failed: {rc}")
+        res = _lib.MsjRankRowsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_fields, d_select
+
     def set_sort_mode(self, mode=_lib.SORT_MODE_AUTO):
         """Test hook: the path ``sort_rows`` takes -- 0 chosen on the device, 1 always the full sort, 2 always the
         selection.  The order does not change."""

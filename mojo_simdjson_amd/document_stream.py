@@ -233,7 +233,7 @@ def _cast_spec(spec):
     """"number", "timestamp" or ("timestamp", unit) -> (kind, unit)"""
     kind, unit = (spec, "ns") if isinstance(spec, str) else tuple(spec)
     if kind not in _lib.CAST_KINDS or unit not in _lib.CAST_UNITS:
-        raise ValueError(f"a cast is 'number', 'timestamp' or ('timestamp', 's' | 'ms' | 'us' | 'ns'): {spec!r}")
+        raise ValueError(f"a cast is 'number', 'timestamp' or ('timestamp', 's' | 'ms' | 'us' | 'ns') -- and 'string' for order / order_by only: {spec!r}")
     return kind, unit
 
 
@@ -291,12 +291,21 @@ class DictionaryColumn:
     uint8[total]: value c is bytes[offsets[c]:offsets[c + 1]]; first int32[n_distinct]: the row value c first appears in;
     valid bool[rows], the column's own validity."""
 
-    def __init__(self, codes, offsets, data, first, valid):
-        self.codes, self.offsets, self.bytes, self.first, self.valid = codes, offsets, data, first, valid
+    def __init__(self, codes, offsets, data, first, valid, dev=None):
+        self.codes, self.offsets, self.bytes, self.first, self.valid, self.dev = codes, offsets, data, first, valid, dev
 
     @property
     def n_distinct(self):
         return self.first.shape[0]
+
+    def order(self, max_rounds=None):
+        """The distinct values in byte order ON THE DEVICE (``msj_dictionary_order_device``) -> ``DictionaryOrder``: the
+        entries ascending by value and every entry's rank, so that ``order().rank_records(self.codes)`` are records that
+        sort, filter and aggregate like the strings.  max_rounds: the rounds of eight bytes one call compares (None: the
+        call's default); values that agree further are ordered by repeating the call."""
+        if self.dev is None:
+            raise ValueError("this DictionaryColumn was made without a device")
+        return _dictionary_order(self.dev, self.offsets, self.bytes, self.n_distinct, max_rounds, "the dictionary")
 
     def counts(self):
         """Rows per value, int64[n_distinct], on the device (``torch.bincount`` of the codes that are not -1)."""
@@ -322,7 +331,57 @@ def _dictionary(window, column, what):
     if res.code != 0:
         raise DocumentStreamError(int(res.code), f"window at {window.base}: the strings of {what} could not be dictionary-encoded")
     n = int(res.n_distinct)
-    return DictionaryColumn(codes[:rows], d_off[:n + 1], d_bytes[:int(res.dict_bytes)], d_first[:n], valid)
+    return DictionaryColumn(codes[:rows], d_off[:n + 1], d_bytes[:int(res.dict_bytes)], d_first[:n], valid, window.dev)
+
+
+class DictionaryOrder:
+    """A dictionary's entries in the byte order of their values ON THE DEVICE (``msj_dictionary_order_device``;
+    ``DictionaryColumn.order``, ``RunningDictionary.order``).  sorted int32[n]: the entry numbers ascending by value -- unsigned
+    bytes, a proper prefix first, which for UTF-8 is code-point order; no collation, no case folding --, equal values by
+    entry number; rank int32[n]: per entry the number of smaller values, so for a real dictionary ``sorted[rank[c]] == c``;
+    result: the last call's ``MsjDictionaryOrderResult``; d_result: the uint8[48] device tensor that holds it."""
+
+    def __init__(self, dev, offsets, data, sorted_entries, rank, d_result, result):
+        self.dev, self.offsets, self.bytes = dev, offsets, data
+        self.sorted, self.rank, self.d_result, self.result = sorted_entries, rank, d_result, result
+
+    @property
+    def n_entries(self):
+        return self.sorted.shape[0]
+
+    def values(self):
+        """The distinct values as str, ascending: the dictionary and the order come to the host."""
+        off, data = self.offsets.cpu().tolist(), self.bytes.cpu().numpy().tobytes()
+        return [data[off[c]:off[c + 1]].decode("utf-8", "surrogateescape") for c in self.sorted.cpu().tolist()]
+
+    def rank_records(self, codes):
+        """A column of this dictionary's codes (int32[rows]) as records that order like the strings
+        (``msj_rank_rows_device``) -> (records int64[rows, 2], the uint8[48] select result that counts them): a row's value's
+        rank as an int64 value, the record of a missing value for a row without one (-1, -2, a code of a later window).
+        ``sort_rows``, ``filter_rows``, ``aggregate`` and ``take_rows`` take them.  Nothing comes to the host."""
+        rows = codes.shape[0]
+        _, d_fields, d_select = self.dev.rank_rows(_or_blank(codes, rows).contiguous(), _or_blank(self.rank, self.n_entries), self.d_result, rows=rows,
+                                                   rank_capacity=self.n_entries, capacity=rows, sync=False)
+        return d_fields[:rows], d_select
+
+
+def _dictionary_order(dev, offsets, data, n, max_rounds, what):
+    """``dictionary_order`` over the n entries of (offsets int64[n + 1], bytes), repeated with MSJ_ORDER_CONTINUE while
+    entries are still tied -> ``DictionaryOrder``.  Each call's 48-byte result comes to the host."""
+    d_sorted = d_rank = None
+    depth, resume = 0, False
+    while True:
+        res, d_sorted, d_rank = dev.dictionary_order(offsets, _or_blank(data, data.shape[0]), n_entries=n, capacity=n, dict_bytes_capacity=data.shape[0],
+                                                     depth=depth, max_rounds=int(max_rounds or 0), resume=resume, d_sorted=d_sorted, d_rank=d_rank,
+                                                     sync=False)
+        d_result = res
+        res = _lib.MsjDictionaryOrderResult.from_buffer_copy(d_result.cpu().numpy().tobytes())
+        if res.code != errors.CAPACITY or res.n_tied == 0 or res.depth <= depth:
+            break
+        depth, resume = int(res.depth), True
+    if res.code != 0 or res.n_entries != n:
+        raise DocumentStreamError(int(res.code), f"{what} could not be ordered")
+    return DictionaryOrder(dev, offsets, data, d_sorted[:n], d_rank[:n], d_result, res)
 
 
 class RunningDictionary:
@@ -368,6 +427,11 @@ class RunningDictionary:
         off, data = self.offsets[:self._n + 1].cpu().tolist(), self.bytes[:self._n_bytes].cpu().numpy().tobytes()
         return [data[off[c]:off[c + 1]].decode("utf-8", "surrogateescape") for c in range(self._n)]
 
+    def order(self, max_rounds=None):
+        """The values held so far in byte order ON THE DEVICE -> ``DictionaryOrder`` (see ``DictionaryColumn.order``): ranks
+        for the codes of every window encoded so far.  A value added later changes the ranks: order again."""
+        return _dictionary_order(self.dev, self.offsets[:self._n + 1], self.bytes[:self._n_bytes], self._n, max_rounds, "the running dictionary")
+
     def encode(self, column, frozen=False, what="a column"):
         """A column (offsets int64[rows + 1], bytes uint8[total], valid bool[rows]) as the column calls return it, encoded
         against this dictionary -> ``DictionaryColumn``: codes int32[rows] in THIS dictionary's numbering; offsets and bytes
@@ -393,7 +457,7 @@ class RunningDictionary:
         prior, self._n, self._n_bytes = self._n, need, need_bytes
         first = torch.full((need,), -1, dtype=torch.int32, device=codes.device)
         first[prior:] = self.first[prior:need]
-        return DictionaryColumn(codes[:rows], self.offsets[:need + 1], self.bytes[:need_bytes], first, valid)
+        return DictionaryColumn(codes[:rows], self.offsets[:need + 1], self.bytes[:need_bytes], first, valid, self.dev)
 
 
 class GroupStats:
@@ -483,6 +547,16 @@ def _sort_keys(keys, index, descending=False):
     return out
 
 
+def _string_ranks(window, d_fields, d_select, rows, c, what):
+    """The cast "string" of ``order`` / ``order_by``: column c's strings -> their dictionary -> its order -> the rows' rank
+    records int64[rows, 2] (``msj_string_column_device``, ``msj_dictionary_device``, ``msj_dictionary_order_device``,
+    ``msj_rank_rows_device``): numbers that ``sort_rows`` orders as the strings order in bytes.  A row without a string has no
+    number value."""
+    column = _string_column(window, d_fields, d_select, rows, c, None, f"column {c} of {what}")
+    categories = _dictionary(window, column, f"column {c} of {what}")
+    return categories.order().rank_records(categories.codes)[0]
+
+
 def _order(window, d_fields, d_select, rows, keys, limit, values_only, cast, what):
     """``sort_rows`` over `rows` records per column of d_fields (int64[n_columns, rows, 2]), one call per key, the minor key
     first and each call's order the next one's d_rows_in (the sort is stable); the last call gets the limit and values_only.
@@ -496,7 +570,9 @@ def _order(window, d_fields, d_select, rows, keys, limit, values_only, cast, wha
     for j, (c, descending) in enumerate(reversed(keys)):
         last = j == len(keys) - 1
         column = d_fields[c]
-        if c in cast and rows:
+        if c in cast and rows and cast[c] == "string":
+            column = _string_ranks(w, d_fields, d_select, rows, c, what)
+        elif c in cast and rows:
             kind, unit = _cast_spec(cast[c])
             column = _cast(w, column, d_select, rows, kind, unit, kind == "number", what)[0]
         res, d_in, d_in_select = w.dev.sort_rows(_or_blank(column, rows).contiguous(), d_select, d_in, d_in_select, descending=descending,
@@ -685,8 +761,10 @@ class _Records:
         direction of the keys that name none.  An int64 is compared with a double as real numbers -- 9007199254740993 lies
         between 9007199254740992.0 and 9007199254740994.0 --, equal values keep their order, rows without a number value
         come last (values_only: are left out).  limit: only the first so many.  cast: ``{"/ts": ("timestamp", "ns")}`` as
-        in ``where``, so that ``order("/ts", cast={"/ts": ("timestamp", "ns")})`` is time order.  Only the last call's
-        48-byte result comes to the host."""
+        in ``where``, so that ``order("/ts", cast={"/ts": ("timestamp", "ns")})`` is time order; and here alone "string":
+        ``order("/name", cast={"/name": "string"})`` orders by the strings' bytes (code-point order for UTF-8, no collation)
+        through the column's dictionary, its order and the rows' ranks (``msj_dictionary_order_device``,
+        ``msj_rank_rows_device``), rows without a string last.  Only small results come to the host."""
         fields, index = self._records, self.paths.index
         return _order(self._window, fields, self.d_select, fields.shape[1], _sort_keys(keys, index, descending), limit, values_only,
                       {index(k): v for k, v in (cast or {}).items()}, self._rows_are)
@@ -844,6 +922,11 @@ class ListColumn:
         of maps) -- ON THE DEVICE -> ``MapColumn`` with one row per element of this column; an element that is no object is a
         row that is not valid."""
         return self._one.entries(0, entries_capacity)
+
+    def order(self, descending=False, limit=None, cast=None, values_only=False):
+        """The element numbers in the order of the elements' values ON THE DEVICE -> (order int32[K], its select result), as
+        ``Window.order`` gives them; cast: "string" for elements that are strings, or a cast as in ``stats``."""
+        return self._one.order(0, limit, {0: cast} if cast else None, values_only, descending)
 
     def stats(self, per_row=False, cast=None):
         """Count, sum, min and max of the elements that are numbers ON THE DEVICE (``msj_aggregate_device``) ->
