@@ -165,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void cs_cast(const uint8_t *__restrict__ 
             uint32_t base = 0;
             if (lane == leader) base = atomicAdd(&w.st->n_list, (uint32_t)__popcll((unsigned long long)m));
             base = (uint32_t)__shfl((int)base, (int)leader);
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            const uint32_t below = lanes_below(m);
             if (listed) w.list[base + below] = (uint32_t)k;  // (base + below < the listed rows <= R <= capacity)
         }
         const uint64_t sum = wave_sum64(cnt);

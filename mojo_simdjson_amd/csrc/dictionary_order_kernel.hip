@@ -23,9 +23,9 @@
 //   do_compact   the tied entries in position order: place, entry, key (the word fetched here) into buffer 0; the OR and AND
 //               of a tile's keys
 //   do_plan      one workgroup: the OR and AND over the tiles -> the digits that differ, the passes of this round
-//   do_count(d), do_scan(d), do_scatter(d)   one stable least-significant-digit pass, as join_rows_kernel.hip's: counts per
-//               (bucket, tile), 256 workgroups scan a bucket each, the scatter ranks by ballots and LDS counters.  A pass
-//               reads the buffer the passes in front of it left (their number's parity)
+//   do_count(d), do_scan(d), do_scatter(d)   one stable least-significant-digit pass, radix_block.h's: counts per (bucket,
+//               tile), 256 workgroups scan a bucket each and leave its total, the scatter ranks by ballots and LDS
+//               counters.  A pass reads the buffer the passes in front of it left (their number's parity)
 //   do_heads     writes the entries back to their places; a head is a tied entry whose key differs from the one in front;
 //               the largest head place of a tile
 //   do_heads_scan, do_rank   the running maximum of the head places over the tiles, then inside a tile: an entry's rank
@@ -39,12 +39,14 @@
 #include "bytes_block.h"
 #include "dictionary_order_math.h"
 #include "launch.h"
+#include "radix_block.h"
 
 namespace msj_dord {
 
 using namespace msj::dord;
 using namespace msj::wave;
 using msj_bytes::kRows, msj_bytes::most_rows;
+using msj_radix::kRounds, msj_radix::kScan, msj_radix::kTile, msj_radix::kTileBlocks, msj_radix::tiles_of;  // also of positions
 using msj_tape::kThreads, msj_tape::kWaves;
 
 static_assert(sizeof(msj_dictionary_order_result) == 48 && sizeof(msj_rank_rows_result) == 48 && sizeof(msj_field) == 16 &&
@@ -52,12 +54,9 @@ static_assert(sizeof(msj_dictionary_order_result) == 48 && sizeof(msj_rank_rows_
               "ABI");
 static_assert(kRows == (uint32_t)kThreads && kWaves == 4 && kBuckets == (uint32_t)kThreads, "geometry");
 static_assert(MSJ_ORDER_NO_RANK == kNoRank && MSJ_ORDER_CONTINUE == kContinue, "ABI");
+static_assert(kBuckets == msj_radix::kBuckets && kDigitBits == msj_radix::kDigitBits, "the radix pass takes dictionary_order_math.h's digits");
 
-constexpr uint32_t kRounds = 4;
-constexpr uint32_t kTile = kRounds * kRows;  // positions or tied entries of a block's tile
-constexpr uint32_t kScan = 1024;             // lanes of the one-workgroup kernels
-constexpr uint32_t kTileBlocks = 1024;       // most blocks of the kernels over tiles
-constexpr uint32_t kGroupWaves = kScan / 64;
+constexpr uint32_t kGroupWaves = kScan / 64;  // (kScan: also the lanes of the one-workgroup kernels)
 static_assert(kGroupEntries == kScan, "a lane per position");
 
 struct State {  // cleared by a memset per call
@@ -88,7 +87,6 @@ struct Call {
     uint32_t *sorted, *rank;
 };
 
-static inline uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
 static inline Work layout(msj_carver &c, uint64_t capacity) {
     const uint64_t n = most_entries(capacity), tiles = tiles_of(n);
     Work w;
@@ -114,65 +112,6 @@ __device__ __forceinline__ Head load_head(const Call &call) {
     h.V = call.d_n_entries ? *call.d_n_entries : call.n_entries;
     h.stop = entries_over(h.V, call.capacity);
     return h;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-// the flagged lanes in front of this one in the workgroup of W waves, and all of them (s_w: W words no lane still reads)
-template <uint32_t W>
-__device__ __forceinline__ uint32_t block_flag_rank(bool flag, uint32_t *s_w, uint32_t &total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t m = __ballot(flag);
-    __syncthreads();  // (the last round's totals have been read)
-    if (lane == 0) s_w[wave] = (uint32_t)__popcll((unsigned long long)m);
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < W; x++) {
-        const uint32_t t = s_w[x];
-        if (x < wave) before += t;
-        all += t;
-    }
-    total = all;
-    return before + lanes_below(m);
-}
-// the maximum of x over this lane and the lanes in front in the workgroup of W waves, and over all of them
-template <uint32_t W>
-__device__ __forceinline__ uint32_t block_scan_max(uint32_t x, uint32_t *s_w, uint32_t &total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t inc = wave_scan_max(x);
-    __syncthreads();
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t y = 0; y < W; y++) {
-        const uint32_t t = s_w[y];
-        if (y < wave) before = max(before, t);
-        all = max(all, t);
-    }
-    total = all;
-    return max(before, inc);
-}
-// a[0 .. count) becomes the maximum of the entries in front of each (0 at the first), by ONE workgroup of 1 024 lanes
-__device__ __forceinline__ void scan_max_in_place(uint32_t *__restrict__ a, uint64_t count, uint32_t *s_w) {
-    uint32_t run = 0;
-    for (uint64_t v0 = 0; v0 < count; v0 += kScan) {
-        const uint64_t v = v0 + threadIdx.x;
-        const uint32_t x = v < count ? a[v] : 0u;
-        uint32_t total;
-        const uint32_t inc = block_scan_max<kGroupWaves>(x, s_w, total);
-        // what stands in front: the inclusive maximum of the lane in front, or at a wave's first lane that of the waves in front
-        uint32_t prev = (uint32_t)__shfl_up((int)inc, 1);
-        if ((threadIdx.x & 63) == 0) {
-            prev = 0;
-            for (uint32_t y = 0; y < (threadIdx.x >> 6); y++) prev = max(prev, s_w[y]);
-        }
-        if (v < count) a[v] = max(run, prev);
-        run = max(run, total);
-        __syncthreads();  // (s_w read before the next chunk writes it)
-    }
 }
 
 __device__ __forceinline__ void write_result(const Call &call, const Head &h, msj_dictionary_order_result *__restrict__ result, uint64_t n_values,
@@ -282,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void do_init_count(const Call call, const
     __shared__ uint32_t s_w[kWaves];
     const Head h = load_head(call);
     if (h.stop) return;
-    const uint64_t tiles = (h.V + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(h.V);
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         uint32_t sum = 0;
 #pragma unroll
@@ -299,7 +238,7 @@ __global__ __launch_bounds__(kScan) void do_init_scan(const Call call, const Wor
     __shared__ uint64_t s_w[16];
     const Head h = load_head(call);
     if (h.stop) return;
-    const uint64_t tiles = (h.V + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(h.V);
     const uint64_t total = scan_in_place(w.tcnt, tiles, s_w);
     if (threadIdx.x == 0) w.tcnt[tiles] = (uint32_t)total;  // (room: tiles + 1 words)
 }
@@ -307,7 +246,7 @@ __global__ __launch_bounds__(kThreads) void do_init_write(const Call call, const
     __shared__ uint32_t s_w[kWaves];
     const Head h = load_head(call);
     if (h.stop) return;
-    const uint64_t tiles = (h.V + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(h.V);
     const uint64_t n_values = w.tcnt[tiles];
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         uint64_t run = w.tcnt[v];
@@ -334,7 +273,7 @@ __global__ __launch_bounds__(kThreads) void do_tied_count(const Call call, const
     const Head h = load_head(call);
     if (round_idle(h, w, t)) return;
     const uint64_t depth = call.depth + (uint64_t)kWordBytes * t;
-    const uint64_t tiles = (h.V + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(h.V);
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         uint32_t sum = 0;
 #pragma unroll
@@ -356,7 +295,7 @@ __global__ __launch_bounds__(kScan) void do_tied_scan(const Call call, const Wor
         if (threadIdx.x == 0) w.st->tied = 0;
         return;
     }
-    const uint64_t total = scan_in_place(w.tcnt, (h.V + kTile - 1) / kTile, s_w);
+    const uint64_t total = scan_in_place(w.tcnt, tiles_of(h.V), s_w);
     if (threadIdx.x != 0) return;
     w.st->tied = total;
     if (total) w.st->rounds_run = t + 1;
@@ -372,7 +311,7 @@ __global__ __launch_bounds__(kThreads) void do_compact(const Call call, const Wo
     const uint64_t n = round_tied(h, w);
     if (n == 0) return;
     const uint64_t depth = call.depth + (uint64_t)kWordBytes * t;
-    const uint64_t tiles = (h.V + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(h.V);
     const MemoryBytes src{call.bytes};
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
@@ -409,7 +348,7 @@ __global__ __launch_bounds__(kScan) void do_plan(const Call call, const Work w) 
     __shared__ uint64_t s_k[4][kGroupWaves];
     const Head h = load_head(call);
     if (round_tied(h, w) == 0) return;
-    const uint64_t tiles = (h.V + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(h.V);
     uint64_t any_word = 0, all_word = ~0ull, any_rn = 0, all_rn = ~0ull;
     for (uint64_t v = threadIdx.x; v < tiles; v += kScan)
         any_word |= w.or_word[v], all_word &= w.and_word[v], any_rn |= w.or_rn[v], all_rn &= w.and_rn[v];
@@ -428,36 +367,43 @@ __global__ __launch_bounds__(kScan) void do_plan(const Call call, const Work w) 
 }
 
 // ---- the tied entries in the order of their keys ------------------------------------------------------------------------------
+// a pass, and as radix_block.h's policy a tied entry of its scatter: its key and its entry number
 struct Pass {
+    struct Record {
+        Key k;
+        uint32_t ent;
+    };
     uint64_t n, tiles;
+    uint32_t d;
     const uint64_t *src_word, *src_rn;
     const uint32_t *src_ent;
     uint64_t *dst_word, *dst_rn;
     uint32_t *dst_ent;
     bool skip;
+    __device__ __forceinline__ bool load_key(uint64_t j, Key &k) const {
+        const bool active = j < n;
+        k.word = active ? src_word[j] : 0, k.rn = active ? src_rn[j] : 0;  // (j < n <= V <= capacity)
+        return active;
+    }
+    __device__ __forceinline__ bool load(uint64_t j, Record &x) const {
+        const bool active = load_key(j, x.k);
+        x.ent = active ? src_ent[j] : 0u;
+        return active;
+    }
+    __device__ __forceinline__ uint32_t digit(const Record &x) const { return digit_of(x.k, d); }
+    __device__ __forceinline__ uint64_t bound() const { return n; }
+    __device__ __forceinline__ void store(uint32_t at, const Record &x) const { dst_word[at] = x.k.word, dst_rn[at] = x.k.rn, dst_ent[at] = x.ent; }
 };
 __device__ __forceinline__ Pass load_pass(const Work &w, const Head &h, uint32_t d) {
     Pass s;
-    s.n = round_tied(h, w);
+    s.n = round_tied(h, w), s.d = d;
     const uint32_t mask = w.st->mask;
     s.skip = s.n == 0 || !((mask >> d) & 1u);
-    s.tiles = (s.n + kTile - 1) / kTile;
+    s.tiles = tiles_of(s.n);
     const uint32_t from = passes_before(mask, d) & 1u;
     s.src_word = w.word[from], s.src_rn = w.rn[from], s.src_ent = w.ent[from];
     s.dst_word = w.word[from ^ 1u], s.dst_rn = w.rn[from ^ 1u], s.dst_ent = w.ent[from ^ 1u];
     return s;
-}
-// one more entry in hist[x] for every active lane; a wave whose active lanes share one x adds once
-__device__ __forceinline__ void wave_hist_add(uint32_t *hist, uint32_t x, bool active) {
-    const uint64_t m = __ballot(active);
-    if (m == 0) return;
-    const int first_lane = __ffsll((unsigned long long)m) - 1;
-    const uint32_t first = (uint32_t)__shfl((int)x, first_lane);
-    if (__ballot(active && x != first) == 0) {
-        if ((int)(threadIdx.x & 63) == first_lane) atomicAdd(&hist[first], (uint32_t)__popcll((unsigned long long)m));
-    } else if (active) {
-        atomicAdd(&hist[x], 1u);
-    }
 }
 
 __global__ __launch_bounds__(kThreads) void do_count(const Call call, const Work w, uint32_t d) {
@@ -465,28 +411,20 @@ __global__ __launch_bounds__(kThreads) void do_count(const Call call, const Work
     const Head h = load_head(call);
     const Pass s = load_pass(w, h, d);
     if (s.skip) return;
-    for (uint64_t v = blockIdx.x; v < s.tiles; v += gridDim.x) {
-        s_h[threadIdx.x] = 0;
-        __syncthreads();
-#pragma unroll
-        for (uint32_t r = 0; r < kRounds; r++) {
-            const uint64_t j = v * kTile + r * kRows + threadIdx.x;
-            const bool active = j < s.n;
-            Key k;
-            k.word = active ? s.src_word[j] : 0, k.rn = active ? s.src_rn[j] : 0;  // (j < n <= V <= capacity)
-            wave_hist_add(s_h, digit_of(k, d), active);
-        }
-        __syncthreads();
-        w.cnt[(uint64_t)threadIdx.x * s.tiles + v] = s_h[threadIdx.x];
-        __syncthreads();  // (read before the next tile zeroes it)
-    }
+    const auto digit_at = [&](uint64_t j, uint32_t &digit) {
+        Key k;
+        const bool active = s.load_key(j, k);
+        digit = digit_of(k, d);
+        return active;
+    };
+    for (uint64_t v = blockIdx.x; v < s.tiles; v += gridDim.x) (void)msj_radix::count_tile(s_h, w.cnt, s.tiles, v, digit_at);
 }
 __global__ __launch_bounds__(kScan) void do_scan(const Call call, const Work w, uint32_t d) {
     __shared__ uint64_t s_w[16];
     const Head h = load_head(call);
     const Pass s = load_pass(w, h, d);
     if (s.skip) return;
-    const uint64_t total = scan_in_place(w.cnt + (uint64_t)blockIdx.x * s.tiles, s.tiles, s_w);  // (bucket blockIdx.x)
+    const uint64_t total = msj_radix::scan_bucket(w.cnt, s.tiles, s_w);
     if (threadIdx.x == 0) w.st->tot[blockIdx.x] = (uint32_t)total;
 }
 __global__ __launch_bounds__(kThreads) void do_scatter(const Call call, const Work w, uint32_t d) {
@@ -494,51 +432,8 @@ __global__ __launch_bounds__(kThreads) void do_scatter(const Call call, const Wo
     const Head h = load_head(call);
     const Pass s = load_pass(w, h, d);
     if (s.skip) return;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // the entries in the buckets in front
-    const uint32_t mine = w.st->tot[threadIdx.x];
-    uint32_t inc = wave_scan32(mine, (int)lane);
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    inc = add_waves_before(inc, s_w, (int)wave);
-    const uint32_t base = inc - mine;
-    for (uint64_t v = blockIdx.x; v < s.tiles; v += gridDim.x) {
-        __syncthreads();  // (the last tile's counters have been read)
-        s_run[threadIdx.x] = base + w.cnt[(uint64_t)threadIdx.x * s.tiles + v];  // where the tile's first entry of the bucket goes
-#pragma unroll
-        for (uint32_t x = 0; x < (uint32_t)kWaves; x++) s_wcnt[x][threadIdx.x] = 0;
-        __syncthreads();
-        for (uint32_t r = 0; r < kRounds; r++) {
-            const uint64_t j = v * kTile + r * kRows + threadIdx.x;
-            const bool active = j < s.n;
-            Key k;
-            k.word = active ? s.src_word[j] : 0, k.rn = active ? s.src_rn[j] : 0;
-            const uint32_t ent = active ? s.src_ent[j] : 0u;
-            const uint32_t digit = digit_of(k, d);
-            // the wave's active lanes with my digit
-            uint64_t peers = __ballot(active);
-#pragma unroll
-            for (uint32_t b = 0; b < kDigitBits; b++) {
-                const bool bit = (digit >> b) & 1u;
-                const uint64_t set = __ballot(bit);
-                peers &= bit ? set : ~set;
-            }
-            const uint32_t rank = lanes_below(peers);
-            if (active && rank == 0) s_wcnt[wave][digit] = (uint32_t)__popcll((unsigned long long)peers);
-            __syncthreads();
-            if (active) {
-                uint32_t at = s_run[digit] + rank;
-                for (uint32_t x = 0; x < wave; x++) at += s_wcnt[x][digit];
-                if (at < s.n) s.dst_word[at] = k.word, s.dst_rn[at] = k.rn, s.dst_ent[at] = ent;  // (always: the counts are the entries' own)
-            }
-            __syncthreads();
-            uint32_t round = 0;
-#pragma unroll
-            for (uint32_t x = 0; x < (uint32_t)kWaves; x++) round += s_wcnt[x][threadIdx.x], s_wcnt[x][threadIdx.x] = 0;
-            s_run[threadIdx.x] += round;
-            __syncthreads();
-        }
-    }
+    const uint32_t base = msj_radix::bucket_base(w.st->tot, s_w);  // the entries in the buckets in front
+    for (uint64_t v = blockIdx.x; v < s.tiles; v += gridDim.x) msj_radix::scatter_tile(s_run, s_wcnt, base, w.cnt, s.tiles, v, s);
 }
 
 // ---- back to their places; the new groups -------------------------------------------------------------------------------------
@@ -548,7 +443,7 @@ __global__ __launch_bounds__(kThreads) void do_heads(const Call call, const Work
     const uint64_t n = round_tied(h, w);
     if (n == 0) return;
     const uint32_t f = passes_before(w.st->mask, kMaxDigits) & 1u;  // the buffer the last pass wrote
-    const uint64_t tiles = (n + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(n);
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         uint32_t most = 0;
         for (uint32_t r = 0; r < kRounds; r++) {
@@ -579,7 +474,7 @@ __global__ __launch_bounds__(kScan) void do_heads_scan(const Call call, const Wo
     const Head h = load_head(call);
     const uint64_t n = round_tied(h, w);
     if (n == 0) return;
-    scan_max_in_place(w.tmax, (n + kTile - 1) / kTile, s_w);
+    scan_max_in_place(w.tmax, tiles_of(n), s_w);
 }
 __global__ __launch_bounds__(kThreads) void do_rank(const Call call, const Work w) {
     __shared__ uint32_t s_w[kWaves];
@@ -587,7 +482,7 @@ __global__ __launch_bounds__(kThreads) void do_rank(const Call call, const Work 
     const uint64_t n = round_tied(h, w);
     if (n == 0) return;
     const uint32_t f = passes_before(w.st->mask, kMaxDigits) & 1u;
-    const uint64_t tiles = (n + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(n);
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         uint32_t run = w.tmax[v];
         for (uint32_t r = 0; r < kRounds; r++) {
@@ -608,7 +503,7 @@ __global__ __launch_bounds__(kThreads) void do_finish_count(const Call call, con
     const Head h = load_head(call);
     if (h.stop) return;
     const uint64_t depth = call.depth + (uint64_t)kWordBytes * w.st->rounds_run;
-    const uint64_t tiles = (h.V + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(h.V);
     uint32_t n_values = 0, n_tied = 0, n_equal = 0;
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
 #pragma unroll

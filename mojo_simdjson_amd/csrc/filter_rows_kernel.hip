@@ -161,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void fr_place(const Rows rows, const Work
         const uint64_t k = v * kRows + threadIdx.x;
         const bool is_kept = k < h.R && keep[k] != 0;
         const uint64_t m = __ballot(is_kept);
-        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const uint32_t below = lanes_below(m);
         __syncthreads();  // (the last round's totals have been read)
         if (lane == 0) s_tot[wave] = (uint32_t)__popcll((unsigned long long)m);
         __syncthreads();

@@ -8,15 +8,13 @@
 // Launches, all on the caller's stream, behind a memset of the call's state; the steps are separated by kernel boundaries
 // only, and no lane ever waits for another lane or workgroup:
 //   jn_clear    count[0 .. G] = 0
-//   jn_count(p), jn_scan(p), jn_scatter(p)   one least-significant-digit pass over the right rows, key_passes(G) of them (the
-//               launches behind that return at once).  A block owns tiles of kTile = 1 024 consecutive rows: its count per
-//               bucket to cnt[bucket][tile]; 256 workgroups, one per bucket, turn a bucket's counts into running sums (kScan
-//               = 1 024 tiles per chunk) and leave the bucket's total; the scatter ranks a tile's rows in four rounds of 256
-//               -- a wave's rows of one bucket by ballots (v_mbcnt), the waves and the rounds in front by counters in LDS --
-//               so that rows of one bucket keep their order: stable, which is "ascending r inside a key".  Pass 0 reads the
-//               caller's keys, leaves out the rows without a key (n_right_null) and counts count[key]: through the block's
-//               LDS histogram when G <= 256 -- the digit is the key --, else by one integer atomic per row (one per wave
-//               where the wave's rows share the key).  The words are (key, row number), four bytes each, in two buffers
+//   jn_count(p), jn_scan(p), jn_scatter(p)   one stable least-significant-digit pass over the right rows, radix_block.h's,
+//               key_passes(G) of them (the launches behind that return at once): counts per (bucket, tile of 1 024 rows),
+//               256 workgroups scan a bucket each and leave its total, the scatter ranks by ballots and LDS counters.
+//               Stable is "ascending r inside a key".  Pass 0 reads the caller's keys, leaves out the rows without a key
+//               (n_right_null) and counts count[key]: through the block's LDS histogram when G <= 256 -- the digit is the
+//               key --, else by one integer atomic per row (one per wave where the wave's rows share the key).  The words
+//               are (key, row number), four bytes each, in two buffers; the last pass stores no key
 //   jn_start_sums, jn_start_scan, jn_start_apply   count[0 .. G] becomes its running sum: start[key], and start[G] = the rows
 //               with a key
 //   jn_left     a lane per left row: c(l) = start[key + 1] - start[key], n(l) into offsets[l], where the row's run starts
@@ -39,21 +37,20 @@
 #include "bytes_block.h"
 #include "join_rows_math.h"
 #include "launch.h"
+#include "radix_block.h"
 
 namespace msj_jrows {
 
 using namespace msj::jrows;
 using namespace msj::wave;
 using msj_bytes::kRows, msj_bytes::most_rows;
-using msj_tape::kThreads, msj_tape::kWaves;
+using msj_radix::kRounds, msj_radix::kScan, msj_radix::kTile, msj_radix::kTileBlocks, msj_radix::tiles_of;  // also of keys and pairs
+using msj_tape::block_scan, msj_tape::kThreads, msj_tape::kWaves;
 
 static_assert(sizeof(msj_join_rows_result) == 64 && sizeof(msj_select_documents_result) == 48, "ABI");
 static_assert(kRows == (uint32_t)kThreads && kWaves == 4 && kBuckets == (uint32_t)kThreads, "geometry");
+static_assert(kBuckets == msj_radix::kBuckets && kDigitBits == msj_radix::kDigitBits, "the radix pass takes join_rows_math.h's digits");
 
-constexpr uint32_t kRounds = 4;
-constexpr uint32_t kTile = kRounds * kRows;  // rows, keys or pairs of a block's tile
-constexpr uint32_t kScan = 1024;             // entries per chunk of scan_in_place's workgroup
-constexpr uint32_t kTileBlocks = 1024;       // most blocks of the kernels over tiles of rows or keys
 constexpr uint32_t kEmitBlocks = 4096;       // most blocks of jn_emit
 constexpr uint32_t kClearBlocks = 4096;      // most blocks of jn_clear
 constexpr uint32_t kStage = kTile + 1;       // offsets jn_emit stages in LDS
@@ -87,7 +84,6 @@ struct Call {
     uint64_t pairs_capacity;
 };
 
-static inline uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
 static inline Work layout(msj_carver &c, uint64_t left_rows, uint64_t right_rows, uint64_t keys_capacity) {
     const uint64_t l = most_rows(left_rows), r = most_rows(right_rows), g = most_keys(keys_capacity) + 1;
     Work w;
@@ -120,40 +116,6 @@ __device__ __forceinline__ Head load_head(const Call &call) {
     return h;
 }
 
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-// one more row in hist[x] for every active lane; a wave whose active lanes share one x adds once
-__device__ __forceinline__ void wave_hist_add(uint32_t *hist, uint32_t x, bool active) {
-    const uint64_t m = __ballot(active);
-    if (m == 0) return;
-    const int first_lane = __ffsll((unsigned long long)m) - 1;
-    const uint32_t first = (uint32_t)__shfl((int)x, first_lane);
-    if (__ballot(active && x != first) == 0) {
-        if ((int)(threadIdx.x & 63) == first_lane) atomicAdd(&hist[first], (uint32_t)__popcll((unsigned long long)m));
-    } else if (active) {
-        atomicAdd(&hist[x], 1u);
-    }
-}
-// x summed over the lanes in front in the workgroup, and over all of them (s_w: kWaves words no lane still reads)
-template <class T>
-__device__ __forceinline__ T block_scan_exclusive(T x, T *s_w, T &total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const T inc = wave_scan(x);
-    __syncthreads();  // (the last round's totals have been read)
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (uint32_t x2 = 0; x2 < (uint32_t)kWaves; x2++) {
-        const T t = s_w[x2];
-        if (x2 < wave) before += t;
-        all += t;
-    }
-    total = all;
-    return before + inc - x;
-}
-
 __global__ __launch_bounds__(kThreads) void jn_clear(const Call call, const Work w) {
     const Head h = load_head(call);
     if (h.stop) return;
@@ -161,20 +123,44 @@ __global__ __launch_bounds__(kThreads) void jn_clear(const Call call, const Work
 }
 
 // ---- the right rows in the order of their keys --------------------------------------------------------------------------------
+// a pass, and as radix_block.h's policy a right row of its scatter: (key, row number)
 struct Pass {
+    struct Record {
+        uint32_t key, row;
+    };
     uint64_t n, valid, tiles;  // the rows the pass reads; the rows with a key (pass 0: not known yet)
+    uint64_t keys;
+    uint32_t p;
     const uint32_t *src_key, *src_row;
     uint32_t *dst_key, *dst_row;
     bool skip, first, last;
+    // pass 0 reads the caller's keys: the row number is the position, and a row without a key stays behind
+    __device__ __forceinline__ bool load(uint64_t j, Record &x) const {
+        bool active = j < n;
+        x.key = 0, x.row = (uint32_t)j;
+        if (active) {
+            x.key = src_key[j];
+            if (first) active = is_key((int32_t)x.key, keys);
+            else x.row = src_row[j];
+        }
+        return active;
+    }
+    __device__ __forceinline__ uint32_t digit(const Record &x) const { return digit_of(x.key, p); }
+    __device__ __forceinline__ uint64_t bound() const { return valid; }
+    __device__ __forceinline__ void store(uint32_t at, const Record &x) const {
+        dst_row[at] = x.row;
+        if (!last) dst_key[at] = x.key;
+    }
 };
 __device__ __forceinline__ Pass load_pass(const Call &call, const Work &w, const Head &h, uint32_t p) {
     Pass s;
+    s.keys = h.keys, s.p = p;
     s.skip = h.stop || p >= h.passes;
     s.first = p == 0, s.last = p + 1 == h.passes;
     const uint64_t nulls = w.st->n_right_null;  // (complete behind pass 0's count)
     s.valid = h.R >= nulls ? h.R - nulls : 0;
     s.n = s.skip ? 0 : s.first ? h.R : s.valid;
-    s.tiles = (s.n + kTile - 1) / kTile;
+    s.tiles = tiles_of(s.n);
     s.src_key = s.first ? reinterpret_cast<const uint32_t *>(call.right_keys) : w.key[(p - 1) & 1u];
     s.src_row = s.first ? nullptr : w.row[(p - 1) & 1u];
     s.dst_key = w.key[p & 1u], s.dst_row = w.row[p & 1u];
@@ -189,28 +175,19 @@ __global__ __launch_bounds__(kThreads) void jn_count(const Call call, const Work
     const bool small = h.keys <= kBuckets;  // the digit is the key: count[key] through s_tot
     s_tot[threadIdx.x] = 0;
     uint32_t nulls = 0;
-    for (uint64_t v = blockIdx.x; v < s.tiles; v += gridDim.x) {
-        s_h[threadIdx.x] = 0;
-        __syncthreads();
-#pragma unroll
-        for (uint32_t r = 0; r < kRounds; r++) {
-            const uint64_t j = v * kTile + r * kRows + threadIdx.x;
-            bool active = j < s.n;
-            const uint32_t key = active ? s.src_key[j] : 0u;  // (j < R <= right_rows; j < valid <= R)
-            if (s.first) {
-                const bool valid = active && is_key((int32_t)key, h.keys);
-                nulls += active && !valid;
-                active = valid;
-                if (!small) wave_hist_add(w.start, key, active);  // (key < keys)
-            }
-            wave_hist_add(s_h, digit_of(key, p), active);
+    const auto digit_at = [&](uint64_t j, uint32_t &digit) {
+        bool active = j < s.n;
+        const uint32_t key = active ? s.src_key[j] : 0u;  // (j < R <= right_rows; j < valid <= R)
+        if (s.first) {
+            const bool valid = active && is_key((int32_t)key, h.keys);
+            nulls += active && !valid;
+            active = valid;
+            if (!small) wave_hist_add(w.start, key, active);  // (key < keys)
         }
-        __syncthreads();
-        const uint32_t mine = s_h[threadIdx.x];
-        w.cnt[(uint64_t)threadIdx.x * s.tiles + v] = mine;
-        s_tot[threadIdx.x] += mine;
-        __syncthreads();  // (read before the next tile zeroes it)
-    }
+        digit = digit_of(key, p);
+        return active;
+    };
+    for (uint64_t v = blockIdx.x; v < s.tiles; v += gridDim.x) s_tot[threadIdx.x] += msj_radix::count_tile(s_h, w.cnt, s.tiles, v, digit_at);
     if (!s.first) return;
     if (small && threadIdx.x < h.keys && s_tot[threadIdx.x]) atomicAdd(&w.start[threadIdx.x], s_tot[threadIdx.x]);
     (void)block_counter_add(nulls, s_n, reinterpret_cast<uint64_t *>(&w.st->n_right_null));
@@ -221,7 +198,7 @@ __global__ __launch_bounds__(kScan) void jn_scan(const Call call, const Work w, 
     const Head h = load_head(call);
     const Pass s = load_pass(call, w, h, p);
     if (s.skip) return;
-    const uint64_t total = scan_in_place(w.cnt + (uint64_t)blockIdx.x * s.tiles, s.tiles, s_w);  // (bucket blockIdx.x; a sum stays below R < 2^31)
+    const uint64_t total = msj_radix::scan_bucket(w.cnt, s.tiles, s_w);
     if (threadIdx.x == 0) w.st->tot[p][blockIdx.x] = (uint32_t)total;
 }
 
@@ -230,57 +207,8 @@ __global__ __launch_bounds__(kThreads) void jn_scatter(const Call call, const Wo
     const Head h = load_head(call);
     const Pass s = load_pass(call, w, h, p);
     if (s.skip) return;
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // the rows in the buckets in front
-    const uint32_t mine = w.st->tot[p][threadIdx.x];
-    uint32_t inc = wave_scan32(mine, (int)lane);
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    inc = add_waves_before(inc, s_w, (int)wave);
-    const uint32_t base = inc - mine;
-    for (uint64_t v = blockIdx.x; v < s.tiles; v += gridDim.x) {
-        __syncthreads();  // (the last tile's counters have been read)
-        s_run[threadIdx.x] = base + w.cnt[(uint64_t)threadIdx.x * s.tiles + v];  // where the tile's first row of the bucket goes
-#pragma unroll
-        for (uint32_t x = 0; x < (uint32_t)kWaves; x++) s_wcnt[x][threadIdx.x] = 0;
-        __syncthreads();
-        for (uint32_t r = 0; r < kRounds; r++) {
-            const uint64_t j = v * kTile + r * kRows + threadIdx.x;
-            bool active = j < s.n;
-            uint32_t key = 0, row = (uint32_t)j;
-            if (active) {
-                key = s.src_key[j];
-                if (s.first) active = is_key((int32_t)key, h.keys);
-                else row = s.src_row[j];
-            }
-            const uint32_t digit = digit_of(key, p);
-            // the wave's active lanes with my digit
-            uint64_t peers = __ballot(active);
-#pragma unroll
-            for (uint32_t b = 0; b < kDigitBits; b++) {
-                const bool bit = (digit >> b) & 1u;
-                const uint64_t set = __ballot(bit);
-                peers &= bit ? set : ~set;
-            }
-            const uint32_t rank = lanes_below(peers);
-            if (active && rank == 0) s_wcnt[wave][digit] = (uint32_t)__popcll((unsigned long long)peers);
-            __syncthreads();
-            if (active) {
-                uint32_t at = s_run[digit] + rank;
-                for (uint32_t x = 0; x < wave; x++) at += s_wcnt[x][digit];
-                if (at < s.valid) {  // (always: the counts are the rows' own)
-                    s.dst_row[at] = row;
-                    if (!s.last) s.dst_key[at] = key;
-                }
-            }
-            __syncthreads();
-            uint32_t round = 0;
-#pragma unroll
-            for (uint32_t x = 0; x < (uint32_t)kWaves; x++) round += s_wcnt[x][threadIdx.x], s_wcnt[x][threadIdx.x] = 0;
-            s_run[threadIdx.x] += round;
-            __syncthreads();
-        }
-    }
+    const uint32_t base = msj_radix::bucket_base(w.st->tot[p], s_w);  // the rows in the buckets in front
+    for (uint64_t v = blockIdx.x; v < s.tiles; v += gridDim.x) msj_radix::scatter_tile(s_run, s_wcnt, base, w.cnt, s.tiles, v, s);
 }
 
 // ---- count[0 .. G] becomes start[0 .. G] --------------------------------------------------------------------------------------
@@ -288,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void jn_start_sums(const Call call, const
     __shared__ uint32_t s_w[kWaves];
     const Head h = load_head(call);
     if (h.stop) return;
-    const uint64_t n = h.keys + 1, tiles = (n + kTile - 1) / kTile;
+    const uint64_t n = h.keys + 1, tiles = tiles_of(n);
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         uint32_t sum = 0;
 #pragma unroll
@@ -297,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void jn_start_sums(const Call call, const
             sum += i < n ? w.start[i] : 0u;
         }
         uint32_t total;
-        (void)block_scan_exclusive(sum, s_w, total);
+        (void)block_scan(sum, s_w, total);
         if (threadIdx.x == 0) w.csum[v] = total;  // (below R < 2^31)
     }
 }
@@ -305,20 +233,20 @@ __global__ __launch_bounds__(kScan) void jn_start_scan(const Call call, const Wo
     __shared__ uint64_t s_w[16];
     const Head h = load_head(call);
     if (h.stop) return;
-    (void)scan_in_place(w.csum, (h.keys + 1 + kTile - 1) / kTile, s_w);
+    (void)scan_in_place(w.csum, tiles_of(h.keys + 1), s_w);
 }
 __global__ __launch_bounds__(kThreads) void jn_start_apply(const Call call, const Work w) {
     __shared__ uint32_t s_w[kWaves];
     const Head h = load_head(call);
     if (h.stop) return;
-    const uint64_t n = h.keys + 1, tiles = (n + kTile - 1) / kTile;
+    const uint64_t n = h.keys + 1, tiles = tiles_of(n);
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         uint32_t run = w.csum[v];
         for (uint32_t r = 0; r < kRounds; r++) {
             const uint64_t i = v * kTile + r * kRows + threadIdx.x;
             const uint32_t x = i < n ? w.start[i] : 0u;
             uint32_t total;
-            const uint32_t before = block_scan_exclusive(x, s_w, total);
+            const uint32_t before = block_scan(x, s_w, total);
             if (i < n) w.start[i] = run + before;
             run += total;
         }
@@ -331,7 +259,7 @@ __global__ __launch_bounds__(kThreads) void jn_left(const Call call, const Work 
     __shared__ uint32_t s_a[kWaves], s_b[kWaves];
     const Head h = load_head(call);
     if (h.stop) return;
-    const uint64_t tiles = (h.L + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(h.L);
     uint32_t nulls = 0, matched = 0;
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         uint64_t sum = 0;
@@ -350,7 +278,7 @@ __global__ __launch_bounds__(kThreads) void jn_left(const Call call, const Work 
             sum += n;
         }
         uint64_t total;
-        (void)block_scan_exclusive(sum, s_sum, total);
+        (void)block_scan(sum, s_sum, total);
         if (threadIdx.x == 0) w.bsum[v] = total;
     }
     (void)block_counter_add(nulls, s_a, reinterpret_cast<uint64_t *>(&w.st->n_left_null));
@@ -363,7 +291,7 @@ __global__ __launch_bounds__(kScan) void jn_total(const Call call, const Work w,
     __shared__ uint64_t s_w[16];
     const Head h = load_head(call);
     uint64_t M = 0;
-    if (!h.stop) M = scan_in_place(w.bsum, (h.L + kTile - 1) / kTile, s_w);
+    if (!h.stop) M = scan_in_place(w.bsum, tiles_of(h.L), s_w);
     if (threadIdx.x != 0) return;
     msj_join_rows_result r;
     r.code = h.stop || pairs_over(M, call.pairs_capacity) ? MSJ_CAPACITY : 0;
@@ -388,14 +316,14 @@ __global__ __launch_bounds__(kThreads) void jn_offsets(const Call call, const Wo
     __shared__ uint64_t s_w[kWaves];
     const Head h = load_head(call);
     if (h.stop) return;
-    const uint64_t tiles = (h.L + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(h.L);
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         uint64_t run = w.bsum[v];
         for (uint32_t r = 0; r < kRounds; r++) {
             const uint64_t l = v * kTile + r * kRows + threadIdx.x;
             const uint64_t x = l < h.L ? off[l] : 0;
             uint64_t total;
-            const uint64_t before = block_scan_exclusive(x, s_w, total);
+            const uint64_t before = block_scan(x, s_w, total);
             if (l < h.L) off[l] = run + before;
             run += total;
         }
@@ -429,7 +357,7 @@ __global__ __launch_bounds__(kThreads) void jn_emit(const Call call, const Work 
     if (M == 0 || pairs_over(M, call.pairs_capacity)) return;
     const uint64_t nulls = w.st->n_right_null, valid = h.R >= nulls ? h.R - nulls : 0;
     const uint32_t *sorted = w.row[(h.passes - 1) & 1u];
-    const uint64_t tiles = (M + kTile - 1) / kTile;
+    const uint64_t tiles = tiles_of(M);
     for (uint64_t v = blockIdx.x; v < tiles; v += gridDim.x) {
         const uint64_t j0 = v * kTile, j1 = (j0 + kTile < M ? j0 + kTile : M) - 1;
         const uint64_t lo = block_row_of_pair(off, 0, h.L, j0);  // (off[0] = 0 <= j0 < M = off[L])

@@ -1,7 +1,8 @@
 // launch.h -- launch interface between stage2_api.cpp and the kernel files behind stage 1: tokens_kernel.hip (rows f1 /
 // f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
 // validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
-// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, dictionary_extend_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip, join_rows_kernel.hip, dictionary_order_kernel.hip.  Every launcher and every internal workspace size is declared
+// array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, dictionary_extend_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip, join_rows_kernel.hip, dictionary_order_kernel.hip (the last three over
+// radix_block.h's one radix pass).  Every launcher and every internal workspace size is declared
 // here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
 // compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
 // (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.

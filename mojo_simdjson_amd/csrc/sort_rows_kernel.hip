@@ -23,12 +23,10 @@
 //               order into buffer 1 (block counts, one workgroup's running sum, ballot ranks), with their digit histograms
 //   sr_plan     one workgroup: the rows to sort (all N in buffer 0, or the survivors in buffer 1), per digit whether it is
 //               constant over them -- its pass is skipped -- and the buffer each pass reads, and the start of every bucket
-//   sr_count(d), sr_scan(d), sr_scatter(d)   one least-significant-digit pass.  A block owns tiles of kTile = 1 024
-//               consecutive rows: its count per bucket to cnt[bucket][tile]; 256 workgroups, one per bucket, turn a
-//               bucket's counts into running sums (kScan = 1 024 tiles per chunk); the scatter ranks a tile's rows in
-//               four rounds of 256 -- a wave's rows of one bucket by ballots (v_mbcnt: the same bucket in the lanes
-//               below), the waves in front and the rounds in front by counters in LDS -- so that rows of one bucket keep
-//               their order: stable.  All three return at once for a constant digit
+//   sr_count(d), sr_scan(d), sr_scatter(d)   one stable least-significant-digit pass, radix_block.h's: counts per (bucket,
+//               tile of 1 024 rows), 256 workgroups scan a bucket each, the scatter ranks by ballots and LDS counters.  The
+//               bucket starts are the plan's; sr_count reads the one word that holds the digit.  All three return at once
+//               for a constant digit
 //   sr_finish   d_order[i] = the row number at the i-th position for i < K, the result, d_order_select
 // Every count is an integer sum and every place a function of the counts: the same bytes from run to run, on both paths.
 // Safety: a record is read only at a row below R <= stride; d_rows_in only below N <= capacity; the buffers only below the
@@ -39,6 +37,7 @@
 #include "../../include/msj_stage1.h"
 #include "bytes_block.h"
 #include "launch.h"
+#include "radix_block.h"
 #include "sort_rows_math.h"
 
 namespace msj_srows {
@@ -46,17 +45,15 @@ namespace msj_srows {
 using namespace msj::srows;
 using namespace msj::wave;
 using msj_bytes::kRows, msj_bytes::most_rows;
+using msj_radix::kScan, msj_radix::kTileBlocks, msj_radix::tiles_of;
 using msj_tape::kThreads, msj_tape::kWaves;
 using msj_tdocs::load_field;
 
 static_assert(sizeof(msj_sort_rows_result) == 48 && sizeof(msj_field) == 16, "ABI");
 static_assert(kRows == (uint32_t)kThreads && kWaves == 4 && kBuckets == (uint32_t)kThreads, "geometry");
+static_assert(kBuckets == msj_radix::kBuckets, "the radix pass takes sort_rows_math.h's digits");
 
-constexpr uint32_t kRounds = 4;
-constexpr uint32_t kTile = kRounds * kRows;  // rows of a tile of the radix passes
-constexpr uint32_t kScan = 1024;             // tiles per chunk of sr_scan: scan_in_place's workgroup
-constexpr uint32_t kRowBlocks = 4096;        // most blocks of the kernels with a lane per row (they loop over what N needs)
-constexpr uint32_t kTileBlocks = 1024;       // most blocks of sr_count / sr_scatter
+constexpr uint32_t kRowBlocks = 4096;  // most blocks of the kernels with a lane per row (they loop over what N needs)
 
 struct Select {  // the selection's progress
     uint32_t pd[kDigits];  // the prefix: the digits fixed so far
@@ -96,7 +93,6 @@ struct Call {
     uint64_t limit, capacity;
 };
 
-static inline uint64_t tiles_of(uint64_t rows) { return (rows + kTile - 1) / kTile; }
 static inline Work layout(msj_carver &c, uint64_t capacity) {
     const uint64_t rows = most_rows(capacity);
     Work w;
@@ -127,21 +123,6 @@ __device__ __forceinline__ Head load_head(const Call &call) {
 }
 __device__ __forceinline__ uint64_t select_k(const Call &call, const Head &h) { return call.limit < h.N ? call.limit : h.N; }
 
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-// one more row in hist[digit] for every active lane; a wave whose active lanes share one digit adds once
-__device__ __forceinline__ void wave_hist_add(uint32_t *hist, uint32_t digit, bool active) {
-    const uint64_t m = __ballot(active);
-    if (m == 0) return;
-    const int first_lane = __ffsll((unsigned long long)m) - 1;
-    const uint32_t first = (uint32_t)__shfl((int)digit, first_lane);
-    if (__ballot(active && digit != first) == 0) {
-        if ((int)(threadIdx.x & 63) == first_lane) atomicAdd(&hist[first], (uint32_t)__popcll((unsigned long long)m));
-    } else if (active) {
-        atomicAdd(&hist[digit], 1u);
-    }
-}
 // a block's LDS histograms of all the digits, zeroed / added to the global ones (lanes = kBuckets)
 __device__ __forceinline__ void hist_zero(uint32_t (*s_hist)[kBuckets]) {
     for (uint32_t d = 0; d < kDigits; d++) s_hist[d][threadIdx.x] = 0;
@@ -338,7 +319,7 @@ __device__ __forceinline__ Pass load_pass(const Work &w, uint32_t d) {
     p.n = w.st->plan.n;  // (0 while the call stops: the memset's)
     p.skip = p.n == 0 || w.st->plan.skip[d] != 0;
     p.src = w.st->plan.src[d] & 1u;
-    p.tiles = (p.n + kTile - 1) / kTile;
+    p.tiles = tiles_of(p.n);
     return p;
 }
 
@@ -347,72 +328,48 @@ __global__ __launch_bounds__(kThreads) void sr_count(const Work w, uint32_t d) {
     const Pass p = load_pass(w, d);
     if (p.skip) return;
     const uint64_t *words = digit_in_hi(d) ? w.hi[p.src] : w.aux[p.src];
-    for (uint64_t v = blockIdx.x; v < p.tiles; v += gridDim.x) {
-        s_h[threadIdx.x] = 0;
-        __syncthreads();
-#pragma unroll
-        for (uint32_t r = 0; r < kRounds; r++) {
-            const uint64_t j = v * kTile + r * kRows + threadIdx.x;
-            const bool active = j < p.n;
-            wave_hist_add(s_h, active ? digit_of_word(words[j], d) : 0u, active);
-        }
-        __syncthreads();
-        w.cnt[(uint64_t)threadIdx.x * p.tiles + v] = s_h[threadIdx.x];
-        __syncthreads();  // (read before the next tile zeroes it)
-    }
+    const auto digit_at = [&](uint64_t j, uint32_t &digit) {
+        const bool active = j < p.n;
+        digit = active ? digit_of_word(words[j], d) : 0u;
+        return active;
+    };
+    for (uint64_t v = blockIdx.x; v < p.tiles; v += gridDim.x) (void)msj_radix::count_tile(s_h, w.cnt, p.tiles, v, digit_at);
 }
 
 __global__ __launch_bounds__(kScan) void sr_scan(const Work w, uint32_t d) {
     __shared__ uint64_t s_w[16];
     const Pass p = load_pass(w, d);
     if (p.skip) return;
-    (void)scan_in_place(w.cnt + (uint64_t)blockIdx.x * p.tiles, p.tiles, s_w);  // (bucket blockIdx.x; a sum stays below n < 2^31)
+    (void)msj_radix::scan_bucket(w.cnt, p.tiles, s_w);
 }
+
+// a row of the scatter: its two words, from one pair of buffers to the other
+struct Rows {
+    struct Record {
+        uint64_t hi, aux;
+    };
+    const uint64_t *src_hi, *src_aux;
+    uint64_t *dst_hi, *dst_aux;
+    uint64_t n;
+    uint32_t d;
+    __device__ __forceinline__ bool load(uint64_t j, Record &x) const {
+        const bool active = j < n;
+        x.hi = 0, x.aux = 0;
+        if (active) x.hi = src_hi[j], x.aux = src_aux[j];
+        return active;
+    }
+    __device__ __forceinline__ uint32_t digit(const Record &x) const { return digit_of(x.hi, x.aux, d); }
+    __device__ __forceinline__ uint64_t bound() const { return n; }
+    __device__ __forceinline__ void store(uint32_t at, const Record &x) const { dst_hi[at] = x.hi, dst_aux[at] = x.aux; }
+};
 
 __global__ __launch_bounds__(kThreads) void sr_scatter(const Work w, uint32_t d) {
     __shared__ uint32_t s_run[kBuckets], s_wcnt[kWaves][kBuckets];
     const Pass p = load_pass(w, d);
     if (p.skip) return;
-    const uint64_t *src_hi = w.hi[p.src], *src_aux = w.aux[p.src];
-    uint64_t *dst_hi = w.hi[p.src ^ 1u], *dst_aux = w.aux[p.src ^ 1u];
-    const uint32_t wave = threadIdx.x >> 6;
+    const Rows rows{w.hi[p.src], w.aux[p.src], w.hi[p.src ^ 1u], w.aux[p.src ^ 1u], p.n, d};
     const uint32_t base = w.st->plan.base[d][threadIdx.x];
-    for (uint64_t v = blockIdx.x; v < p.tiles; v += gridDim.x) {
-        __syncthreads();  // (the last tile's counters have been read)
-        s_run[threadIdx.x] = base + w.cnt[(uint64_t)threadIdx.x * p.tiles + v];  // where the tile's first row of the bucket goes
-#pragma unroll
-        for (uint32_t x = 0; x < kWaves; x++) s_wcnt[x][threadIdx.x] = 0;
-        __syncthreads();
-        for (uint32_t r = 0; r < kRounds; r++) {
-            const uint64_t j = v * kTile + r * kRows + threadIdx.x;
-            const bool active = j < p.n;
-            uint64_t hi = 0, aux = 0;
-            if (active) hi = src_hi[j], aux = src_aux[j];
-            const uint32_t digit = digit_of(hi, aux, d);
-            // the wave's active lanes with my digit
-            uint64_t peers = __ballot(active);
-#pragma unroll
-            for (uint32_t b = 0; b < 8; b++) {
-                const bool bit = (digit >> b) & 1u;
-                const uint64_t set = __ballot(bit);
-                peers &= bit ? set : ~set;
-            }
-            const uint32_t rank = lanes_below(peers);
-            if (active && rank == 0) s_wcnt[wave][digit] = (uint32_t)__popcll((unsigned long long)peers);
-            __syncthreads();
-            if (active) {
-                uint32_t at = s_run[digit] + rank;
-                for (uint32_t x = 0; x < wave; x++) at += s_wcnt[x][digit];
-                if (at < p.n) dst_hi[at] = hi, dst_aux[at] = aux;  // (always: the counts are the rows' own)
-            }
-            __syncthreads();
-            uint32_t round = 0;
-#pragma unroll
-            for (uint32_t x = 0; x < kWaves; x++) round += s_wcnt[x][threadIdx.x], s_wcnt[x][threadIdx.x] = 0;
-            s_run[threadIdx.x] += round;
-            __syncthreads();
-        }
-    }
+    for (uint64_t v = blockIdx.x; v < p.tiles; v += gridDim.x) msj_radix::scatter_tile(s_run, s_wcnt, base, w.cnt, p.tiles, v, rows);
 }
 
 __global__ __launch_bounds__(kThreads) void sr_finish(const Call call, const Work w, uint32_t *__restrict__ order, msj_sort_rows_result *__restrict__ result,

@@ -1,7 +1,9 @@
 // wave_ops.h -- reductions and scans over one wave64 and the padded four-byte load that documents_kernel.hip,
 // numbers_kernel.hip, validate_kernel.hip, validate_docs_kernel.hip and tape_kernel.hip share; a workgroup's counter and
-// the running sum over an array by one workgroup, which the select and column kernels share.  Device code only.
-// (tokens_kernel.hip has its own DPP scans.)  The device code of the four older files is pinned instruction for
+// the running sum over an array by one workgroup, which the select and column kernels share; the ballot ranks, the
+// histogram add and the workgroup ranks and running maxima of the query kernels (filter_rows, cast_strings, sort_rows,
+// join_rows, dictionary_order; radix_block.h).  Device code only.  (tokens_kernel.hip has its own DPP scans and
+// stage1_kernel.hip its own ballot rank.)  The device code of the four older files is pinned instruction for
 // instruction: see the notes on the forms below.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -66,6 +68,35 @@ __device__ __forceinline__ uint32_t wave_rscan_min(uint32_t v) {
     return v;
 }
 
+// the lanes below this one whose bit is set in the ballot m (v_mbcnt): a flagged lane's rank inside its wave
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+// the wave's active lanes whose x agrees with this lane's in its low `Bits` bits: a ballot per bit
+template <uint32_t Bits>
+__device__ __forceinline__ uint64_t wave_match(uint32_t x, bool active) {
+    uint64_t peers = __ballot(active);
+#pragma unroll
+    for (uint32_t b = 0; b < Bits; b++) {
+        const bool bit = (x >> b) & 1u;
+        const uint64_t set = __ballot(bit);
+        peers &= bit ? set : ~set;
+    }
+    return peers;
+}
+// one more in hist[x] for every active lane; a wave whose active lanes share one x adds once
+__device__ __forceinline__ void wave_hist_add(uint32_t *hist, uint32_t x, bool active) {
+    const uint64_t m = __ballot(active);
+    if (m == 0) return;
+    const int first_lane = __ffsll((unsigned long long)m) - 1;
+    const uint32_t first = (uint32_t)__shfl((int)x, first_lane);
+    if (__ballot(active && x != first) == 0) {
+        if ((int)(threadIdx.x & 63) == first_lane) atomicAdd(&hist[first], (uint32_t)__popcll((unsigned long long)m));
+    } else if (active) {
+        atomicAdd(&hist[x], 1u);
+    }
+}
+
 // wave totals through LDS: lane 63 of every wave has left its inclusive sum in s_w[wave] and the workgroup has met at a
 // barrier; adds what the waves in front of `wave` hold to sum
 template <class A, class T, int N>
@@ -110,6 +141,63 @@ __device__ __forceinline__ uint64_t scan_in_place(T *__restrict__ a, uint64_t co
         run += all;
     }
     return run;
+}
+
+// the flagged lanes in front of this one in the workgroup of W waves, and all of them (s_w: W words no lane still reads)
+template <uint32_t W>
+__device__ __forceinline__ uint32_t block_flag_rank(bool flag, uint32_t *s_w, uint32_t &total) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t m = __ballot(flag);
+    __syncthreads();  // (the last round's totals have been read)
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll((unsigned long long)m);
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < W; x++) {
+        const uint32_t t = s_w[x];
+        if (x < wave) before += t;
+        all += t;
+    }
+    total = all;
+    return before + lanes_below(m);
+}
+// the maximum of x over this lane and the lanes in front in the workgroup of W waves, and over all of them
+template <uint32_t W>
+__device__ __forceinline__ uint32_t block_scan_max(uint32_t x, uint32_t *s_w, uint32_t &total) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t inc = wave_scan_max(x);
+    __syncthreads();
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t y = 0; y < W; y++) {
+        const uint32_t t = s_w[y];
+        if (y < wave) before = max(before, t);
+        all = max(all, t);
+    }
+    total = all;
+    return max(before, inc);
+}
+// a[0 .. count) becomes the maximum of the entries in front of each (0 at the first), by ONE workgroup of 1 024 lanes in
+// chunks of 1 024 (s_w: 16 words)
+__device__ __forceinline__ void scan_max_in_place(uint32_t *__restrict__ a, uint64_t count, uint32_t *s_w) {
+    uint32_t run = 0;
+    for (uint64_t v0 = 0; v0 < count; v0 += 1024) {
+        const uint64_t v = v0 + threadIdx.x;
+        const uint32_t x = v < count ? a[v] : 0u;
+        uint32_t total;
+        const uint32_t inc = block_scan_max<16>(x, s_w, total);
+        // what stands in front: the inclusive maximum of the lane in front, or at a wave's first lane that of the waves in front
+        uint32_t prev = (uint32_t)__shfl_up((int)inc, 1);
+        if ((threadIdx.x & 63) == 0) {
+            prev = 0;
+            for (uint32_t y = 0; y < (threadIdx.x >> 6); y++) prev = max(prev, s_w[y]);
+        }
+        if (v < count) a[v] = max(run, prev);
+        run = max(run, total);
+        __syncthreads();  // (s_w read before the next chunk writes it)
+    }
 }
 
 // bytes a[j .. j + 4) as one word, j a multiple of 4; bytes from n on read as 0

@@ -29,6 +29,7 @@ GROUP_ENTRIES = 1024
 ALPHABET = (0x00, ord("a"), ord("b"), 0x7F, 0x80, 0xFF)
 PREFIXES = (0, 7, 8, 9, 15, 16, 17, 63, 64, 65)
 LENGTHS = tuple(range(18)) + tuple(range(62, 67))
+RADIX_SIZES = (63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2 * 1024 + 1)  # a wave, a round of 256, a tile of 1 024
 
 
 class OrderResult(ctypes.Structure):
@@ -212,6 +213,17 @@ def corpus():
     for V in (GROUP_ENTRIES - 1, GROUP_ENTRIES, GROUP_ENTRIES + 1):
         pre = word(rng, 9)
         out[f"border-{V}"] = [None if rng.random() < 0.02 else (pre if rng.random() < 0.7 else b"") + word(rng, rng.choice((0, 1, 3, 8, 11))) for _ in range(V)]
+    # The grid path's radix pass (radix_block.h) at its borders: N entries, every one with a value, so that round 0 sorts a tied
+    # set of exactly N.  Byte 0 takes every bucket inside a tile; byte 2 is the same over 64 neighbours (a wave adds to the
+    # histogram once); byte 1 between them is constant: its pass is skipped, and the pass behind it reads the buffer that the
+    # NUMBER of passes in front says.  Equal values on both sides of a wave, a round and a tile border; entries 768 apart tie
+    # again in round 1
+    for N in RADIX_SIZES:
+        vals = [bytes([i % 256, 0x40, 1 + (i // 64) % 3]) + b"-----%04d" % (N - i) for i in range(N)]
+        for a in (63, 255, 1023):
+            if a + 1 < N:
+                vals[a + 1] = vals[a]
+        out[f"radix-{N}"] = vals
     return out
 
 
@@ -275,6 +287,13 @@ def test_constant_digits_cost_no_pass(tw):
     rc, res, srt, rnk, passes = run_twin(tw, d, max_rounds=64, mode=GRID)
     check_against(vals, res, srt, rnk, None, d.V)
     assert res.depth == 16 and passes == 4 + 1 + 2
+
+
+def test_a_constant_digit_between_two_that_differ(tw):
+    """radix-257, round 0: bytes 0 and 2 of the word differ (digits 8 and 6), byte 1 between them does not: two passes, the
+    second of which reads what ONE pass in front of it wrote"""
+    rc, res, _, _, passes = run_twin(tw, Dict(CORPUS["radix-257"]), max_rounds=1, mode=GRID)
+    assert rc == 0 and res.depth == 8 and passes == 2
 
 
 def test_capacity_and_empty(tw):

@@ -166,9 +166,9 @@ def test_kinds_with_nulls_on_both_sides(dev, jtw, kind):
     run_join(dev, jtw, lk, rk, 700, kind, held=held, pairs_capacity=held.room, want_right=False, want_offsets=False, want_selects=False, where="no optional output")
 
 
-@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 511, 512, 513, T - 1, T, T + 1, 2 * T + 1])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 255, 256, 257, 511, 512, 513, T - 1, T, T + 1, 2 * T + 1])
 def test_row_counts_around_the_waves_and_the_tile(dev, jtw, n):
-    """L and R mod 256 in {0, 1, 255}, and one row past a radix tile (kTile = 1 024)"""
+    """L and R on both sides of a wave, L and R mod 256 in {0, 1, 255}, and one row past a radix tile (kTile = 1 024)"""
     rng = np.random.default_rng(n)
     for kind in KINDS:
         run_join(dev, jtw, keys_with_nulls(rng, n, 300), keys_with_nulls(rng, 777, 300), 300, kind, where=("L", n, kind))
@@ -185,6 +185,15 @@ def test_digit_borders(dev, jtw, G):
     for kind in (INNER, LEFT):
         run_join(dev, jtw, draw(3000), draw(2600), G, kind, where=(G, kind))
     run_join(dev, jtw, draw(1500), draw(1500), G, SEMI, keys_capacity=G + 1000, where=(G, "room above G"))
+    # every right row with a key in ONE bucket in every pass (a wave adds to the histogram once) and equal keys across every
+    # wave, round and tile border: ascending r; rows without a key on both sides of a wave border and a tile border in pass 0
+    one = np.full(2 * T + 1, G - 1, dtype=np.int32)
+    one[[63, 64, T - 1, T]] = -1
+    want, _ = run_join(dev, jtw, np.array([G - 1, -1, G - 1], dtype=np.int32), one, G, INNER, where=(G, "one bucket"))
+    assert want.res.n_right_null == 4 and want.res.n_pairs == 2 * (2 * T - 3)
+    # all the buckets of pass 0 inside one tile
+    buckets = min(G, 256)
+    run_join(dev, jtw, np.arange(buckets, dtype=np.int32), (np.arange(T) % buckets).astype(np.int32), G, INNER, where=(G, "every bucket"))
 
 
 def test_hot_key(dev, jtw):
