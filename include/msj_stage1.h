@@ -152,6 +152,10 @@ int32_t msj_ctx_device(const msj_ctx *ctx); /* the HIP device the context was cr
  * default context on device 0 (created on first use).
  * utf8_verdict_out (optional): 0 valid, 11 invalid -- reported separately from
  * the return code unless MSJ_FLAG_STRICT_UTF8.
+ * On CAPACITY, UNCLOSED_STRING, UNESCAPED_CHARS and UNEXPECTED_ERROR n_out is
+ * not set and no trailer is written (as in the reference); inputs past the
+ * small-input path then leave min(n, idx_capacity) indices in idx_out, the
+ * same words whether the call staged plainly or through the pinned pipeline.
  */
 int32_t msj_stage1(const uint8_t *buf, uint64_t len, uint32_t *idx_out, uint64_t idx_capacity,
                    uint64_t *n_out, int32_t *utf8_verdict_out, uint32_t flags);

@@ -473,8 +473,13 @@ int32_t msj_stage1_ctx(msj_ctx *ctx, const uint8_t *buf, uint64_t len, uint32_t 
     // On UNCLOSED_STRING / UNESCAPED_CHARS the reference returns before it sets
     // n_structural_indexes or the trailer (json_structural_indexer.mojo:151-158).
     if (res.code == MSJ_UNCLOSED_STRING || res.code == MSJ_UNESCAPED_CHARS ||
-        res.code == MSJ_UNEXPECTED_ERROR || res.code == MSJ_CAPACITY)
+        res.code == MSJ_UNEXPECTED_ERROR || res.code == MSJ_CAPACITY) {
+        // The pipeline has brought down what its chunks found before the code was known: the indices, clipped to the
+        // capacity, and no trailer.  Plain staging leaves the caller the same words (tests/test_host_pointer_borders.py)
+        const uint64_t have = res.count < dev_cap ? res.count : dev_cap;
+        if (!piped && have && !hip_ok(hipMemcpy(idx_out, d_idx, have * sizeof(uint32_t), hipMemcpyDeviceToHost))) return MSJ_ERR_HIP;
         return res.code;
+    }
     const uint64_t n = res.count;
     if (!piped && !hip_ok(hipMemcpy(idx_out, d_idx, (n + 3) * sizeof(uint32_t), hipMemcpyDeviceToHost)))
         return MSJ_ERR_HIP;  // (the pipeline has brought the indices and the trailer down already)

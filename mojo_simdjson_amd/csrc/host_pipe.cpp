@@ -194,13 +194,25 @@ static int knob_int(const char *, int dflt, int) { return dflt; }
 bool knob_set(const char *) { return false; }
 #endif
 
+// Chunk and piece sizes: compiled in.  The CPU harness of the pipeline (tests/cpp/host_pipe_sanitize.cpp) builds this file
+// with kilobyte sizes, so that every chunk and piece border is reached by thousands of small runs; the product never
+// defines either name.
+#ifndef MSJ_PIPE_CHUNK_BYTES
+#define MSJ_PIPE_CHUNK_BYTES (16ull << 20)
+#endif
+#ifndef MSJ_PIPE_PIECE_BYTES
+#define MSJ_PIPE_PIECE_BYTES (16ull << 20)
+#endif
+
 struct HostPipe {
     static constexpr int kInSlots = 3, kOutSlots = 2;
     // copy workers and slices per staging copy (defaults measured on the MI355X box's host)
     const int kCopyThreads = knob_int("MSJ_PIPE_THREADS", 8, 1), kParts = knob_int("MSJ_PIPE_PARTS", 4, 1);
     const bool direct_upload = knob_int("MSJ_PIPE_DIRECT_UPLOAD", 0, 0) != 0;
-    static constexpr uint64_t kChunk = 16ull << 20;  // input bytes per chunk (a multiple of the tile)
-    static constexpr uint64_t kPiece = 16ull << 20;  // index bytes per download piece
+    static constexpr uint64_t kChunk = MSJ_PIPE_CHUNK_BYTES;  // input bytes per chunk (a multiple of the tile)
+    static constexpr uint64_t kPiece = MSJ_PIPE_PIECE_BYTES;  // index bytes per download piece
+    static_assert(kChunk > 0 && kChunk % msj::kTileBytes == 0, "a chunk is whole tiles: only the stream's last shard may end inside one");
+    static_assert(kPiece % 256 == 0 && kPiece / sizeof(uint32_t) > 64, "a piece keeps its source's offset inside a 256-byte line (up to 63 words) and still moves words");
     uint8_t *pin_in[kInSlots] = {nullptr, nullptr, nullptr};
     uint8_t *pin_out[kOutSlots] = {nullptr, nullptr};
     msj_carry *h_carries = nullptr;  // pinned: the carry after every chunk
@@ -354,6 +366,21 @@ int32_t host_pipeline(msj_ctx *ctx, const uint8_t *buf, uint64_t len, uint32_t *
         for (auto &c : copying) CopyPool::wait(&c);
         if (out_pinned && !hip_ok(hipStreamSynchronize(P.s_down))) down_rc = MSJ_ERR_HIP;
     });
+    // Whatever leaves this frame from here on (the staging pool's queue or a launch may throw std::bad_alloc, which
+    // msj_stage1_ctx catches) leaves it with the downloader joined -- a joinable std::thread that is destroyed is
+    // std::terminate -- and with nothing of this call left in the queues that still reads or writes caller memory
+    struct JoinDown {
+        std::thread &t;
+        std::atomic<bool> &abort;
+        HostPipe &P;
+        ~JoinDown() {
+            if (!t.joinable()) return;
+            abort.store(true);
+            t.join();
+            (void)hipStreamSynchronize(P.s_k);
+            (void)hipStreamSynchronize(P.s_up);
+        }
+    } join_down{down, abort, P};
 
     // ---- the uploader (this thread): pinned staging, H2D, one shard launch per chunk
     double t_copy = 0, t_wait = 0;
@@ -394,6 +421,9 @@ int32_t host_pipeline(msj_ctx *ctx, const uint8_t *buf, uint64_t len, uint32_t *
     const double t_up = now();
     down.join();
     (void)hipStreamSynchronize(P.s_k);
+    // a chunk whose upload was enqueued and whose launch then was not: no event ties that copy to s_k, and it reads the
+    // caller's registered input (or a staging slot that the next call fills without a wait)
+    if (rc != MSJ_SUCCESS) (void)hipStreamSynchronize(P.s_up);
     if (trace)
         std::fprintf(stderr, "msj host pipeline: %llu chunks, upload loop %.2f ms (slot waits %.2f, staging copies %.2f), "
                              "then %.2f ms until the last index was down\n",
