@@ -1592,7 +1592,8 @@ uint64_t msj_dictionary_extend_workspace_bytes(uint64_t rows, uint64_t dict_capa
  * a stride or capacity of 2^40 records or more: MSJ_CAPACITY; d_out overlapping
  * d_fields, d_result == a select result, d_out_select == d_take_select or d_rows_select; alignment (d_fields, d_out 16-byte,
  * d_take 4-byte, the results 8-byte): MSJ_ERR_BAD_ARGUMENT.  Asynchronous on `stream`, safe on ANY arrays.
- * Out of scope: contains / suffix / regex, predicates on dictionary codes, nested boolean expressions (a second call over
+ * Out of scope: contains / suffix / LIKE (msj_match_strings_device, below: its records under MSJ_PRED_FOUND), regex,
+ * predicates on dictionary codes, nested boolean expressions (a second call over
  * the taken rows is AND).  (Order: msj_sort_rows_device, which takes d_kept as it is.)
  */
 #define MSJ_PRED_FOUND 0u
@@ -2068,6 +2069,90 @@ int32_t msj_rank_rows_device(msj_ctx *ctx,
         const uint32_t *d_rank, uint64_t rank_capacity, const msj_dictionary_order_result *d_order_result,
         msj_field *d_fields, uint64_t capacity,
         msj_rank_rows_result *d_result, msj_select_documents_result *d_select, void *stream);
+
+/*
+ * ---- substring patterns over a byte column (DERIVED) -----------------------------------------------------
+ * msj_match_strings_device answers "which lines' /message contains timeout" on the device: for every row of a byte column
+ * and each of up to 16 patterns, the first place where the pattern matches, as a record that the filter, take, aggregate
+ * and sort calls read.  Over a raw column of the documents themselves the same call is grep over the lines of a window.
+ * Patterns: msj_patterns_create compiles 1 to 16 patterns into an immutable object, like msj_predicates_create and
+ * msj_paths_create: synchronous, the device memory owned by the object, usable on any stream of the context's device;
+ * msj_patterns_destroy(NULL) does nothing.  A pattern is 1 to 4 literal PIECES of 1 to 255 bytes each: `bytes` holds them
+ * back to back, piece_len[j] their lengths (0 behind n_pieces), and the bytes are read during create only.  There is no
+ * text syntax at this level -- no %, *, _ and no escapes: the pieces are explicit, no byte value is special.  Pattern
+ * flags: MSJ_MATCH_AT_START, MSJ_MATCH_AT_END, MSJ_MATCH_NOCASE_ASCII.  A NULL array or `out`, a count outside 1..16, a
+ * pattern without bytes, with 0 or more than 4 pieces, a piece of 0 or more than 255 bytes, a length behind n_pieces, an
+ * unknown pattern flag, a non-zero `flags` of the create call: MSJ_ERR_BAD_ARGUMENT.
+ * Match: a value v (bytes) matches the pieces s_0 .. s_(n-1) iff positions p_0 .. p_(n-1) exist with
+ *   v[p_j : p_j + len(s_j)] == s_j,   p_(j+1) >= p_j + len(s_j) (pieces do not overlap),
+ *   p_0 == 0 under AT_START,   p_(n-1) + len(s_(n-1)) == len(v) under AT_END.
+ * The row's number is the smallest p_0 of any such sequence.  With NOCASE_ASCII the bytes A-Z on both sides compare as a-z;
+ * every other byte, 0x80-0xFF included, compares as itself.  One piece is "contains", with AT_START "starts with", with
+ * AT_END "ends with", with both equality; several pieces are a%b%c of SQL LIKE without _.
+ * Inputs: the (d_offsets[rows + 1], d_valid[rows], d_bytes[bytes_len]) layout exactly as msj_dictionary_device takes it: a
+ * path's strings, a list's strings, a map's keys, raw JSON text.  R = d_n_rows ? *d_n_rows : rows is read on the device.
+ * The row test is checked on the arrays, never believed: a row has a value iff d_valid[k] != 0, and the offsets must ascend
+ * over 0 .. R and end inside bytes_len -- d_offsets[k] <= d_offsets[k + 1] <= bytes_len, as both column calls write them.
+ * On a violation the code is MSJ_ERR_BAD_ARGUMENT in d_result and d_select and nothing else is written
+ * (msj_select_elements_device's rule for rows that do not ascend).  The bytes of a row with d_valid == 0 belong to no row,
+ * and a match never spans two rows.
+ * Outputs: n_patterns columns of records, d_fields[p * capacity + k] for k < R; nothing at or past R is written.  A row
+ * that matches pattern p gets {bits = p_0 as int64, token = 0xFFFFFFFF, type 'l', flags 0, code 0}, the shape
+ * msj_rank_rows_device writes; a row that does not, and a null row, gets the record of a missing value that
+ * msj_take_rows_device writes (code 20, token 0xFFFFFFFF, the rest 0).  d_select is written as a select result over the
+ * records (n_documents = R, n_paths = n_patterns, n_found recounted), so msj_filter_rows_device, msj_take_rows_device,
+ * msj_aggregate_device and msj_sort_rows_device run on them unchanged: MSJ_PRED_FOUND on a column is "contains",
+ * MSJ_PRED_NUM_EQ 0 is "starts with", MSJ_PRED_NOT also passes a row without a value, and the count of a column per group
+ * is the number of matching lines per group.
+ * d_result: code; flags 0; n_rows = R; n_values the rows that are not null; n_matched the matching (pattern, row) pairs;
+ * max_pieces the most pieces of a pattern.  R > rows, R > capacity or R >= 2^31: MSJ_CAPACITY with n_rows = R and nothing
+ * else written.  R == 0 writes zero results (n_paths and max_pieces kept).
+ * Arguments, checked in this order: NULL ctx / patterns / d_result / d_select, patterns of another device; NULL d_offsets
+ * / d_valid with rows > 0, NULL d_fields with capacity > 0; NULL d_bytes with bytes_len > 0: MSJ_ERR_BAD_ARGUMENT.  rows,
+ * capacity or bytes_len of 2^40 or more: MSJ_CAPACITY.  Then d_result == d_select, and alignment -- d_fields 16-byte,
+ * d_offsets, d_n_rows and the two results 8-byte, d_bytes and d_valid any: MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on
+ * any of them.  Asynchronous on `stream`, no host round trip, workspace in the context.  Safe on ANY arrays: d_bytes is read
+ * only inside [0, bytes_len), whatever its alignment; an offset only at or below R; nothing at or past R is touched.  Every
+ * output is a pure function of the input, bit for bit from run to run.
+ * The search is organised by byte, not by row: a block stages a tile of consecutive bytes and 256 bytes behind it in LDS
+ * with aligned 16-byte loads, every lane tests a run of start positions against every pattern, and a hit finds its row by
+ * binary search in the offsets and competes there by minimum.  One pass over the bytes per piece level; a pattern of one
+ * piece has one pass and no state besides its word per row.
+ * Out of scope: _ / ? / character classes / regular expressions; Unicode case folding and normalisation; all occurrences
+ * or a count per row (the first one only); replacement.
+ */
+#define MSJ_MATCH_AT_START 1u       /* msj_pattern.flags: the first piece stands at the value's first byte */
+#define MSJ_MATCH_AT_END 2u         /* the last piece ends at the value's last byte */
+#define MSJ_MATCH_NOCASE_ASCII 4u   /* A-Z compare as a-z, on both sides */
+#define MSJ_MATCH_MAX_PATTERNS 16u
+#define MSJ_MATCH_MAX_PIECES 4u
+#define MSJ_MATCH_MAX_PIECE_BYTES 255u
+typedef struct msj_patterns msj_patterns;
+typedef struct msj_pattern {   /* 32 bytes */
+    const uint8_t *bytes;      /* the pieces back to back */
+    uint32_t n_pieces;         /* 1 .. 4 */
+    uint32_t flags;            /* MSJ_MATCH_* */
+    uint32_t piece_len[4];     /* 1 .. 255 each; 0 behind n_pieces */
+} msj_pattern;
+typedef struct msj_match_strings_result {   /* 48 bytes */
+    int32_t  code;        /* 0; MSJ_CAPACITY; MSJ_ERR_BAD_ARGUMENT: the offsets do not ascend inside bytes_len */
+    uint32_t flags;       /* 0 */
+    uint64_t n_rows;      /* R */
+    uint64_t n_values;    /* rows that are not null */
+    uint64_t n_matched;   /* matching (pattern, row) pairs, summed over the patterns */
+    uint64_t max_pieces;  /* the most pieces of a pattern: the passes over the bytes */
+    uint64_t reserved;
+} msj_match_strings_result;
+int32_t msj_patterns_create(msj_ctx *ctx, const msj_pattern *patterns, uint32_t n_patterns, uint32_t flags, msj_patterns **out);
+void msj_patterns_destroy(msj_patterns *patterns);
+int32_t msj_match_strings_device(msj_ctx *ctx, const msj_patterns *patterns,
+        const uint64_t *d_offsets, const uint8_t *d_valid, uint64_t rows, const uint64_t *d_n_rows,
+        const uint8_t *d_bytes, uint64_t bytes_len,
+        msj_field *d_fields, uint64_t capacity,
+        msj_match_strings_result *d_result, msj_select_documents_result *d_select, void *stream);
+/* Device workspace of one msj_match_strings_device call (the context keeps it): 16 bytes per (pattern, row) -- the word the
+ * places compete on and the chain's cursor -- and the call's state. */
+uint64_t msj_match_strings_workspace_bytes(uint64_t rows, uint32_t n_patterns);
 
 /*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors

@@ -249,6 +249,24 @@ class MsjRankRowsResult(ctypes.Structure):
                 ("n_null", ctypes.c_uint64), ("n_unknown", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
 
 
+class MsjPattern(ctypes.Structure):
+    """``msj_pattern`` (include/msj_stage1.h): the pieces back to back, their number, the flags, their lengths."""
+
+    _fields_ = [("bytes", ctypes.c_void_p), ("n_pieces", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("piece_len", ctypes.c_uint32 * 4)]
+
+
+class MsjMatchStringsResult(ctypes.Structure):
+    """``msj_match_strings_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_values", ctypes.c_uint64),
+                ("n_matched", ctypes.c_uint64), ("max_pieces", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+# msj_pattern.flags; the limits of msj_patterns_create
+MATCH_AT_START, MATCH_AT_END, MATCH_NOCASE_ASCII = 1, 2, 4
+MATCH_FLAGS = {"at_start": MATCH_AT_START, "at_end": MATCH_AT_END, "nocase": MATCH_NOCASE_ASCII}
+MATCH_MAX_PATTERNS, MATCH_MAX_PIECES, MATCH_MAX_PIECE_BYTES = 16, 4, 255
+
 # msj_dictionary_order_device: flags, the rank of an entry without a value, the most rounds; msj_debug_set_order_mode
 ORDER_CONTINUE = 1
 ORDER_NO_RANK = 0xFFFFFFFF
@@ -297,6 +315,7 @@ assert ctypes.sizeof(MsjDocumentVerdict) == 16 and ctypes.sizeof(MsjValidateDocu
 
 assert ctypes.sizeof(MsjDocumentTape) == 32 and ctypes.sizeof(MsjTapeDocumentsResult) == 64
 assert ctypes.sizeof(MsjField) == 16 and ctypes.sizeof(MsjSelectDocumentsResult) == 48
+assert ctypes.sizeof(MsjPattern) == 32 and ctypes.sizeof(MsjMatchStringsResult) == 48
 assert ctypes.sizeof(MsjStringColumnResult) == 48 and ctypes.sizeof(MsjArrayColumnResult) == 48
 assert ctypes.sizeof(MsjObjectEntriesResult) == 48 and ctypes.sizeof(MsjRawColumnResult) == 48
 assert ctypes.sizeof(MsjDictionaryResult) == 48 and ctypes.sizeof(MsjDictionaryExtendResult) == 64
@@ -539,6 +558,16 @@ def load():
     lib.msj_rank_rows_device.restype = ctypes.c_int32
     lib.msj_rank_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_patterns_create.restype = ctypes.c_int32
+    lib.msj_patterns_create.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
+    lib.msj_patterns_destroy.restype = None
+    lib.msj_patterns_destroy.argtypes = [ctypes.c_void_p]
+    lib.msj_match_strings_device.restype = ctypes.c_int32
+    lib.msj_match_strings_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p]
+    lib.msj_match_strings_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_match_strings_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

@@ -2,7 +2,7 @@
 // f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
 // validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
 // array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, dictionary_extend_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip, join_rows_kernel.hip, dictionary_order_kernel.hip (the last three over
-// radix_block.h's one radix pass).  Every launcher and every internal workspace size is declared
+// radix_block.h's one radix pass), match_strings_kernel.hip.  Every launcher and every internal workspace size is declared
 // here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
 // compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
 // (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.
@@ -273,3 +273,12 @@ extern "C" int msj_launch_dictionary_order(const uint64_t *d_dict_offsets, const
 extern "C" int msj_launch_rank_rows(const int32_t *d_codes, uint64_t rows, const uint64_t *d_n_rows, const uint32_t *d_rank, uint64_t rank_capacity,
                                     const msj_dictionary_order_result *d_order_result, msj_field *d_fields, uint64_t capacity,
                                     msj_rank_rows_result *d_result, msj_select_documents_result *d_select, void *stream);
+
+// ---- match_strings_kernel.hip ----
+// d_patterns: the compiled patterns (match_strings_math.h: Patterns) in device memory; n_patterns / max_pieces: what the host
+// knows of them; the (d_offsets, d_valid, d_bytes) layout of a byte column; d_n_rows: the rows on the device, or null for
+// `rows`; d_fields: pattern p's records at p * capacity; the two results are cleared on the stream in front of the kernels
+extern "C" int msj_launch_match_strings(const void *d_patterns, uint32_t n_patterns, uint32_t max_pieces, const uint64_t *d_offsets,
+                                        const uint8_t *d_valid, uint64_t rows, const uint64_t *d_n_rows, const uint8_t *d_bytes, uint64_t bytes_len,
+                                        msj_field *d_fields, uint64_t capacity, msj_match_strings_result *d_result,
+                                        msj_select_documents_result *d_select, void *d_ws, void *stream);

@@ -2,8 +2,9 @@
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
 // window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
 // elements, the arrays inside list rows, an object's members as a map column, a selected value's JSON text as a column, a byte column as codes plus distinct
-// values (in one window, or against a dictionary carried across windows), rows by predicate, strings cast to numbers, count / sum / min / max per group, rows by numeric order, the equi-join of two code columns, a dictionary's values in byte order and the rank records of a code column.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// values (in one window, or against a dictionary carried across windows), rows by predicate, strings cast to numbers, count / sum / min / max per group, rows by numeric order, the equi-join of two code columns, a dictionary's values in byte order, the rank records of a code column and substring patterns over a byte column.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
 // see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
+#include <memory>
 #include <new>
 
 #include "ctx.h"
@@ -12,6 +13,7 @@
 #include "dictionary_order_math.h"
 #include "filter_rows_math.h"
 #include "join_rows_math.h"
+#include "match_strings_math.h"
 #include "select_math.h"
 
 // msj_paths_create's object: the compiled paths (select_math.h: Paths) in device memory, and what the host needs of them
@@ -26,6 +28,14 @@ struct msj_paths {
 struct msj_predicates {
     int device = 0;
     uint32_t max_column = 0;
+    DeviceBuffer blob;
+};
+
+// msj_patterns_create's object: the compiled patterns (match_strings_math.h: Patterns) in device memory, and what the host
+// needs of them
+struct msj_patterns {
+    int device = 0;
+    uint32_t n_patterns = 0, max_pieces = 0;
     DeviceBuffer blob;
 };
 
@@ -772,6 +782,50 @@ int32_t msj_rank_rows_device(msj_ctx *ctx, const int32_t *d_codes, uint64_t rows
         return MSJ_ERR_BAD_ARGUMENT;
     if (!hip_ok(hipSetDevice(ctx->device))) return MSJ_ERR_HIP;
     return launched(msj_launch_rank_rows(d_codes, rows, d_n_rows, d_rank, rank_capacity, d_order_result, d_fields, capacity, d_result, d_select, stream));
+}
+
+int32_t msj_patterns_create(msj_ctx *ctx, const msj_pattern *patterns, uint32_t n_patterns, uint32_t flags, msj_patterns **out) {
+    using namespace msj::mstr;
+    if (!ctx || !out) return MSJ_ERR_BAD_ARGUMENT;
+    const std::unique_ptr<Patterns> host(new (std::nothrow) Patterns);  // (17 KiB: not on the stack; no exception leaves the C ABI)
+    if (!host) return MSJ_MEMALLOC;
+    Patterns &h = *host;
+    if (compile_patterns(patterns, n_patterns, flags, h) != 0) return MSJ_ERR_BAD_ARGUMENT;
+    if (!hip_ok(hipSetDevice(ctx->device))) return MSJ_ERR_HIP;
+    msj_patterns *obj = new (std::nothrow) msj_patterns;
+    if (!obj) return MSJ_MEMALLOC;
+    obj->device = ctx->device, obj->n_patterns = h.n, obj->max_pieces = h.max_pieces;
+    if (!obj->blob.reserve(sizeof h, false)) {
+        delete obj;
+        return MSJ_MEMALLOC;
+    }
+    if (!hip_ok(hipMemcpy(obj->blob.p, &h, sizeof h, hipMemcpyHostToDevice))) {  // synchronous: usable on any stream from here on
+        delete obj;
+        return MSJ_ERR_HIP;
+    }
+    *out = obj;
+    return MSJ_SUCCESS;
+}
+
+void msj_patterns_destroy(msj_patterns *patterns) {
+    if (!patterns) return;
+    (void)hipSetDevice(patterns->device);
+    delete patterns;
+}
+
+int32_t msj_match_strings_device(msj_ctx *ctx, const msj_patterns *patterns, const uint64_t *d_offsets, const uint8_t *d_valid, uint64_t rows,
+                                 const uint64_t *d_n_rows, const uint8_t *d_bytes, uint64_t bytes_len, msj_field *d_fields, uint64_t capacity,
+                                 msj_match_strings_result *d_result, msj_select_documents_result *d_select, void *stream) {
+    if (!ctx || !patterns || !d_result || !d_select || patterns->device != ctx->device) return MSJ_ERR_BAD_ARGUMENT;
+    if ((rows > 0 && (!d_offsets || !d_valid)) || (capacity > 0 && !d_fields)) return MSJ_ERR_BAD_ARGUMENT;
+    if (bytes_len > 0 && !d_bytes) return MSJ_ERR_BAD_ARGUMENT;
+    if (rows >= (1ull << 40) || capacity >= (1ull << 40) || bytes_len >= msj::mstr::kMaxBytes) return MSJ_CAPACITY;
+    if ((const void *)d_result == (const void *)d_select) return MSJ_ERR_BAD_ARGUMENT;
+    if (!aligned(d_fields, 16) || !all_aligned(8, d_offsets, d_n_rows, d_result, d_select)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->match_ws, msj_match_strings_workspace_bytes(rows, patterns->n_patterns));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_match_strings(patterns->blob.p, patterns->n_patterns, patterns->max_pieces, d_offsets, d_valid, rows, d_n_rows,
+                                             d_bytes, bytes_len, d_fields, capacity, d_result, d_select, ctx->match_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

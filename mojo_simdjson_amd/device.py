@@ -64,6 +64,41 @@ class Predicates:
             self.handle = None
 
 
+class Patterns:
+    """Compiled substring patterns (``msj_patterns``), from ``Stage1Device.compile_patterns``."""
+
+    def __init__(self, lib, handle, n_patterns, max_pieces):
+        self.lib, self.handle = lib, handle
+        self.n_patterns, self.max_pieces = n_patterns, max_pieces
+
+    def close(self):
+        if self.handle:
+            self.lib.msj_patterns_destroy(self.handle)
+            self.handle = None
+
+
+def pattern_struct(spec, keep_alive):
+    """One spec of ``Stage1Device.compile_patterns`` -> ``_lib.MsjPattern``; the pieces' bytes are appended to keep_alive"""
+    if isinstance(spec, (str, bytes, bytearray)):
+        spec = ([spec], ())
+    if not isinstance(spec, (tuple, list)) or len(spec) != 2 or isinstance(spec[0], (str, bytes, bytearray)) or isinstance(spec[1], (str, bytes)):
+        raise ValueError(f"a pattern is bytes / str (contains) or (pieces, flags): {spec!r}")
+    pieces = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in spec[0]]
+    names = list(spec[1])
+    if any(n not in _lib.MATCH_FLAGS for n in names):
+        raise ValueError(f"a pattern's flags are of {sorted(_lib.MATCH_FLAGS)}: {spec!r}")
+    if not 1 <= len(pieces) <= _lib.MATCH_MAX_PIECES or any(not 1 <= len(x) <= _lib.MATCH_MAX_PIECE_BYTES for x in pieces):
+        raise ValueError(f"a pattern is 1 to {_lib.MATCH_MAX_PIECES} pieces of 1 to {_lib.MATCH_MAX_PIECE_BYTES} bytes: {spec!r}")
+    flags = 0
+    for n in names:
+        flags |= _lib.MATCH_FLAGS[n]
+    data = b"".join(pieces)
+    buf = ctypes.create_string_buffer(data, len(data))
+    keep_alive.append(buf)
+    lens = (ctypes.c_uint32 * 4)(*[len(x) for x in pieces])
+    return _lib.MsjPattern(ctypes.addressof(buf), len(pieces), flags, lens)
+
+
 _TYPE_NAMES = {"object": 1, "array": 2, "string": 4, "int": 8, "double": 16, "number": 8 | 16, "true": 32, "false": 64, "bool": 32 | 64,
                "null": 128}
 _NUM_OPS = {"==": _lib.PRED_NUM_EQ, "<": _lib.PRED_NUM_LT, "<=": _lib.PRED_NUM_LE, ">": _lib.PRED_NUM_GT, ">=": _lib.PRED_NUM_GE}
@@ -1090,6 +1125,60 @@ class Stage1Device:
         if rc != 0:
             raise RuntimeError(f"msj_rank_rows_device failed: {rc}")
         res = _lib.MsjRankRowsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_fields, d_select
+
+    def compile_patterns(self, specs):
+        """Compile 1 to 16 substring patterns for ``match_strings`` (``msj_patterns_create``).  A spec is ``bytes`` or ``str``
+        (UTF-8) -- the value contains it --, or ``(pieces, flags)``: 1 to 4 literal pieces of 1 to 255 bytes that must stand
+        in the value in this order without overlapping, and a collection of "at_start" (the first piece at the value's first
+        byte), "at_end" (the last piece at its end) and "nocase" (A-Z as a-z).  ``([b"GET ", b".png"], {"at_start",
+        "at_end"})`` is LIKE 'GET %.png'.  No byte is special.  The handle is immutable, usable by any number of calls, and
+        closed with the device.  ValueError for what is no pattern or beyond the limits."""
+        specs = list(specs)
+        if not 1 <= len(specs) <= _lib.MATCH_MAX_PATTERNS:
+            raise ValueError(f"1 to {_lib.MATCH_MAX_PATTERNS} patterns: {len(specs)}")
+        alive = []
+        table = (_lib.MsjPattern * len(specs))(*[pattern_struct(s, alive) for s in specs])
+        h = ctypes.c_void_p()
+        rc = self.lib.msj_patterns_create(self.ctx, table, len(specs), 0, ctypes.byref(h))
+        if rc == -1:
+            raise ValueError(f"no such patterns: {specs}")
+        if rc != 0:
+            raise RuntimeError(f"msj_patterns_create failed: {rc}")
+        patterns = Patterns(self.lib, h, len(specs), max(int(t.n_pieces) for t in table))
+        self._paths.append(patterns)
+        return patterns
+
+    def match_strings(self, patterns, d_offsets, d_valid, d_bytes, rows=None, d_n_rows=None, bytes_len=None, capacity=None, d_fields=None,
+                      d_result=None, d_select=None, sync=True):
+        """Substring patterns over a byte column (``msj_match_strings_device``): per (pattern, row) the first place where
+        the pattern matches as an 'l' record, or the record of a missing value, all on the device.  patterns: from
+        ``compile_patterns``; d_offsets (int64, rows + 1 entries), d_valid (uint8, one per row) and d_bytes (uint8): what
+        ``string_column`` or ``raw_column`` wrote, or any arrays of that shape; rows: default the room of d_offsets;
+        d_n_rows: an int64 device tensor whose first word is the number of rows, read on the device; bytes_len: default the
+        size of d_bytes.  d_fields: int64 (n_patterns, capacity, 2) (default: a new one, capacity = rows).  d_select
+        receives the select result over the records, so ``filter_rows`` (``(p, "found")`` is "contains"), ``take_rows``,
+        ``aggregate`` and ``sort_rows`` run on them.  Offsets that do not ascend inside bytes_len: code -1 in both results and
+        nothing written.  Returns (``MsjMatchStringsResult``, d_fields, d_select) -- blocking for the 48-byte result; with
+        sync=False the device tensor that holds it."""
+        if d_offsets.dtype != torch.int64 or d_offsets.stride(-1) != 1 or d_valid.dtype != torch.uint8 or d_bytes.dtype != torch.uint8:
+            raise ValueError("the offsets are a contiguous int64 tensor, d_valid and d_bytes uint8 tensors")
+        rows = d_offsets.numel() - 1 if rows is None else int(rows)
+        bytes_len = d_bytes.numel() if bytes_len is None else int(bytes_len)
+        if capacity is None:
+            capacity = d_fields.shape[1] if d_fields is not None else rows
+        capacity = int(capacity)
+        if d_fields is None:
+            d_fields = torch.empty((patterns.n_patterns, max(capacity, 1), 2), dtype=torch.int64, device=self.device)
+        if d_fields.dim() != 3 or d_fields.shape[0] != patterns.n_patterns or not d_fields.is_contiguous() or d_fields.shape[1] != max(capacity, 1):
+            raise ValueError("d_fields is a contiguous int64 tensor of shape (n_patterns, capacity, 2)")
+        d_result, d_select = self._result(d_result), self._result(d_select)
+        rc = self.lib.msj_match_strings_device(self.ctx, patterns.handle, _ptr(d_offsets), _ptr(d_valid), rows, _opt(d_n_rows),
+                                               _ptr(d_bytes) if bytes_len else None, bytes_len, _ptr(d_fields), capacity, _ptr(d_result),
+                                               _ptr(d_select), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_match_strings_device failed: {rc}")
+        res = _lib.MsjMatchStringsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
         return res, d_fields, d_select
 
     def set_sort_mode(self, mode=_lib.SORT_MODE_AUTO):

@@ -214,6 +214,61 @@ def _filter(window, d_fields, d_select, rows, specs, any, what, d_list_offsets=N
     return d_keep[:rows].view(torch.bool), d_kept[:int(res.n_kept)], d_kept_select, d_list_out
 
 
+# where's substring operators -> (the pattern's flags besides "nocase", is the operand LIKE text)
+_MATCH_OPS = {"contains": ((), False), "suffix": (("at_end",), False), "like": ((), True)}
+
+
+def _match_pattern(op, operand):
+    """The operand of a ``where`` operator "contains" "suffix" "like" or their "i..." forms -> the pattern spec
+    ``Stage1Device.compile_patterns`` takes, or None when `op` is none of them.  LIKE text: % separates the pieces, a leading
+    or trailing % lifts that end's anchor; _ and an empty piece are refused"""
+    nocase = op.startswith("i") and op[1:] in _MATCH_OPS
+    name = op[1:] if nocase else op
+    if name not in _MATCH_OPS:
+        return None
+    if not isinstance(operand, (str, bytes)):
+        raise ValueError(f"the operand of {op!r} is a str or bytes: {operand!r}")
+    data = operand.encode("utf-8") if isinstance(operand, str) else bytes(operand)
+    flags, like = _MATCH_OPS[name]
+    flags = set(flags) | ({"nocase"} if nocase else set())
+    if not like:
+        if not data:
+            raise ValueError(f"the operand of {op!r} is not empty")
+        return ([data], flags)
+    if b"_" in data:
+        raise ValueError(f"'like' has % only, no _: {operand!r}")
+    pieces = data.split(b"%")
+    if len(pieces) == 1 or pieces[0]:
+        flags.add("at_start")
+    if len(pieces) == 1 or pieces[-1]:
+        flags.add("at_end")
+    pieces = pieces[1 if not pieces[0] and len(pieces) > 1 else 0:]
+    pieces = pieces[:-1] if pieces and not pieces[-1] else pieces
+    if not pieces or any(not x for x in pieces):
+        raise ValueError(f"'like' has no empty piece: {operand!r}")
+    return (pieces, flags)
+
+
+def _match_specs(specs, n_columns):
+    """Predicate specs by column number with the substring operators rewritten: such a spec becomes (column, "found") on a
+    new column behind the n_columns there are, which is to hold the match records of its pattern.
+    -> (specs, {column: [(new column, pattern spec), ...]})"""
+    wanted = {}
+    count = [n_columns]
+
+    def one(spec):
+        if len(spec) == 2 and spec[0] == "not":
+            return ("not", one(spec[1]))
+        pattern = _match_pattern(spec[1], spec[2]) if len(spec) == 3 and isinstance(spec[1], str) else None
+        if pattern is None:
+            return spec
+        wanted.setdefault(spec[0], []).append((count[0], pattern))
+        count[0] += 1
+        return (count[0] - 1, "found")
+
+    return [one(s) for s in specs], wanted
+
+
 _EPOCH = datetime.datetime(1970, 1, 1, tzinfo=datetime.timezone.utc)
 
 
@@ -691,6 +746,28 @@ class _Records:
         w, fields, rows, p, what = self._at(path_or_index)
         return _raw_column(w, fields[p], self.d_select, rows, compact, bytes_capacity, what)
 
+    def match(self, path_or_index, patterns, raw=False, compact=False):
+        """Substring patterns over the string values of one path ON THE DEVICE (``msj_match_strings_device`` over
+        ``strings(path)``) -> (fields int64[n_patterns, rows, 2], the uint8[48] ``msj_select_documents_result`` that goes with
+        them): per (pattern, row) the 'l' record of the first place where the pattern matches the unescaped value, or the
+        record of a missing value -- no match, no string, a missing key, a document with a verdict code.  patterns: 1 to 16
+        specs as ``Stage1Device.compile_patterns`` takes them: ``b"timeout"`` (contains), ``([b"GET ", b".png"], {"at_start",
+        "at_end", "nocase"})``.  raw=True: over ``raw(path, compact)``, the values' JSON text, instead: ``win.match("",
+        [b"timeout"], raw=True)`` is grep over the window's lines.  ``filter_rows``, ``take_rows``, ``aggregate`` and
+        ``sort_rows`` take the records as they take a select call's.  Only 48-byte results come to the host."""
+        w, _, rows, _, what = self._at(path_or_index)
+        d_off, d_bytes, valid = self.raw(path_or_index, compact) if raw else self.strings(path_or_index)
+        compiled = w.dev.compile_patterns(patterns)
+        try:
+            d_res, d_fields, d_sel = w.dev.match_strings(compiled, d_off, valid.view(torch.uint8), d_bytes, rows=rows, sync=False)
+        finally:  # (the patterns live for the call, as ``_filter``'s predicates do: freeing their device memory waits for the
+            compiled.close()  # device, so the kernels that were just enqueued have read them)
+            w.dev._paths.remove(compiled)
+        code = _code(d_res)
+        if code != 0:
+            raise DocumentStreamError(code, f"window at {w.base}: {what} could not be matched")
+        return d_fields[:, :rows], d_sel
+
     def elements(self, path_or_index, elements_capacity=None):
         """The arrays of one path as a list column -- ``tags``, ``items[*].tags`` -- ON THE DEVICE
         (``msj_array_elements_device``) -> ``ListColumn`` with one row per row of these records: offsets int64[rows + 1], one
@@ -746,8 +823,17 @@ class _Records:
         w, fields, index = self._window, self._records, self.paths.index
         rows = fields.shape[1]
         specs, seen = _column_specs(specs, index), fields
-        if cast:
-            specs, seen = _cast_for_filter(w, fields, self.d_select, rows, specs, cast, index, self._rows_are)
+        specs, wanted = _match_specs(specs, fields.shape[0])
+        if wanted:  # a column's strings, one call with all of its patterns, the match records as further columns
+            found = {}
+            for c, news in wanted.items():
+                records = self.match(c, [pattern for _, pattern in news])[0]
+                found.update({new: records[j:j + 1] for j, (new, _) in enumerate(news)})
+            seen = torch.cat([fields[:, :rows]] + [found[new] for new in sorted(found)])
+        if cast or wanted:
+            specs, seen = _cast_for_filter(w, seen, self.d_select, rows, specs, cast or {}, index, self._rows_are)
+            if wanted and seen.shape[0] > _lib.MAX_COLUMNS:
+                raise ValueError(f"predicates on more than {_lib.MAX_COLUMNS} columns, the substring operators' included")
         return _filter(w, seen, self.d_select, rows, specs, any, self._rows_are, d_list_offsets)
 
     def _taken(self, d_take, d_take_select, n_take):
@@ -1277,7 +1363,11 @@ class Window(_Records):
         cast: ``{"/ts": ("timestamp", "ms"), "/price": "number"}`` makes the predicates see those columns cast
         (``msj_cast_strings_device``), so that ``[("/ts", ">=", t0), ("/ts", "<", t1)]`` is two exact int64 compares; a
         ``datetime.datetime`` operand -- aware, or naive, which means UTC -- becomes the column's unit by integer arithmetic
-        (``datetime_units``).  The records the selection carries stay the originals."""
+        (``datetime_units``).  The records the selection carries stay the originals.
+        Substring operators on a string column (``msj_match_strings_device`` over its unescaped strings, then "found" on
+        the match records): ``("/message", "contains", "timeout")``, ``("/path", "suffix", ".png")``, ``("/line", "like",
+        "GET %.png")`` -- % separates literal pieces, a leading or trailing % lifts the anchor, there is no _ --, and
+        "icontains" "isuffix" "ilike", which compare A-Z as a-z.  Under ("not", ...) a document without the string passes."""
         keep, kept, d_kept_select, _ = self._filtered(specs, any, cast)
         fields, d_fsel = self._taken(kept, d_kept_select, kept.shape[0])
         return RowSelection(self, keep, kept, fields, d_fsel)
