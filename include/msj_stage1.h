@@ -1794,8 +1794,9 @@ int32_t msj_debug_set_cast_fetch(msj_ctx *ctx, uint32_t fetch);
  * Two paths, chosen on the device from G: up to the context's limit (256 groups) a block sums its rows in LDS and adds what
  * it touched to the group's words once; above it every lane adds to the group's words directly.  Both give the same bytes.
  * msj_debug_set_aggregate_limits moves the limit (0: never LDS; at most 256) so that tests run both on small inputs.
- * Out of scope: mean and variance (the caller divides); grouping by a numeric key or a time bucket; more than one key;
- * argmin / argmax rows; sums across windows (above); sorting the groups.
+ * Out of scope: mean and variance (the caller divides); making the codes -- a numeric key, a time bucket and more than one
+ * key are msj_bucket_rows_device and msj_group_keys_device in front of a dictionary call (below), the groups in key order
+ * msj_dictionary_order_device over that dictionary --; argmin / argmax rows; sums across windows (above).
  */
 #define MSJ_AGG_INT_OVERFLOW 1u   /* msj_aggregate.flags: every value an 'l', the exact sum outside int64: sum_type 'd' */
 #define MSJ_AGG_INFINITE 2u       /* the sum lies beyond DBL_MAX: sum_bits is +-infinity */
@@ -2153,6 +2154,108 @@ int32_t msj_match_strings_device(msj_ctx *ctx, const msj_patterns *patterns,
 /* Device workspace of one msj_match_strings_device call (the context keeps it): 16 bytes per (pattern, row) -- the word the
  * places compete on and the chain's cursor -- and the call's state. */
 uint64_t msj_match_strings_workspace_bytes(uint64_t rows, uint32_t n_patterns);
+
+/*
+ * ---- rows grouped by numbers, time buckets and several keys at once (DERIVED) -------------------------
+ * "Errors per minute per status": msj_aggregate_device groups by any int32 codes, and msj_dictionary_device gives dense codes
+ * to any (offsets, valid, bytes) column.  The two calls here are the step in front of them: msj_bucket_rows_device floors a
+ * column of number records to multiples of a width (/ts cast to milliseconds, width 60 000: the minute), and
+ * msj_group_keys_device lays 1 to 8 columns -- number records, int32 codes -- out as ONE canonical, order-preserving,
+ * fixed-width byte key per row, in exactly the layout the dictionary calls read.  Codes, first rows, distinct keys, counts,
+ * the order of the groups and the aggregate then come from the calls that exist, unchanged.
+ *
+ * msj_bucket_rows_device.  R = d_rows_select->n_documents is read on the device.  The output record of row k < R:
+ *   the input has a code       the input record, unchanged
+ *   a number value             msj_aggregate_device's rule: code == 0, type 'l' or 'd', MSJ_FIELD_NO_BITS not set, a 'd' finite.
+ *                              Let f be the value of an 'l' and floor(value) of a 'd'.  The result is
+ *                              s = origin + floor((f - origin) / width) * width over the integers -- which is the same
+ *                              expression over the reals, width and origin being integers: -0.5 with width 1 is -1, 1969-12-31
+ *                              T23:59:59.999Z with width 60 000 is -60 000, a floor and not a truncation.  The record is type
+ *                              'l', bits = s, token = the input's, flags 0, code 0.  A 'd' whose floor lies outside int64, and
+ *                              s < INT64_MIN (s <= f: the other end cannot be left), give code 9 (NUMBER_ERROR), token
+ *                              0xFFFFFFFF, everything else 0, counted in n_range
+ *   code 0, 'l' / 'd' without usable bits (MSJ_FIELD_NO_BITS, a NaN, an infinity)     code 9 likewise, counted in n_skipped
+ *   anything else with code 0  code 17 (INCORRECT_TYPE), token 0xFFFFFFFF, everything else 0, counted in n_other
+ * The remainder r = (f - origin) mod width in [0, width) comes from an unsigned 64-bit subtraction and one %, in two cases (f >=
+ * origin; f < origin), and s = f - r: no 128-bit word, no multiply that wraps, exact for every int64 f and origin and every
+ * width up to 2^63 - 1.
+ * d_result: code; flags 0; n_rows = R; n_bucketed the records written as buckets; n_range; n_skipped; n_other.  The codes,
+ * the capacity rule (R > capacity or R >= 2^31: MSJ_CAPACITY with n_rows = R, nothing else written), d_rows_select->code != 0,
+ * R == 0, d_out_select (n_found = n_bucketed, n_no_bits recounted over what was written) and d_out == d_rows exactly, a bucket
+ * in place, are msj_cast_strings_device's.  Every output is a pure function of the input.
+ * Arguments, checked in this order: NULL ctx / d_result / d_rows_select; NULL d_rows / d_out with capacity > 0; width < 1 or a
+ * non-zero `flags`: MSJ_ERR_BAD_ARGUMENT.  A capacity of 2^40 records or more: MSJ_CAPACITY.  Then d_out overlapping d_rows in
+ * any way but d_out == d_rows, d_result == a select result, d_out_select == d_rows_select, and alignment -- d_rows, d_out
+ * 16-byte; the result and select results 8-byte: MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of them.  Asynchronous on
+ * `stream`, no host round trip, workspace in the context.  Safe on ANY records: nothing at or past R or capacity is touched.
+ *
+ * msj_group_keys_device.  `parts` is a HOST array of n_parts columns, every one with room for `stride` rows:
+ *   MSJ_KEY_NUMBER  d_column: msj_field[stride]; 11 key bytes.  The tag byte 0x00, then msj_sort_rows_device's ascending key of
+ *                   the value, big-endian: hi in 8 bytes, lo in 2.  So equal reals have equal bytes (3 and 3.0; -0.0 and 0) and
+ *                   the bytes' order is the order of the reals, an int64 against a double exactly (9007199254740992.0 <
+ *                   9007199254740993 < 9007199254740994.0).  A record that is no number value (the rule above): the tag 0x01
+ *                   and ten zero bytes
+ *   MSJ_KEY_CODE    d_column: int32_t[stride]; 5 key bytes.  The tag byte 0x00, then the code big-endian in 4 bytes.  A code
+ *                   below 0: the tag 0x01 and four zero bytes
+ * W, the key's width, is the sum of the parts' widths, at most 88.  R = d_rows_select->n_documents is read on the device.
+ * d_offsets[k] = k * W for k <= R; d_bytes[k * W, (k + 1) * W) holds row k's parts in part order; d_valid[k] = 1 iff every
+ * null part of row k carries MSJ_KEY_NULL_IS_GROUP.  By default a row with a null part has no key -- code -1 from the
+ * dictionary, "ungrouped" in the aggregate; with the flag "no value" is a group of its own, and it sorts last.  Its bytes are
+ * written either way.  Nothing at or past R (valid), R + 1 (offsets) or R * W (bytes) is written.  memcmp of two keys is the
+ * lexicographic order of their parts, and two keys are equal iff every part is the same real, the same code or null in both.
+ * Every output is a pure function of the input.
+ * d_result: code; flags 0; n_rows = R; n_keys the rows with d_valid = 1; n_null_rows the rows with any null part; key_width =
+ * W (in every case: it is a function of the arguments); bytes_len = R * W.  d_rows_select->code != 0: a zero result with that
+ * code, nothing else written.  R > stride, R > capacity, R >= 2^31 or R * W > bytes_capacity: MSJ_CAPACITY with n_rows = R,
+ * nothing else written.  R == 0 writes d_offsets[0] = 0 (where d_offsets is given) and a result of zeros and key_width.
+ * Arguments, checked in this order: NULL ctx / d_result / d_rows_select / parts; n_parts outside 1..8; an unknown kind or
+ * flag; a NULL d_column with stride > 0; NULL d_offsets / d_valid / d_bytes with capacity > 0; d_result == d_rows_select;
+ * then alignment -- records and d_bytes 16-byte, codes 4-byte, d_offsets, the result and the select result 8-byte:
+ * MSJ_ERR_BAD_ARGUMENT.  Nothing is launched on any of them.  Asynchronous on `stream`, no host round trip, workspace in the
+ * context (the counters).  Safe on ANY records and codes: one is read only at k < R <= stride.
+ * A block takes 256 consecutive rows: every lane builds its row's W bytes in LDS (at most 22 KiB), then the block writes its
+ * 256 * W contiguous bytes -- the first a multiple of 16 -- with aligned 16-byte stores, the last block its tail byte by byte.
+ * Out of scope: calendar months and time zones (a bucket is a multiple of a fixed width); a dense path without a hash for
+ * small bucket ranges; more than 8 parts; keys on raw JSON text (msj_raw_column_device's column is a dictionary input as it is).
+ */
+#define MSJ_KEY_NUMBER 1u          /* msj_key_part.kind: d_column is msj_field[stride]; 11 key bytes */
+#define MSJ_KEY_CODE   2u          /* d_column is int32_t[stride]; 5 key bytes */
+#define MSJ_KEY_NULL_IS_GROUP 1u   /* msj_key_part.flags: a null part does not take the row's key away */
+#define MSJ_KEY_MAX_PARTS 8u
+typedef struct msj_key_part {   /* 16 bytes; a host array */
+    const void *d_column;
+    uint32_t kind;    /* MSJ_KEY_NUMBER, MSJ_KEY_CODE */
+    uint32_t flags;   /* MSJ_KEY_NULL_IS_GROUP */
+} msj_key_part;
+typedef struct msj_bucket_rows_result {   /* 48 bytes */
+    int32_t  code;        /* 0; MSJ_CAPACITY (R > capacity or R >= 2^31: n_rows = R, nothing else written); or d_rows_select->code */
+    uint32_t flags;       /* 0 */
+    uint64_t n_rows;      /* R */
+    uint64_t n_bucketed;  /* records written as buckets: type 'l', code 0 */
+    uint64_t n_range;     /* number values whose floor or bucket lies outside int64 */
+    uint64_t n_skipped;   /* 'l' / 'd' records without usable bits (MSJ_FIELD_NO_BITS, NaN, infinity) */
+    uint64_t n_other;     /* rows with code 0 that are no number */
+} msj_bucket_rows_result;
+typedef struct msj_group_keys_result {   /* 48 bytes */
+    int32_t  code;         /* 0; MSJ_CAPACITY; or d_rows_select->code */
+    uint32_t flags;        /* 0 */
+    uint64_t n_rows;       /* R */
+    uint64_t n_keys;       /* rows with d_valid = 1 */
+    uint64_t n_null_rows;  /* rows with at least one null part */
+    uint64_t key_width;    /* W */
+    uint64_t bytes_len;    /* R * W */
+} msj_group_keys_result;
+int32_t msj_bucket_rows_device(msj_ctx *ctx, const msj_field *d_rows, const msj_select_documents_result *d_rows_select,
+        int64_t width, int64_t origin, uint32_t flags,
+        msj_field *d_out, uint64_t capacity,
+        msj_bucket_rows_result *d_result, msj_select_documents_result *d_out_select, void *stream);
+int32_t msj_group_keys_device(msj_ctx *ctx, const msj_key_part *parts, uint32_t n_parts, uint64_t stride,
+        const msj_select_documents_result *d_rows_select,
+        uint64_t *d_offsets, uint8_t *d_valid, uint8_t *d_bytes, uint64_t capacity, uint64_t bytes_capacity,
+        msj_group_keys_result *d_result, void *stream);
+/* Device workspace of one call of either (the context keeps it): the counters. */
+uint64_t msj_bucket_rows_workspace_bytes(uint64_t capacity);
+uint64_t msj_group_keys_workspace_bytes(uint64_t capacity);
 
 /*
  * Device memory for hosts that have no HIP binding of their own (a Mojo DLHandle, plain C, the C++ mirrors

@@ -262,6 +262,33 @@ class MsjMatchStringsResult(ctypes.Structure):
                 ("n_matched", ctypes.c_uint64), ("max_pieces", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
 
 
+class MsjKeyPart(ctypes.Structure):
+    """``msj_key_part`` (include/msj_stage1.h): one column of a group key -- a host array."""
+
+    _fields_ = [("d_column", ctypes.c_void_p), ("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class MsjBucketRowsResult(ctypes.Structure):
+    """``msj_bucket_rows_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_bucketed", ctypes.c_uint64),
+                ("n_range", ctypes.c_uint64), ("n_skipped", ctypes.c_uint64), ("n_other", ctypes.c_uint64)]
+
+
+class MsjGroupKeysResult(ctypes.Structure):
+    """``msj_group_keys_result`` (include/msj_stage1.h)."""
+
+    _fields_ = [("code", ctypes.c_int32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_uint64), ("n_keys", ctypes.c_uint64),
+                ("n_null_rows", ctypes.c_uint64), ("key_width", ctypes.c_uint64), ("bytes_len", ctypes.c_uint64)]
+
+
+# msj_key_part.kind and .flags, the bytes of a part by kind, the most parts and the widest key
+KEY_NUMBER, KEY_CODE = 1, 2
+KEY_KINDS = {"number": KEY_NUMBER, "code": KEY_CODE}
+KEY_NULL_IS_GROUP = 1
+KEY_PART_BYTES = {KEY_NUMBER: 11, KEY_CODE: 5}
+KEY_MAX_PARTS, KEY_MAX_WIDTH = 8, 88
+
 # msj_pattern.flags; the limits of msj_patterns_create
 MATCH_AT_START, MATCH_AT_END, MATCH_NOCASE_ASCII = 1, 2, 4
 MATCH_FLAGS = {"at_start": MATCH_AT_START, "at_end": MATCH_AT_END, "nocase": MATCH_NOCASE_ASCII}
@@ -316,6 +343,7 @@ assert ctypes.sizeof(MsjDocumentVerdict) == 16 and ctypes.sizeof(MsjValidateDocu
 assert ctypes.sizeof(MsjDocumentTape) == 32 and ctypes.sizeof(MsjTapeDocumentsResult) == 64
 assert ctypes.sizeof(MsjField) == 16 and ctypes.sizeof(MsjSelectDocumentsResult) == 48
 assert ctypes.sizeof(MsjPattern) == 32 and ctypes.sizeof(MsjMatchStringsResult) == 48
+assert ctypes.sizeof(MsjKeyPart) == 16 and ctypes.sizeof(MsjBucketRowsResult) == 48 and ctypes.sizeof(MsjGroupKeysResult) == 48
 assert ctypes.sizeof(MsjStringColumnResult) == 48 and ctypes.sizeof(MsjArrayColumnResult) == 48
 assert ctypes.sizeof(MsjObjectEntriesResult) == 48 and ctypes.sizeof(MsjRawColumnResult) == 48
 assert ctypes.sizeof(MsjDictionaryResult) == 48 and ctypes.sizeof(MsjDictionaryExtendResult) == 64
@@ -568,6 +596,16 @@ def load():
                                              ctypes.c_void_p]
     lib.msj_match_strings_workspace_bytes.restype = ctypes.c_uint64
     lib.msj_match_strings_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+    lib.msj_bucket_rows_device.restype = ctypes.c_int32
+    lib.msj_bucket_rows_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_bucket_rows_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_bucket_rows_workspace_bytes.argtypes = [ctypes.c_uint64]
+    lib.msj_group_keys_device.restype = ctypes.c_int32
+    lib.msj_group_keys_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    lib.msj_group_keys_workspace_bytes.restype = ctypes.c_uint64
+    lib.msj_group_keys_workspace_bytes.argtypes = [ctypes.c_uint64]
     lib.msj_carry_fetch.restype = ctypes.c_int32
     lib.msj_carry_fetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MsjCarry), ctypes.c_void_p]
     lib.msj_debug_set_wait_ticks.restype = ctypes.c_int32

@@ -127,6 +127,8 @@ struct msj_ctx {
     DeviceBuffer join_ws;         // msj_join_rows_device: the counters, count / start per key, two buffers of (key, row) per right row, a run and an offset per left row
     DeviceBuffer order_ws;        // msj_dictionary_order_device: the counters, and per entry the tied entries' keys, entries and places twice over
     DeviceBuffer match_ws;        // msj_match_strings_device: the state, per (pattern, row) the word the places compete on and the cursor
+    DeviceBuffer bucket_ws;       // msj_bucket_rows_device: the counters
+    DeviceBuffer gkeys_ws;        // msj_group_keys_device: the counters
     uint32_t order_mode = 0;      // msj_debug_set_order_mode: 0 the path by capacity, 1 always the grid path, 2 the one-workgroup path wherever it fits
     uint32_t sort_mode = 0;       // msj_debug_set_sort_mode: 0 chosen on the device, 1 always the full sort, 2 always the selection
 };

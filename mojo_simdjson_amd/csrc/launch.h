@@ -2,7 +2,7 @@
 // f2 / f4 of SURVEY.md section 8), documents_kernel.hip, numbers_kernel.hip, validate_kernel.hip,
 // validate_docs_kernel.hip, tape_kernel.hip, tape_docs_kernel.hip, select_kernel.hip, string_column_kernel.hip,
 // array_column_kernel.hip, select_elements_kernel.hip, array_elements_kernel.hip, object_entries_kernel.hip, raw_column_kernel.hip, dictionary_kernel.hip, dictionary_extend_kernel.hip, filter_rows_kernel.hip, cast_strings_kernel.hip, aggregate_kernel.hip, sort_rows_kernel.hip, join_rows_kernel.hip, dictionary_order_kernel.hip (the last three over
-// radix_block.h's one radix pass), match_strings_kernel.hip.  Every launcher and every internal workspace size is declared
+// radix_block.h's one radix pass), match_strings_kernel.hip, group_keys_kernel.hip.  Every launcher and every internal workspace size is declared
 // here and nowhere else; the file that defines one and the file that calls it both include this header, so the compiler
 // compares the two signatures (C linkage alone would not).  The calls over a window take what they read as named views
 // (msj_token_view, msj_split_view, msj_number_view): two arrays of one type cannot change places on the way.
@@ -282,3 +282,13 @@ extern "C" int msj_launch_match_strings(const void *d_patterns, uint32_t n_patte
                                         const uint8_t *d_valid, uint64_t rows, const uint64_t *d_n_rows, const uint8_t *d_bytes, uint64_t bytes_len,
                                         msj_field *d_fields, uint64_t capacity, msj_match_strings_result *d_result,
                                         msj_select_documents_result *d_select, void *d_ws, void *stream);
+
+// ---- group_keys_kernel.hip ----
+// d_rows / d_rows_select: any records with their select result; width >= 1; d_out == d_rows: in place
+extern "C" int msj_launch_bucket_rows(const msj_field *d_rows, const msj_select_documents_result *d_rows_select, int64_t width, int64_t origin,
+                                      msj_field *d_out, uint64_t capacity, msj_bucket_rows_result *d_result,
+                                      msj_select_documents_result *d_out_select, void *d_ws, void *stream);
+// parts: the HOST array, kinds and flags checked by the caller (group_keys_math.h: bad_part); `stride` the room of every column
+extern "C" int msj_launch_group_keys(const msj_key_part *parts, uint32_t n_parts, uint64_t stride, const msj_select_documents_result *d_rows_select,
+                                     uint64_t *d_offsets, uint8_t *d_valid, uint8_t *d_bytes, uint64_t capacity, uint64_t bytes_capacity,
+                                     msj_group_keys_result *d_result, void *d_ws, void *stream);

@@ -2,7 +2,7 @@
 // the fused prep, segments, documents, number values, the verdict and the tape (one document, or every document of a
 // window), fields by path, a path's strings as a column and its arrays as a list column, fields by path inside list
 // elements, the arrays inside list rows, an object's members as a map column, a selected value's JSON text as a column, a byte column as codes plus distinct
-// values (in one window, or against a dictionary carried across windows), rows by predicate, strings cast to numbers, count / sum / min / max per group, rows by numeric order, the equi-join of two code columns, a dictionary's values in byte order, the rank records of a code column and substring patterns over a byte column.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
+// values (in one window, or against a dictionary carried across windows), rows by predicate, strings cast to numbers, count / sum / min / max per group, rows by numeric order, the equi-join of two code columns, a dictionary's values in byte order, the rank records of a code column, substring patterns over a byte column, numbers floored to buckets and byte keys from several columns.  Every call is the same few steps: check the arguments (the order of the checks is part of the ABI: callers
 // see which error wins; tests/test_check_order.py), select the device, grow the call's workspace, launch.
 #include <memory>
 #include <new>
@@ -12,6 +12,7 @@
 #include "cast_strings_math.h"
 #include "dictionary_order_math.h"
 #include "filter_rows_math.h"
+#include "group_keys_math.h"
 #include "join_rows_math.h"
 #include "match_strings_math.h"
 #include "select_math.h"
@@ -826,6 +827,46 @@ int32_t msj_match_strings_device(msj_ctx *ctx, const msj_patterns *patterns, con
     if (rc != MSJ_SUCCESS) return rc;
     return launched(msj_launch_match_strings(patterns->blob.p, patterns->n_patterns, patterns->max_pieces, d_offsets, d_valid, rows, d_n_rows,
                                              d_bytes, bytes_len, d_fields, capacity, d_result, d_select, ctx->match_ws.p, stream));
+}
+
+int32_t msj_bucket_rows_device(msj_ctx *ctx, const msj_field *d_rows, const msj_select_documents_result *d_rows_select, int64_t width, int64_t origin,
+                               uint32_t flags, msj_field *d_out, uint64_t capacity, msj_bucket_rows_result *d_result,
+                               msj_select_documents_result *d_out_select, void *stream) {
+    if (!ctx || !d_result || !d_rows_select) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && (!d_rows || !d_out)) return MSJ_ERR_BAD_ARGUMENT;
+    if (msj::gkeys::bad_bucket(width, flags)) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity >= (1ull << 40)) return MSJ_CAPACITY;  // (the extent below: no overflow)
+    if (d_out && d_rows && d_out != d_rows) {           // in place, or no byte shared
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_rows), b = reinterpret_cast<uintptr_t>(d_out);
+        if (a < b + 16 * capacity && b < a + 16 * capacity) return MSJ_ERR_BAD_ARGUMENT;
+    }
+    if ((const void *)d_result == (const void *)d_rows_select || (const void *)d_result == (const void *)d_out_select ||
+        d_out_select == d_rows_select)
+        return MSJ_ERR_BAD_ARGUMENT;
+    if (!all_aligned(16, d_rows, d_out) || !all_aligned(8, d_rows_select, d_result, d_out_select)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->bucket_ws, msj_bucket_rows_workspace_bytes(capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_bucket_rows(d_rows, d_rows_select, width, origin, d_out, capacity, d_result, d_out_select, ctx->bucket_ws.p, stream));
+}
+
+int32_t msj_group_keys_device(msj_ctx *ctx, const msj_key_part *parts, uint32_t n_parts, uint64_t stride,
+                              const msj_select_documents_result *d_rows_select, uint64_t *d_offsets, uint8_t *d_valid, uint8_t *d_bytes,
+                              uint64_t capacity, uint64_t bytes_capacity, msj_group_keys_result *d_result, void *stream) {
+    if (!ctx || !d_result || !d_rows_select || !parts) return MSJ_ERR_BAD_ARGUMENT;
+    if (n_parts == 0 || n_parts > msj::gkeys::kMaxParts) return MSJ_ERR_BAD_ARGUMENT;
+    for (uint32_t j = 0; j < n_parts; j++)
+        if (msj::gkeys::bad_part(parts[j].kind, parts[j].flags)) return MSJ_ERR_BAD_ARGUMENT;
+    for (uint32_t j = 0; j < n_parts; j++)
+        if (stride > 0 && !parts[j].d_column) return MSJ_ERR_BAD_ARGUMENT;
+    if (capacity > 0 && (!d_offsets || !d_valid || !d_bytes)) return MSJ_ERR_BAD_ARGUMENT;
+    if ((const void *)d_result == (const void *)d_rows_select) return MSJ_ERR_BAD_ARGUMENT;
+    for (uint32_t j = 0; j < n_parts; j++)
+        if (!aligned(parts[j].d_column, parts[j].kind == MSJ_KEY_NUMBER ? 16 : 4)) return MSJ_ERR_BAD_ARGUMENT;
+    if (!aligned(d_bytes, 16) || !all_aligned(8, d_offsets, d_rows_select, d_result)) return MSJ_ERR_BAD_ARGUMENT;
+    const int32_t rc = begin_call(ctx, ctx->gkeys_ws, msj_group_keys_workspace_bytes(capacity));
+    if (rc != MSJ_SUCCESS) return rc;
+    return launched(msj_launch_group_keys(parts, n_parts, stride, d_rows_select, d_offsets, d_valid, d_bytes, capacity, bytes_capacity, d_result,
+                                          ctx->gkeys_ws.p, stream));
 }
 
 int32_t msj_debug_set_span_limits(msj_ctx *ctx, uint32_t lds_limit_bytes, uint32_t fix_capacity) {

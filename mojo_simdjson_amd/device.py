@@ -918,6 +918,75 @@ class Stage1Device:
         res = _lib.MsjCastStringsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
         return res, d_out, d_out_select
 
+    def bucket_rows(self, d_rows, d_rows_select, width, origin=0, capacity=None, d_out=None, d_result=None, d_out_select=None, sync=True):
+        """Numbers floored to multiples of a width (``msj_bucket_rows_device``), all on the device: the record of a number
+        value becomes the int64 ``origin + floor((floor(v) - origin) / width) * width``, exactly -- a timestamp cast to
+        milliseconds with width 60 000 is its minute, also before 1970.  d_rows: int64 of shape (rows, 2), any ``msj_field``
+        records -- a path of ``select_documents``, cast strings, taken rows; d_rows_select: the device
+        ``msj_select_documents_result`` that counts them, read on the device.  width: an int of at least 1; origin: an int.
+        A record with a code is copied; a number whose bucket leaves int64 and a number without bits become code 9, anything
+        else code 17.  capacity: default the rows of d_rows.  d_out: int64 tensor of shape (capacity, 2) (default: a new one);
+        d_rows itself buckets in place.  d_out_select: uint8[48] that receives the ``msj_select_documents_result`` of d_out
+        (default: a new one).  Returns (``MsjBucketRowsResult``, d_out, d_out_select) -- blocking for the 48-byte result;
+        with sync=False the device tensor that holds it, nothing waited for."""
+        _check_records(d_rows, "the records")
+        width, origin = int(width), int(origin)
+        if width < 1 or width >= 1 << 63 or not -(1 << 63) <= origin < 1 << 63:
+            raise ValueError(f"width lies in 1..2^63 - 1 and origin in int64: {width!r}, {origin!r}")
+        capacity = d_rows.shape[0] if capacity is None else int(capacity)
+        if d_out is None:
+            d_out = torch.empty((max(capacity, 1), 2), dtype=torch.int64, device=self.device)
+        _check_records(d_out, "the output records")
+        d_result, d_out_select = self._result(d_result), self._result(d_out_select)
+        rc = self.lib.msj_bucket_rows_device(self.ctx, _ptr(d_rows), _ptr(d_rows_select), width, origin, 0, _ptr(d_out), capacity,
+                                             _ptr(d_result), _ptr(d_out_select), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_bucket_rows_device failed: {rc}")
+        res = _lib.MsjBucketRowsResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_out, d_out_select
+
+    def group_keys(self, parts, d_rows_select, capacity=None, d_offsets=None, d_valid=None, d_bytes=None, d_result=None, sync=True):
+        """One fixed-width, order-preserving byte key per row from 1 to 8 columns (``msj_group_keys_device``), all on the
+        device, in the (d_offsets, d_valid, d_bytes) layout ``dictionary`` and ``dictionary_extend`` take: their codes are the
+        rows' groups.  parts: a list of tensors or of (tensor, null_is_group) pairs -- int64 of shape (rows, 2) is a NUMBER
+        part (``msj_field`` records: 11 key bytes; equal reals have equal bytes and the bytes order as the reals do), int32
+        of `rows` entries a CODE part (5 key bytes; a code below 0 is null).  Every part has the same rows.  A row with a null
+        part has no key (d_valid 0) unless that part says null_is_group.  d_rows_select: the device
+        ``msj_select_documents_result`` that counts the rows, read on the device.  capacity: default the rows of the parts.
+        d_offsets (int64, capacity + 1), d_valid (uint8, capacity), d_bytes (uint8, capacity * W, 16-byte aligned): the
+        caller's or new ones.  Returns (``MsjGroupKeysResult``, d_offsets, d_valid, d_bytes) -- blocking for the 48-byte
+        result; with sync=False the device tensor that holds it, nothing waited for."""
+        parts = [p if isinstance(p, (tuple, list)) else (p, False) for p in parts]
+        if not 1 <= len(parts) <= _lib.KEY_MAX_PARTS:
+            raise ValueError(f"1 to {_lib.KEY_MAX_PARTS} parts: {len(parts)}")
+        table = (_lib.MsjKeyPart * len(parts))()
+        stride, W = None, 0
+        for j, (t, null_is_group) in enumerate(parts):
+            if t.dtype == torch.int64:
+                _check_records(t, "a NUMBER part")
+                kind, rows = _lib.KEY_NUMBER, t.shape[0]
+            elif t.dtype == torch.int32 and t.dim() == 1 and t.stride(-1) == 1:
+                kind, rows = _lib.KEY_CODE, t.numel()
+            else:
+                raise ValueError("a part is int64 records of shape (rows, 2) or a contiguous int32 tensor of codes")
+            if stride is not None and rows != stride:
+                raise ValueError("every part has the same rows")
+            stride = rows
+            table[j].d_column, table[j].kind, table[j].flags = t.data_ptr(), kind, _lib.KEY_NULL_IS_GROUP if null_is_group else 0
+            W += _lib.KEY_PART_BYTES[kind]
+        capacity = stride if capacity is None else int(capacity)
+        capacity, d_offsets, d_valid = self._column_rows(parts[0][0], d_offsets, d_valid, capacity)
+        bytes_capacity = capacity * W if d_bytes is None else d_bytes.numel()
+        if d_bytes is None:
+            d_bytes = torch.empty(max(bytes_capacity, 1), dtype=torch.uint8, device=self.device)
+        d_result = self._result(d_result)
+        rc = self.lib.msj_group_keys_device(self.ctx, table, len(parts), stride, _ptr(d_rows_select), _ptr(d_offsets), _ptr(d_valid), _ptr(d_bytes),
+                                            capacity, bytes_capacity, _ptr(d_result), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"msj_group_keys_device failed: {rc}")
+        res = _lib.MsjGroupKeysResult.from_buffer_copy(d_result.cpu().numpy().tobytes()) if sync else d_result
+        return res, d_offsets, d_valid, d_bytes
+
     def aggregate(self, d_fields, d_rows_select, d_codes=None, n_groups=1, d_n_groups=None, d_groups=None, groups_capacity=None,
                   d_result=None, sync=True):
         """Count, sum, min and max per group (``msj_aggregate_device``), exact and bit for bit the same from run to run, all

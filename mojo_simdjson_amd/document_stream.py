@@ -304,6 +304,47 @@ def _cast(window, d_rows, d_select, rows, kind, unit, keep_numbers, what):
     return d_out[:rows], d_out_select
 
 
+def _bucket_numbers(width, origin, unit):
+    """A bucket's width and origin as the two int64 ``bucket_rows`` takes.  width: an int, or a ``datetime.timedelta`` that is
+    a whole number of `unit`; origin: an int, or a ``datetime.datetime`` (``datetime_units``).  unit: the unit of the column's
+    timestamp cast, None without one -- then only ints will do."""
+    def needs_unit(what, value):
+        if unit is None:
+            raise ValueError(f"a {what} needs its column cast to a timestamp: {value!r}")
+
+    if isinstance(width, datetime.timedelta):
+        needs_unit("timedelta width", width)
+        micros = ((width.days * 86400 + width.seconds) * 10**6 + width.microseconds) * _lib.CAST_UNIT_PER_SECOND[unit]
+        if micros % 10**6:
+            raise ValueError(f"the width is no whole number of {unit!r}: {width!r}")
+        width = micros // 10**6
+    if isinstance(origin, datetime.datetime):
+        needs_unit("datetime origin", origin)
+        origin = datetime_units(origin, unit)
+    if isinstance(width, bool) or isinstance(origin, bool) or not isinstance(width, int) or not isinstance(origin, int):
+        raise ValueError(f"a width is an int or a timedelta, an origin an int or a datetime: {width!r}, {origin!r}")
+    if not 1 <= width < 1 << 63 or not -(1 << 63) <= origin < 1 << 63:
+        raise ValueError(f"a width lies in 1..2^63 - 1, an origin in int64: {width!r}, {origin!r}")
+    return width, origin
+
+
+def _bucket(window, d_rows, d_select, rows, width, origin, cast, what):
+    """``bucket_rows`` over `rows` records (int64[rows, 2]), cast first where asked -> (the bucket records int64[rows, 2], the
+    uint8[48] select result that goes with them).  Only 48-byte results come to the host."""
+    w = window
+    unit = None
+    if cast is not None:
+        kind, unit = _cast_spec(cast)
+        d_rows, d_select = _cast(w, d_rows, d_select, rows, kind, unit, kind == "number", what)
+        unit = unit if kind == "timestamp" else None
+    width, origin = _bucket_numbers(width, origin, unit)
+    d_res, d_out, d_out_select = w.dev.bucket_rows(_or_blank(d_rows, rows).contiguous(), d_select, width, origin, capacity=rows, sync=False)
+    code = _code(d_res)
+    if code != 0:
+        raise DocumentStreamError(code, f"window at {w.base}: {what} could not be put into buckets")
+    return d_out[:rows], d_out_select
+
+
 def _cast_for_filter(window, d_fields, d_select, rows, specs, cast, index, what):
     """What ``where(..., cast=...)`` hands the filter: the columns the predicates name, copied, the cast ones replaced by
     their cast records (a quoted number next to a plain one is kept), and the specs re-numbered onto that copy with every
@@ -515,10 +556,117 @@ class RunningDictionary:
         return DictionaryColumn(codes[:rows], self.offsets[:need + 1], self.bytes[:need_bytes], first, valid, self.dev)
 
 
+def _key_specs(keys):
+    """The keys of ``group_by``: "/status" | (path, "string" | "number"[, {"nulls"}]) | (path, "bucket", width[, origin][,
+    {"nulls"}]) -> [(path, kind, width, origin, null_is_group)]"""
+    if not isinstance(keys, list):
+        raise ValueError(f"the keys are a list: {keys!r}")
+    out = []
+    for key in keys:
+        rest = list(key[1:]) if isinstance(key, tuple) else ["string"]
+        path = key[0] if isinstance(key, tuple) else key
+        nulls = bool(rest) and isinstance(rest[-1], (set, frozenset))
+        if nulls and set(rest.pop()) != {"nulls"}:
+            raise ValueError(f'the flags of a key are {{"nulls"}}: {key!r}')
+        kind = rest[0] if rest else None
+        if kind in ("string", "number") and len(rest) == 1:
+            out.append((path, kind, None, None, nulls))
+        elif kind == "bucket" and len(rest) in (2, 3):
+            out.append((path, kind, rest[1], rest[2] if len(rest) == 3 else 0, nulls))
+        else:
+            raise ValueError(f'a key is a path, (path, "string" | "number") or (path, "bucket", width[, origin]), with {{"nulls"}} behind it '
+                             f"where no value is a group of its own: {key!r}")
+    if not 1 <= len(out) <= _lib.KEY_MAX_PARTS:
+        raise ValueError(f"1 to {_lib.KEY_MAX_PARTS} keys: {len(out)}")
+    return out
+
+
+def _decode_number_part(part):
+    """The eleven bytes of a NUMBER part -> the canonical value: an integer inside int64 as an ``int``, anything else the
+    ``float``; None for a null part (group_keys_math.h: decode_number)"""
+    if part[0] != 0:
+        return None
+    hi, lo = int.from_bytes(part[1:9], "big"), int.from_bytes(part[9:11], "big")
+    d = struct.unpack("<d", struct.pack("<Q", hi ^ (1 << 63) if hi >> 63 else ~hi & ((1 << 64) - 1)))[0]
+    if d.is_integer() and -(1 << 63) <= int(d) + lo < 1 << 63:
+        return int(d) + lo
+    return d
+
+
+def _decode_keys(offsets, data, n, kinds, strings):
+    """n keys of a key dictionary (host: offsets a list, data bytes) -> a list of tuples.  kinds: "string" | "number" per
+    part; strings: per part the string dictionary's values, None for a number part"""
+    out = []
+    for g in range(n):
+        key, at, row = data[offsets[g]:offsets[g + 1]], 0, []
+        for kind, values in zip(kinds, strings):
+            if kind == "number":
+                row.append(_decode_number_part(key[at:at + 11]))
+                at += 11
+            else:
+                code = int.from_bytes(key[at + 1:at + 5], "big")
+                row.append(values[code] if key[at] == 0 and code < len(values) else None)
+                at += 5
+        out.append(tuple(row))
+    return out
+
+
+class GroupKeys(DictionaryColumn):
+    """The groups of ``group_by`` ON THE DEVICE: a ``DictionaryColumn`` over the rows' composite byte keys
+    (``msj_group_keys_device``, then ``msj_dictionary_device`` or a ``RunningGroups``' dictionary).  codes int32[rows]: the
+    row's group in the order of first appearance, -1 for a row without a key (a part without a value that is no group of its
+    own); first int32[n_distinct]: the row group g first appears in; offsets / bytes: the distinct keys, key_width bytes
+    each -- per part a tag byte, then a number's order-preserving key or a string's code; kinds: "string" | "number" per
+    part; parts: per part the string part's ``DictionaryColumn``, None for a number.  ``counts()`` as every dictionary
+    column's.  ``order()``: the groups in key order -- the first key major, numbers as reals, a string part by its code (the
+    order of first appearance; ``RunningDictionary.order`` has the byte order), no value last."""
+
+    def __init__(self, column, key_width, kinds, parts):
+        super().__init__(column.codes, column.offsets, column.bytes, column.first, column.valid, column.dev)
+        self.key_width, self.kinds, self.parts = key_width, list(kinds), list(parts)
+
+    def values(self):
+        """The groups' keys as tuples, decoded FROM THE KEY BYTES on the host: a number part as an ``int`` (an integer inside
+        int64: 200, 200.0 and 2e2 are the one group 200) or a ``float``, a string part as its dictionary's value, a part
+        without a value as None.  The key dictionary and the string parts' dictionaries come to the host, the codes do not."""
+        strings = [p.values() if p is not None else None for p in self.parts]
+        return _decode_keys(self.offsets.cpu().tolist(), self.bytes.cpu().numpy().tobytes(), self.n_distinct, self.kinds, strings)
+
+
+class RunningGroups:
+    """The groups a stream carries from window to window ON THE DEVICE: one ``RunningDictionary`` per string part of `keys`
+    and one for the composite keys.  ``win.group_by(keys, dictionary=rg)`` and ``win.stats(paths, by=keys, dictionary=rg)``
+    encode each window against them, so that group g is the same key tuple in every window and the windows' records merge
+    by position (include/msj_stage1.h, "Merging two windows' records").  keys: as ``group_by`` takes them, the same in every
+    window."""
+
+    def __init__(self, dev, keys, dict_capacity=1024):
+        self.dev, self.specs = dev, _key_specs(keys)
+        self.kinds = ["string" if s[1] == "string" else "number" for s in self.specs]
+        self.strings = [RunningDictionary(dev, dict_capacity) if k == "string" else None for k in self.kinds]
+        width = sum(5 if k == "string" else 11 for k in self.kinds)
+        self.keys = RunningDictionary(dev, dict_capacity, dict_capacity * width)
+
+    @property
+    def n_distinct(self):
+        return self.keys.n_distinct
+
+    def values(self):
+        """The key tuples in group order, as ``GroupKeys.values`` gives them: the dictionaries come to the host."""
+        k = self.keys
+        strings = [rd.values() if rd is not None else None for rd in self.strings]
+        return _decode_keys(k.offsets[:k._n + 1].cpu().tolist(), k.bytes[:k._n_bytes].cpu().numpy().tobytes(), k._n, self.kinds, strings)
+
+    def order(self, max_rounds=None):
+        """The groups held so far in key order ON THE DEVICE -> ``DictionaryOrder`` (see ``GroupKeys``)."""
+        return self.keys.order(max_rounds)
+
+
 class GroupStats:
     """Count, sum, min and max per group ON THE DEVICE (``msj_aggregate_device``; ``Window.stats``, ``RowSelection.stats``,
     ``ElementFields.stats``, ``ListColumn.stats``).  keys: the ``DictionaryColumn`` of the grouping path, whose value g names
-    group g (None: one group, or a group per row of a list column); pointers: the aggregated columns' names; records
+    group g -- for a list of keys the ``GroupKeys``, whose value g is a tuple -- (None: one group, or a group per row of a
+    list column); pointers: the aggregated columns' names; records
     uint8[n_columns, n_groups, 48], the ``msj_aggregate`` records as the call wrote them, and as views of them: n_rows
     int64[n_groups]; n_values, sums, mins, maxs int64[n_columns, n_groups] -- sums, mins and maxs hold an int64 where
     sum_types / min_types / max_types (uint8, the same shape) say ord("l"), the pattern of a double where they say ord("d"),
@@ -790,7 +938,9 @@ class _Records:
         """Count, sum, min and max of paths per group ON THE DEVICE (``msj_aggregate_device``) -> ``GroupStats``:
         ``win.stats(["/latency_ms"], by="/status")`` is how many lines, what total, smallest and largest latency per status.
         by: a path whose strings are dictionary-encoded first (``categories``): group g is the g-th distinct value, a row
-        without a string is in no group; None: all rows are one group.  An int64 stays an int64 -- the sum of integers is
+        without a string is in no group; None: all rows are one group; a LIST of keys as ``group_by`` takes them --
+        ``by=["/status", ("/ts", "bucket", timedelta(minutes=1))]`` with ``cast={"/ts": ("timestamp", "ms")}`` is errors per
+        minute per status --: ``keys`` is then the ``GroupKeys``, "key" a tuple, and `dictionary` a ``RunningGroups``.  An int64 stays an int64 -- the sum of integers is
         the exact integer while it fits -- and a sum with doubles is rounded once: the same bits from run to run and for every
         order of the lines.  cast: ``{"/ts": ("timestamp", "ms"), "/price": "number"}`` as in ``where``, so that a timestamp
         has a minimum and a maximum and a quoted number a sum.  The call's 48-byte result comes to the host.
@@ -798,6 +948,67 @@ class _Records:
         n_distinct after this window, so that record g is the same value in every window and the windows' records merge
         by position (include/msj_stage1.h, "Merging two windows' records"); frozen=True as in ``categories``."""
         return self._grouped(paths, by, cast, dictionary=dictionary, frozen=frozen)
+
+    def bucket(self, path_or_index, width, origin=0, cast=None):
+        """One path's numbers floored to multiples of a width ON THE DEVICE (``msj_bucket_rows_device``) -> (records
+        int64[rows, 2], the uint8[48] ``msj_select_documents_result`` that goes with them), as ``Window.cast`` returns its
+        records: ``origin + floor((floor(v) - origin) / width) * width`` as an exact int64, a floor also below the origin.
+        cast: "number", "timestamp" or ("timestamp", unit), applied first as in ``where``: ``win.bucket("/ts",
+        datetime.timedelta(minutes=1), cast=("timestamp", "ms"))`` is every line's minute.  width: an int of at least 1, or a
+        ``timedelta`` that is a whole number of the cast's unit; origin: an int, or a ``datetime`` in the cast's unit.  A
+        value that is no number becomes code 17, a bucket outside int64 code 9.  Only 48-byte results come to the host."""
+        w, fields, rows, p, what = self._at(path_or_index)
+        return _bucket(w, fields[p], self.d_select, rows, width, origin, cast, what)
+
+    def group_by(self, keys, cast=None, dictionary=None, frozen=False):
+        """The rows grouped by 1 to 8 keys at once ON THE DEVICE (``msj_group_keys_device``, then ``msj_dictionary_device``)
+        -> ``GroupKeys``.  keys, a list, the major key first: ``"/status"`` -- a string part: the path's ``categories`` codes;
+        ``("/status", "string", {"nulls"})`` -- the same, and a row without a string is a group of its own instead of being in
+        none; ``("/code", "number")`` -- the numbers as reals: 200, 200.0 and 2e2 are one group; ``("/ts", "bucket", width[,
+        origin])`` -- ``bucket``'s numbers.  cast: ``{"/ts": ("timestamp", "ms")}``, applied first as in ``where``.
+        dictionary: a ``RunningGroups`` made for the same keys: the groups are then ITS groups, the same in every window;
+        frozen=True: nothing is added to it, a row whose key it does not hold is -2 (a string it does not hold is a part
+        without a value).  Only 48- and 64-byte results come to the host.  Out of scope: calendar months and time zones, more than 8 keys, keys on raw JSON text (``raw`` +
+        ``categories`` serve those)."""
+        w, fields, index = self._window, self._records, self.paths.index
+        rows = fields.shape[1]
+        specs = _key_specs(keys)
+        if dictionary is not None and (not isinstance(dictionary, RunningGroups) or dictionary.specs != specs):
+            raise ValueError("the dictionary of a list of keys is a RunningGroups made for the same keys")
+        if frozen and dictionary is None:
+            raise ValueError("frozen=True needs a dictionary")
+        casts = {index(k): v for k, v in (cast or {}).items()}
+        tensors, kinds, parts = [], [], []
+        for j, (path, kind, width, origin, nulls) in enumerate(specs):
+            c = index(path)
+            what = f"path {c} of {self._rows_are}"
+            if kind == "string":
+                column = self.categories(path, dictionary=dictionary.strings[j] if dictionary is not None else None, frozen=frozen)
+                tensors.append((_or_blank(column.codes, rows).contiguous(), nulls))
+                parts.append(column)
+            elif kind == "bucket":
+                tensors.append((_or_blank(_bucket(w, fields[c], self.d_select, rows, width, origin, casts.get(c), what)[0], rows).contiguous(), nulls))
+                parts.append(None)
+            else:
+                records = fields[c]
+                if c in casts:
+                    k, unit = _cast_spec(casts[c])
+                    records = _cast(w, records, self.d_select, rows, k, unit, k == "number", what)[0]
+                tensors.append((_or_blank(records, rows).contiguous(), nulls))
+                parts.append(None)
+            kinds.append("string" if kind == "string" else "number")
+        d_res, d_off, d_valid, d_bytes = w.dev.group_keys(tensors, self.d_select, capacity=rows, sync=False)
+        code = _code(d_res)
+        if code != 0:
+            raise DocumentStreamError(code, f"window at {w.base}: the keys of {self._rows_are} could not be laid out")
+        width = sum(_lib.KEY_PART_BYTES[_lib.KEY_CODE if k == "string" else _lib.KEY_NUMBER] for k in kinds)
+        column = (d_off[:rows + 1], d_bytes[:rows * width], d_valid[:rows].view(torch.bool))
+        what = f"the keys of {self._rows_are}"
+        if dictionary is not None:
+            encoded = dictionary.keys.encode(column, frozen=frozen, what=f"window at {w.base}: {what}")
+        else:
+            encoded = _dictionary(w, column, what)
+        return GroupKeys(encoded, width, kinds, parts)
 
     def _grouped(self, paths, by, cast, d_list_offsets=None, dictionary=None, frozen=False):
         """``stats``; d_list_offsets: a list column's offsets over these rows, for a group per row of it -- the element's
@@ -807,7 +1018,10 @@ class _Records:
         columns = [index(p) for p in paths]
         if by is None and (dictionary is not None or frozen):
             raise ValueError("a dictionary groups the rows of `by`")
-        keys = self.categories(by, dictionary=dictionary, frozen=frozen) if by is not None else None
+        if isinstance(by, list):
+            keys = self.group_by(by, cast=cast, dictionary=dictionary, frozen=frozen)
+        else:
+            keys = self.categories(by, dictionary=dictionary, frozen=frozen) if by is not None else None
         if keys is not None:
             d_codes, n_groups = keys.codes, keys.n_distinct
         elif d_list_offsets is not None:
@@ -1008,6 +1222,11 @@ class ListColumn:
         of maps) -- ON THE DEVICE -> ``MapColumn`` with one row per element of this column; an element that is no object is a
         row that is not valid."""
         return self._one.entries(0, entries_capacity)
+
+    def bucket(self, width, origin=0, cast=None):
+        """The elements that are numbers floored to multiples of a width ON THE DEVICE -> (records int64[n_elements, 2], their
+        select result), as every record view's ``bucket``."""
+        return self._one.bucket(0, width, origin, cast)
 
     def order(self, descending=False, limit=None, cast=None, values_only=False):
         """The element numbers in the order of the elements' values ON THE DEVICE -> (order int32[K], its select result), as
